@@ -7,6 +7,7 @@ kNN-bridge pairs/s (config C5) as an extra field.  One JSON line on rank 0.
   python bench.py --config c3                                    # config C3: Twitter_Graph stand-in, F=300, hidden 128
   python bench.py --config c2                                    # config C2: Sync-RD_intra 10k nodes, hidden 64
   python bench.py --config c5                                    # config C5 alone: 100k x 100k cosine kNN bridge
+  python bench.py --dump-outputs DIR                             # + the last timed step's outputs as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -93,13 +94,20 @@ def parse():
                          "of the two is `value`, both are reported")
     ap.add_argument("--graph-timeout", type=float, default=60.0,
                     help="seconds the HIP-graph phase may take before the eager result is printed and the process exits non-zero")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write the arrays the timed path returned in its last timed step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed seeded row sample when larger; N>1: rank 0's rows).  "
+                         "The inputs are the same on every run; compare with a tolerance, since the domain sums are "
+                         "accumulated with floating-point atomics and the last bits vary from run to run")
     args = ap.parse_args()
     dflt = {"c2": (64, 64), "c3": (300, 128), "c4": (128, 128), "c5": (128, 128)}[args.config]
     args.feat = dflt[0] if args.feat is None else args.feat
     args.hidden = dflt[1] if args.hidden is None else args.hidden
-    small = args.config in ("c2", "c3")
-    args.steps = (200 if small else 20) if args.steps is None else args.steps
-    args.warmup = (20 if small else 5) if args.warmup is None else args.warmup
+    # c5: one kNN call is a step (3 timed after 1 untimed by default)
+    args.steps = {"c2": 200, "c3": 200, "c5": 3}.get(args.config, 20) if args.steps is None else args.steps
+    args.warmup = {"c2": 20, "c3": 20, "c5": 1}.get(args.config, 5) if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -288,6 +296,37 @@ def knn_cpu_baselines(n, k=20, sample_queries=8192):
     return port, gemm
 
 
+DUMP_BUDGET = 64 << 20          # bytes written by --dump-outputs, .npy headers included
+
+
+def dump_outputs(dirname, arrays, source):
+    """--dump-outputs: `arrays` (name -> tensor, rows on axis 0) -> <dirname>/<name>.npy.  Float tensors keep float64 or
+    become float32, integer tensors become float64 (exact below 2**53).  When the whole is larger than DUMP_BUDGET every
+    array keeps the same fraction of its rows, drawn with a fixed seed and kept in order; their ids go to
+    <dirname>/<name>.rows.npy.  Equal shapes give equal samples, so two builds compare output for output.  `source` names
+    the step the arrays come from in the note on stderr."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    room = DUMP_BUDGET - 2 * 4096 * len(host)          # header allowance for each array and its row ids
+    os.makedirs(dirname, exist_ok=True)
+    written = 0
+    for name, a in host.items():
+        row_bytes = a.nbytes // max(a.shape[0], 1) + 8                      # a row and its id
+        keep = max(1, int(room * a.nbytes / max(total, 1)) // row_bytes)
+        if total > room and keep < a.shape[0]:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, f"{name}.rows.npy"), rows.astype(np.float64))
+            written += os.path.getsize(os.path.join(dirname, f"{name}.rows.npy"))
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+        written += os.path.getsize(os.path.join(dirname, f"{name}.npy"))
+    print(f"bench: outputs of {source} -> {dirname}: {', '.join(host)} ({written / 2**20:.1f} MiB"
+          f"{', row sample' if total > room else ''})", file=sys.stderr, flush=True)
+
+
 def max_over_ranks(vals, dev):
     """MAX all-reduce of a few floats; on the host when the process group is gloo (the `--dist-backend gloo` rehearsal of
     the N>1 code path with several ranks on one GPU: RCCL refuses two ranks per device)."""
@@ -298,17 +337,18 @@ def max_over_ranks(vals, dev):
 
 
 # ------------------------------------------------------------------------------------------------ C5: kNN bridge
-def knn_bench(args, dev, rank=0, world=1):
+def knn_bench(args, dev, rank=0, world=1, steps=3, warmup=1):
     """C5: cosine kNN bridge through the library's sharded entry point (bridge.sharded_cosine_topk_edges): query rows
     are sharded over the ranks, each rank normalises ITS slice of the candidates and one all_gather makes them whole
-    (SURVEY 8(e)); the job time is the max over ranks.  The top-k call itself is timed with HIP events on the launch stream."""
+    (SURVEY 8(e)); the job time is the max over ranks.  The top-k call itself is timed with HIP events on the launch stream.
+    `warmup` untimed calls, then `steps` timed ones (median); the last call's outputs are returned under "outputs"."""
     from bridged_gnn_amd import bridge, synth
     n = args.knn_n
     lo, hi = rank * n // world, (rank + 1) * n // world
     q = torch.from_numpy(synth.gaussian_embeddings(n, 128, seed=0)[lo:hi]).to(dev)
     c_mine = torch.from_numpy(synth.gaussian_embeddings(n, 128, seed=1)[lo:hi]).to(dev)   # this rank's share of the candidates
     ts, ks = [], []
-    for it in range(4):
+    for it in range(warmup + steps):
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
@@ -321,8 +361,8 @@ def knn_bench(args, dev, rank=0, world=1):
             dt = max_over_ranks([dt], dev)[0]
         ts.append(dt)
         ks.append(s.elapsed_time(e))
-    t = float(np.median(ts[1:]))
-    tk = float(np.median(ks[1:])) * 1e-3
+    t = float(np.median(ts[warmup:]))
+    tk = float(np.median(ks[warmup:])) * 1e-3
     pairs = float(n) * float(n)
     pairs_rank = float(hi - lo) * float(n)
     pieces = int(os.environ.get("BGNN_KNN_FAST_PRODUCTS", "1"))     # bf16 MFMA products per pair term in the fast pass: cand_hi . query_hi
@@ -336,7 +376,8 @@ def knn_bench(args, dev, rank=0, world=1):
                          "algorithmic_tflops": pairs_rank * 256 / tk / 1e12,
                          "note": "achieved = bf16 MFMA flops actually issued (2 d x `bf16_products_per_pair_term` per pair) / time of the "
                                  "whole top-k call; the fast pass is bound by the shortlist upkeep (vector / LDS issue), not by the "
-                                 "matrix pipe: one product per term instead of three cut the matrix work 3x and the time 1.6x"}}
+                                 "matrix pipe: one product per term instead of three cut the matrix work 3x and the time 1.6x"},
+            "outputs": {"edge_index": ei.t(), "topk_index": idx, "topk_prob": val, "fallback_counts": nfb.reshape(1, -1)}}
 
 
 # ------------------------------------------------------------------------------------------------ HIP-graph phase
@@ -347,7 +388,7 @@ def graph_phase(args, runner, barrier, use_dist, dev, rank, world, out, units):
     outputs and the replay is faster.  The ranks agree through the rendezvous STORE (host side, no collective) whether
     everybody captured before anybody replays, so a failed capture is a clean fallback to the eager line; a replay that
     stalls (a graph-launched collective is the one thing that cannot be rehearsed on a one-GPU box) trips the watchdog,
-    which prints the eager line and exits NON-ZERO."""
+    which prints the eager line and exits NON-ZERO.  -> the replayed outputs on rank 0 when the replay became `value`, else None."""
     import threading
     done = threading.Event()
 
@@ -406,6 +447,7 @@ def graph_phase(args, runner, barrier, use_dist, dev, rank, world, out, units):
         out["config"]["execution"] = ("HIP-graph replay: the whole forward (all launches" +
                                       (" and the RCCL collectives" if use_dist else "") +
                                       ") captured once, outputs checked against the eager forward, K replays timed")
+        return [t.clone() for t in got]          # the last timed replay's outputs (the graph's pool goes with `g`)
 
 
 class AggTimer:
@@ -526,15 +568,18 @@ def main():
         torch.cuda.synchronize()
 
     if args.config == "c5":                              # the kNN bridge alone
-        knn = knn_bench(args, dev, rank, world)
+        knn = knn_bench(args, dev, rank, world, args.steps, args.warmup)
+        knn_out = knn.pop("outputs")
         if rank == 0:
             out = {"metric": "knn_bridge_pairs_per_sec", "value": knn["pairs_per_s"], "unit": "pairs/s", "n_gpus": world,
-                   "steps": 3, "warmup": 1, "ms_per_step": knn["ms"], "higher_is_better": True, "scaling": "strong",
+                   "steps": args.steps, "warmup": args.warmup, "ms_per_step": knn["ms"], "higher_is_better": True, "scaling": "strong",
                    "vs_baseline": None, "dtype": "f32 (bf16-piece MFMA shortlist, fp64 canonical re-score)", "data": "synthetic",
                    "config": {"workload": knn["workload"], "parallelism": "single" if world == 1 else f"query rows x{world}"},
                    "roofline": knn["roofline"], "fallback_rows": knn["fallback_rows"]}
             if world == 1 and not args.no_cpu:
                 out["cpu_baseline"], out["cpu_baseline_gemm"] = knn_cpu_baselines(args.knn_n)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, knn_out, "the last timed kNN call (this rank's query rows)")
             print(json.dumps(out), flush=True)
         if use_dist:
             torch.distributed.barrier()
@@ -690,6 +735,8 @@ def main():
                 train["graph_replay_ms_per_train_step"] = f"capture failed: {type(e).__name__}: {str(e)[:160]}"
         del tmodel, opt
     knn = knn_bench(args, dev, rank, world) if (not args.no_knn and args.config == "c4") else None   # every rank takes part
+    if knn is not None:
+        del knn["outputs"]
     out = None
     if rank == 0:
         n_local = N if not use_dist else len(pk.owned_global)
@@ -767,9 +814,15 @@ def main():
                 out["knn"]["cpu_baseline"], out["knn"]["cpu_baseline_gemm"] = knn_cpu_baselines(args.knn_n)
         out["eager_ms_per_step"] = ms_step
         out["config"]["execution"] = "eager launches"
+    replay_out = None
     if not args.no_graph_replay:
-        graph_phase(args, runner, barrier, use_dist, dev, rank, world, out, 4 * Eprime)
+        replay_out = graph_phase(args, runner, barrier, use_dist, dev, rank, world, out, 4 * Eprime)
     if rank == 0:
+        if args.dump_outputs:
+            arrays = dict(zip(("base", "target", "target_hat"), gpu_out if replay_out is None else replay_out))
+            if use_dist:
+                arrays["node_ids"] = pk.owned_global                # global node id of each row
+            dump_outputs(args.dump_outputs, arrays, "the last eager timed step" if replay_out is None else "the last timed HIP-graph replay")
         print(json.dumps(out), flush=True)
     if use_dist:
         torch.distributed.barrier()
