@@ -21,6 +21,12 @@ Round 2 (run alone with `--only c3,layers,a4,assembly`; the sections above are u
   ktgnn_layers.npz       layer_num = 1 (KTGNN.py:344-347) and layer_num = 3 (:348-358) eval forwards on a small graph
   a4_office_a2d.npz      a4 glue: v2 encoders / class probs / get_probs_{cross,within}_domain on enumerated pairs, PairNorm modes
   assembly_office_a2d.npz  merge_graphs (main_bridged_graph.py:163-193) and reorder (:195-222) outputs on the office pieces
+Round 3 (`--only f4`):
+  f4_utils.npz           utils.dataset_conversion / eval_bridged_Graph / eval_homophily on a seeded synthetic graph
+Gradients (`--only grads`; needs office_a2d_graph.npz and partition_office.npz from the full run):
+  grads_office_a2d.npz   one training step's fp64 gradients, outputs, loss terms and BN buffers: office64 / office128
+  grads_small.npz        the same for heads3 / odd4 / c3 / wide5 / l3 / root on two seeded multigraphs (see grads_section;
+                         inputs and weights are regenerated from seeds by oracle/grad_cases.py, large results stored as summaries)
 """
 import argparse
 import os
@@ -252,15 +258,121 @@ def round3_sections(want):
     save("f4_utils.npz", **arrs)
 
 
+def grads_section(KT, want):
+    """`--only grads`: one training step's gradients of the reference's KTGNN_no_complement (train mode, dropout 0, use_bn)
+    in fp64, with the loss of main_graph_knowledge_transfer.py:44-54 computed and back-propagated by the reference's own
+    `train()` (:39-68; its optimizer here holds a dummy tensor, so the model's weights do not move).  The cases, their inputs and
+    their fp32 initial weights come from oracle/grad_cases.py (regenerated from seeds there; only their sha256 is stored); the
+    model is loaded with those weights and then converted (.double()).
+      grads_office_a2d.npz   office64 / office128 on the shipped office A->D graph (undirected, as ktgnn_office.npz)
+      grads_small.npz        heads3 on graph 'm' (4200 nodes), odd4 / c3 / wide5 / l3 / root on graph 's' (700 nodes)
+    Per case (key prefix `<case>.`): data_sha / sd_sha, the state_dict shapes (shape:*), loss [total, l_s, l_t1, l_t2, l_kl], gmax
+    (largest |gradient|), every parameter gradient (grad.<name>:<part>) and dL/dx and the three log-prob outputs (res.*) in the
+    form of grad_cases.summary, the BatchNorm buffers after the forward (bn.*), and the leaky-ReLU / ReLU input counts within
+    1e-6 (and 1e-7) of their tensor's max of zero per call (kinks_*).  Printed, not stored: the fp32-vs-fp64 reference error of
+    every gradient relative to its own max (the floor an fp32 implementation can reach; the fp32 run's CPU reductions are not
+    bit-reproducible from run to run, the fp64 run's stored values are)."""
+    if not want("grads"):
+        return
+    import contextlib
+    import io
+    import torch.nn.functional as TF
+    import grad_cases as GC
+    from torch_geometric.data import Data as SData
+    from torch_geometric.utils import to_undirected as s_to_undirected
+    cwd = os.getcwd()
+    os.chdir(ref_import.REF_CODE)                   # the driver appends ./models to sys.path at import time
+    try:
+        import main_graph_knowledge_transfer as MG
+    finally:
+        os.chdir(cwd)
+    print("[grads] KTGNN_no_complement training-step gradients (fp64) on office A->D and two small multigraphs")
+    g = np.load(os.path.join(OUT, "office_a2d_graph.npz"))
+    ei_o = s_to_undirected(torch.from_numpy(g["edge_index"].astype(np.int64)), num_nodes=g["x"].shape[0])
+    assert np.array_equal(ei_o.numpy(), GC.graph("office")[1])
+    graphs = {t: GC.graph(t) for t in ("office", "s", "m")}
+
+    def step(case, dtype, count_kinks=False):
+        gname, feat, hidden, C, layers, root, seed = GC.CASES[case]
+        x, ei, cm = graphs[gname]
+        x = np.ascontiguousarray(x[:, :feat])
+        y, tm = GC.labels(case, x.shape[0])
+        model = KT.KTGNN_no_complement(feat, C, layers, hidden, root_weight=root, use_bn=True, dim_share=feat, dropout=0.0,
+                                       need_complement=False)
+        sd0 = GC.init_state(case, model.state_dict())
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in sd0.items()})
+        model = model.to(dtype).train()
+        xt = torch.from_numpy(x).to(dtype).requires_grad_(True)
+        data = SData(x=xt, edge_index=torch.from_numpy(ei), y=torch.from_numpy(y), train_mask=torch.from_numpy(tm),
+                     central_mask=torch.from_numpy(cm))
+        outs, kinks = [], {"leaky_relu": [], "relu": []}
+        hook = model.register_forward_hook(lambda m, i, o: outs.append(o))
+        orig = {k: getattr(TF, k) for k in kinks}
+
+        def counting(name):
+            def f(inp, *a, **k):
+                v = inp.detach().abs()
+                kinks[name].append((int((v <= 1e-6 * v.max()).sum()), int((v <= 1e-7 * v.max()).sum())))
+                return orig[name](inp, *a, **k)
+            return f
+        if count_kinks:
+            for k in kinks:
+                setattr(TF, k, counting(k))
+        try:
+            opt = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=0.0)
+            with contextlib.redirect_stdout(io.StringIO()):
+                loss, l_t2, l_t1, l_kl = MG.train(data, model, opt, gnn="KTGNN", Lambda=1.0)
+        finally:
+            for k, f in orig.items():
+                setattr(TF, k, f)
+            hook.remove()
+        l_s = (4.0 * (loss - l_kl) - l_t1 - l_t2) / 2.0
+        grads = {k: p.grad.detach().double().numpy() for k, p in model.named_parameters()}
+        bufs = {k: v.detach().numpy().copy() for k, v in model.named_buffers()}
+        return dict(sd0=sd0, data_sha=GC.sha(x, ei, cm, y, tm), outs=[o.detach().double().numpy() for o in outs[0][:3]],
+                    loss=np.array([loss, l_s, l_t1, l_t2, l_kl]), grads=grads, dx=xt.grad.double().numpy(), bufs=bufs,
+                    kinks=kinks)
+
+    files = {"grads_office_a2d.npz": {}, "grads_small.npz": {}}
+    for case in GC.CASES:
+        r64, r32 = step(case, torch.float64, count_kinks=True), step(case, torch.float32)
+        p = case + "."
+        gmax = max(float(np.abs(v).max()) for v in r64["grads"].values())
+        a = {p + "data_sha": np.array(r64["data_sha"]), p + "sd_sha": np.array(GC.sha(*(r64["sd0"][k] for k in sorted(r64["sd0"])))),
+             p + "loss": r64["loss"], p + "gmax": np.float64(gmax),
+             p + "kinks_leaky_relu": np.array(r64["kinks"]["leaky_relu"], np.int32), p + "kinks_relu": np.array(r64["kinks"]["relu"], np.int32)}
+        a.update({f"{p}shape:{k}": np.array(v.shape, np.int64) for k, v in r64["sd0"].items()})
+        for k, v in r64["grads"].items():
+            a.update(GC.pack(p + "grad.", k, GC.summary(v)))
+        for nm, v in zip(("logp_base", "logp_target", "logp_target_hat", "dx"), r64["outs"] + [r64["dx"]]):
+            a.update(GC.pack(p + "res.", nm, GC.summary(v)))
+        a.update({f"{p}bn.{k}": v for k, v in r64["bufs"].items()})
+        floors = {}                    # relative to the tensor's max; to the model's largest gradient where the tensor's is zero
+        for k, v in r64["grads"].items():
+            m = float(np.abs(v).max())
+            floors[k] = float(np.abs(r32["grads"][k] - v).max()) / (m if m >= 1e-9 * gmax else gmax)
+        floors["dx"] = float(np.abs(r32["dx"] - r64["dx"]).max() / np.abs(r64["dx"]).max())
+        worst = max(floors, key=floors.get)
+        print(f"  {case}: loss {r64['loss'][0]:.6f}; fp32 vs fp64 worst {floors[worst]:.2e} ({worst}), dx {floors['dx']:.2e}; "
+              f"leaky-relu inputs within 1e-6 / 1e-7 of max per call {[k[0] for k in r64['kinks']['leaky_relu']]} / "
+              f"{[k[1] for k in r64['kinks']['leaky_relu']]}, relu {[k[0] for k in r64['kinks']['relu']]}")
+        for k, v in floors.items():
+            print(f"      floor {k:40s} {v:.2e}")
+        files[GC.fixture_file(case)].update(a)
+    for name, arrs in files.items():
+        save(name, **arrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="comma list of round-2 / round-3 sections (c3,layers,a4,assembly,f4); default: everything")
+    ap.add_argument("--only", default="", help="comma list of round-2 / round-3 / gradient sections (c3,layers,a4,assembly,f4,grads); default: everything")
     only = [t for t in ap.parse_args().only.split(",") if t]
     os.makedirs(OUT, exist_ok=True)
     KT, MD, BG = ref_import.import_reference()
     if only:
         round2_sections(KT, MD, BG, lambda t: t in only)
         round3_sections(lambda t: t in only)
+        grads_section(KT, lambda t: t in only)
         print("done")
         return
     import torch_geometric
@@ -483,6 +595,7 @@ def main():
          seed_src=np.int64(21), seed_tar=np.int64(22), e_sim=vals.numpy(), idx=idxs.numpy().astype(np.int32))
     round2_sections(KT, MD, BG, lambda t: True)
     round3_sections(lambda t: True)
+    grads_section(KT, lambda t: True)
     print("done")
 
 

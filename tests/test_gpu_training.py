@@ -172,21 +172,15 @@ def test_training_steps_follow_the_autograd_oracle(n, feat, hidden, C, ne):
         loss.backward()
         opt.step()
         losses.append(loss.item())
-    # ---- oracle: same model structure in plain CPU torch
+    # ---- oracle: the whole-model train-mode step in plain CPU torch (OT.ktgnn_train, pinned to the reference's own fp64
+    #      gradients by tests/test_oracle_torch.py); the module only holds the parameters and buffers for Adam
     class Ref(torch.nn.Module):
         def __init__(self):
             super().__init__()
             self.m = KTGNN_no_complement(feat, C, 2, hidden, use_bn=True, dim_share=feat, dropout=0.0)
             self.m.load_state_dict(sd0)
-        def conv(self, c, xx, mo, e1, e2):
-            return OT.adaptedconv(xx, mo, e1, e2, dict(c.named_parameters()))
         def forward(self, xx, mo, e1, e2):
-            m = self.m
-            h = torch.relu(m.bns[0](self.conv(m.convs[0], xx, mo, e1, e2)))
-            b = self.conv(m.clf_base, h, mo, e1, e2)
-            hat = self.conv(m.clf_target, m.clf_transformer(h), mo, e1, e2)
-            t = self.conv(m.clf_target, h, mo, e1, e2)
-            return torch.log_softmax(b, 1), torch.log_softmax(t, 1), torch.log_softmax(hat, 1)
+            return OT.ktgnn_train(xx, mo, e1, e2, dict(self.m.named_parameters()), dict(self.m.named_buffers()))
     ref = Ref().train()
     mo = torch.from_numpy(mask)
     e1, e2 = OT.graph_partition(torch.from_numpy(ei), mo)
