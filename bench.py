@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric on MI355X: aggregated edges/s of the KT-GNN eval forward
-(4 AdaptedConv calls: hidden conv + 3 classifier convs, reference models/KTGNN.py:401-435) plus
+(4 AdaptedConv calls: hidden conv + 3 classifier convs, reference models/KTGNN.py:401-435); with --full also
 kNN-bridge pairs/s (config C5) as an extra field.  One JSON line on rank 0.
 
   python bench.py --gpus 1 --steps 20 --warmup 5                 # config C4: 1M nodes / 20M edges, hidden 128
+  python bench.py --full                                         # + roofline, parity, CPU baselines, kNN, training, ...
   python bench.py --config c3                                    # config C3: Twitter_Graph stand-in, F=300, hidden 128
   python bench.py --config c2                                    # config C2: Sync-RD_intra 10k nodes, hidden 64
   python bench.py --config c5                                    # config C5 alone: 100k x 100k cosine kNN bridge
@@ -17,7 +18,12 @@ activations) and one all_to_all of the classifier stage's halo rows per forward 
 the all-reduced domain sums of the input features (static data, like the graph) stay resident per version of x.
 After the eager measurement the same K steps are timed as replays of a HIP graph of the forward
 (outputs checked against the eager ones); the faster execution is `value`, both are in the line.
-`parity` = the timed forward's own outputs against the CPU oracle (all rows at N=1, part of the cpu_baseline leg).
+
+A plain run does only that (set-up, warm-up, the K timed steps both ways, --dump-outputs, the line).  --full adds
+what takes runs of its own: per-step event statistics, the aggregation roofline (kept launches replayed, the
+uniform-random variant of the graph), the partitioned driver at N=1, training steps, the kNN bridge, the CPU
+baselines and `parity` = the timed forward's own outputs against the CPU oracle (all rows at N=1).
+--no-uniform, --no-partitioned-check, --no-knn and --no-cpu leave single legs of a --full run out.
 """
 import argparse
 import json
@@ -73,15 +79,17 @@ def parse():
     ap.add_argument("--classes", type=int, default=2)
     ap.add_argument("--graph", choices=["local", "uniform"], default="local",
                     help="c4: local = bridged/kNN-like locality (p_local=0.9, clusters of 1024); uniform = adversarial")
-    ap.add_argument("--no-uniform", action="store_true", help="c4: skip the uniform-random graph's hidden aggregation (the conservative roofline figure)")
-    ap.add_argument("--no-knn", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (see the module docstring); off by default")
+    ap.add_argument("--no-uniform", action="store_true", help="--full, c4: skip the uniform-random graph's hidden aggregation (the conservative roofline figure)")
+    ap.add_argument("--no-knn", action="store_true", help="--full, c4: skip the kNN bridge")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines and `parity`")
     ap.add_argument("--knn-n", type=int, default=100_000)
     ap.add_argument("--train-steps", type=int, default=-1,
-                    help="also time this many training steps (fwd+bwd+Adam, reference loss); default: 5 for config c4 on one GPU, else 0")
+                    help="also time this many training steps (fwd+bwd+Adam, reference loss); default: 5 for config c4 on one GPU with --full, else 0")
     ap.add_argument("--force-dist", action="store_true", help="run the partitioned (RCCL) code path even at world size 1")
     ap.add_argument("--no-partitioned-check", action="store_true",
-                    help="N=1: skip timing the same forward through the partitioned driver at world size 1 (`partitioned_path_n1`)")
+                    help="--full, N=1: skip timing the same forward through the partitioned driver at world size 1 (`partitioned_path_n1`)")
     ap.add_argument("--no-input-halo-cache", action="store_true",
                     help="N>1: exchange transformed rows for the first conv on every forward instead of keeping the halo rows "
                          "of the (static) input features resident and transforming them locally")
@@ -492,22 +500,24 @@ class AggTimer:
         return s.elapsed_time(e) / reps
 
 
-def time_forward(runner, steps, warmup, barrier, timer):
+def time_forward(runner, steps, warmup, barrier, timer=None, per_step=True):
     """-> (seconds of EXACTLY `steps` forwards between two barriers -- the driver's contract --, outputs, stats).  `stats`:
     `first_forward_ms` (the process's first forward on this workload: allocations, packed weights, the memoised input domain sums)
-    and per-step times of a SECOND loop of max(steps, 20) forwards, each between its own pair of events (median / min / max:
-    SURVEY 8(d) asks for the median of >= 20 forwards; the contract's figure is the mean over the bracketed loop)."""
+    and, with `per_step`, per-step times of a SECOND loop of max(steps, 20) forwards, each between its own pair of events (median /
+    min / max: SURVEY 8(d) asks for the median of >= 20 forwards; the contract's figure is the mean over the bracketed loop)."""
     with torch.no_grad():
         # one untimed forward whose aggregation launches are kept for AggTimer.take_ms.  Its argument tensors stay alive, so
         # the allocator hands the following forwards other blocks: that one-time allocation must happen in the warm-up, not
         # in the timed loop (it cost 1-16 ms there, i.e. up to 0.8 ms per step of a 20-step run)
-        timer.on = True
+        if timer is not None:
+            timer.on = True
         barrier()
         t0 = time.perf_counter()
         out = runner()
         torch.cuda.synchronize()
         first_ms = (time.perf_counter() - t0) * 1e3
-        timer.on = False
+        if timer is not None:
+            timer.on = False
         for _ in range(max(warmup, 1)):
             out = runner()
         barrier()
@@ -529,14 +539,15 @@ def time_forward(runner, steps, warmup, barrier, timer):
         if os.environ.get("BENCH_TRACE"):
             print("host ms per iteration of the bracketed loop:", [round((b - a) * 1e3, 2) for a, b in zip([t0] + host[:-1], host)],
                   "final sync", round((t0 + dt - host[-1]) * 1e3, 2), "MiB allocated/reserved", mem, "allocator", {k: v for k, v in torch.cuda.memory_stats().items() if k in ("num_device_alloc", "num_device_free", "num_alloc_retries")}, file=sys.stderr)
-        n2 = max(steps, 20)
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n2)]
-        for a, b in evs:
-            a.record(); runner(); b.record()
-        torch.cuda.synchronize()
-        per = sorted(a.elapsed_time(b) for a, b in evs)
-    stats = {"first_forward_ms": first_ms, "median_ms_per_step": float(np.median(per)), "min_ms_per_step": per[0],
-             "max_ms_per_step": per[-1], "median_over_steps": n2}
+        stats = {"first_forward_ms": first_ms}
+        if per_step:
+            n2 = max(steps, 20)
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n2)]
+            for a, b in evs:
+                a.record(); runner(); b.record()
+            torch.cuda.synchronize()
+            per = sorted(a.elapsed_time(b) for a, b in evs)
+            stats.update(median_ms_per_step=float(np.median(per)), min_ms_per_step=per[0], max_ms_per_step=per[-1], median_over_steps=n2)
     return dt, out, stats
 
 
@@ -576,7 +587,7 @@ def main():
                    "vs_baseline": None, "dtype": "f32 (bf16-piece MFMA shortlist, fp64 canonical re-score)", "data": "synthetic",
                    "config": {"workload": knn["workload"], "parallelism": "single" if world == 1 else f"query rows x{world}"},
                    "roofline": knn["roofline"], "fallback_rows": knn["fallback_rows"]}
-            if world == 1 and not args.no_cpu:
+            if world == 1 and args.full and not args.no_cpu:
                 out["cpu_baseline"], out["cpu_baseline_gemm"] = knn_cpu_baselines(args.knn_n)
             if args.dump_outputs:
                 dump_outputs(args.dump_outputs, knn_out, "the last timed kNN call (this rank's query rows)")
@@ -591,7 +602,7 @@ def main():
     ei_np, mask_np = wl["ei_np"], wl["mask_np"]
     N = mask_np.shape[0]
     model = build_model(args, dev)
-    timer = AggTimer(args.hidden)
+    timer = AggTimer(args.hidden) if args.full else None
 
     if not use_dist:
         data = Data(x=wl["x"], edge_index=torch.from_numpy(ei_np).to(dev), central_mask=torch.from_numpy(mask_np).to(dev))
@@ -599,11 +610,13 @@ def main():
         csr = model._prepare(data)
         torch.cuda.synchronize()
         csr_first_ms = (time.perf_counter() - t0) * 1e3          # first call of the process: allocations + code-object load
-        from bridged_gnn_amd import ops as _ops
-        t0 = time.perf_counter()
-        _ops.build_dst_csr(data.edge_index, N)
-        torch.cuda.synchronize()
-        csr_ms = (time.perf_counter() - t0) * 1e3                # the build itself (one-time per graph, cached by the model)
+        csr_ms = None
+        if args.full:
+            from bridged_gnn_amd import ops as _ops
+            t0 = time.perf_counter()
+            _ops.build_dst_csr(data.edge_index, N)
+            torch.cuda.synchronize()
+            csr_ms = (time.perf_counter() - t0) * 1e3            # the build itself (one-time per graph, cached by the model)
         Eprime = csr.num_edges
         runner = lambda: model(data)
         par = "single"
@@ -623,19 +636,19 @@ def main():
                ("halo rows and all-reduced domain sums of the static input features resident (fetched once per version of x)"
                 if not args.no_input_halo_cache else "hidden conv: domain-sum all-reduce + 512-byte halo rows exchanged every forward"))
 
-    dt, gpu_out, fstats = time_forward(runner, args.steps, args.warmup, barrier, timer)
+    dt, gpu_out, fstats = time_forward(runner, args.steps, args.warmup, barrier, timer, per_step=args.full)
     if use_dist:
         dt = max_over_ranks([dt], dev)[0]
     ms_step = dt / args.steps * 1e3
     # per STEP: the partitioned path aggregates a conv in two launches (interior rows, then boundary rows)
-    agg_ms = timer.take_ms(args.steps)
+    agg_ms = timer.take_ms(args.steps) if args.full else None
     gpu_out = [t.clone() for t in gpu_out[:3]]
     checksums = [float(t.double().sum().item()) for t in gpu_out]        # of THIS rank's rows
 
     # ---- the conservative roofline figure: the same hidden aggregation on the uniform-random variant of the graph (no
     #      neighbour reuse for the L2 to exploit; SURVEY 8(d) "also run the adversarial uniform-random variant")
     uniform = None
-    if args.config == "c4" and args.graph == "local" and not use_dist and not args.no_uniform:
+    if args.full and args.config == "c4" and args.graph == "local" and not use_dist and not args.no_uniform:
         ei_u, mask_u = c4_graph(args.nodes, args.edges, "uniform")
         model_u = build_model(args, dev)
         data_u = Data(x=wl["x"], edge_index=torch.from_numpy(ei_u).to(dev), central_mask=torch.from_numpy(mask_u).to(dev))
@@ -653,7 +666,7 @@ def main():
     # N=1 through the partitioned driver (no process group, world size 1): the path the N>1 runs take must cost what the plain
     # forward costs when there is nothing to exchange (VERDICT r2 #4d: within 3 %)
     part_n1 = None
-    if not use_dist and args.config == "c4" and not args.no_partitioned_check:
+    if args.full and not use_dist and args.config == "c4" and not args.no_partitioned_check:
         from bridged_gnn_amd.dist import PartitionedKTGNN
         t0 = time.perf_counter()
         pk1 = PartitionedKTGNN(model, ei_np, mask_np, 0, 1, dev)
@@ -675,7 +688,7 @@ def main():
         del pk1, x1, o1
     train = None
     if args.train_steps < 0:
-        args.train_steps = 5 if (args.config == "c4" and not use_dist) else 0
+        args.train_steps = 5 if (args.full and args.config == "c4" and not use_dist) else 0
     if args.train_steps > 0 and not use_dist:
         # one optimisation step = train-mode forward (dropout, batch-stat BN) + HIP backward + Adam
         import torch.nn.functional as F
@@ -734,11 +747,11 @@ def main():
             except Exception as e:                                   # reported, not fatal: the eager number stands
                 train["graph_replay_ms_per_train_step"] = f"capture failed: {type(e).__name__}: {str(e)[:160]}"
         del tmodel, opt
-    knn = knn_bench(args, dev, rank, world) if (not args.no_knn and args.config == "c4") else None   # every rank takes part
+    knn = knn_bench(args, dev, rank, world) if (args.full and not args.no_knn and args.config == "c4") else None   # every rank takes part
     if knn is not None:
         del knn["outputs"]
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_local = N if not use_dist else len(pk.owned_global)
         e_local = Eprime if not use_dist else pk.local_num_edges
         bytes_launch = agg_bytes(e_local, n_local, args.hidden)
@@ -774,25 +787,25 @@ def main():
                     "graph": "the timed workload itself (no uniform-random variant was run); frac is null when the algorithmic "
                              "figure exceeds the peak (gathers served by the L2s): see timed_workload_launch",
                     "timed_workload_launch": this}
+    if rank == 0:
         out = {
             "metric": "aggregated_edges_per_sec_ktgnn_fwd", "value": 4 * Eprime / (ms_step * 1e-3), "unit": "edges/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{wl['name']} N={N} E'={Eprime}, 2-layer KT-GNN eval fwd F={args.feat} hidden={args.hidden} C={args.classes}",
-                       "parallelism": par, "csr_build_ms": csr_ms, "csr_build_first_call_ms": csr_first_ms,
+                       "parallelism": par, **({"csr_build_ms": csr_ms} if csr_ms is not None else {}), "csr_build_first_call_ms": csr_first_ms,
                        "cached": ["by-destination CSR of the graph (built once, like the reference's cached graph_partition)",
                                   "per-domain column sums of the static input features x (memoised per tensor version; the "
                                   "HIP-graph replay recomputes them every forward)"] +
                                  (["input halo rows + all-reduced input domain sums"] if use_dist and not args.no_input_halo_cache else [])},
-            "first_forward_ms": fstats["first_forward_ms"], "median_ms_per_step": fstats["median_ms_per_step"],
-            "min_ms_per_step": fstats["min_ms_per_step"], "max_ms_per_step": fstats["max_ms_per_step"],
-            "median_over_steps": fstats["median_over_steps"],
-            "hidden_conv_edges_per_sec": e_local * world / (agg_ms * 1e-3),
-            "roofline": roof,
-            "output_checksums": {"what": "fp64 sums of the three log-prob outputs of the timed forward" +
-                                         (" (this rank's rows)" if use_dist else ""),
-                                 "base": checksums[0], "target": checksums[1], "target_hat": checksums[2]},
+            **fstats,
         }
+        if args.full:
+            out["hidden_conv_edges_per_sec"] = e_local * world / (agg_ms * 1e-3)
+            out["roofline"] = roof
+        out["output_checksums"] = {"what": "fp64 sums of the three log-prob outputs of the timed forward" +
+                                           (" (this rank's rows)" if use_dist else ""),
+                                   "base": checksums[0], "target": checksums[1], "target_hat": checksums[2]}
         if part_n1 is not None:
             out["partitioned_path_n1"] = part_n1
         if use_dist:
@@ -804,7 +817,7 @@ def main():
             out["knn"] = knn
         if train is not None:
             out["train"] = train
-        if world == 1 and not use_dist and not args.no_cpu:
+        if world == 1 and not use_dist and args.full and not args.no_cpu:
             out["cpu_baseline"], parity = cpu_baseline(args, model, wl, gpu_out)
             if parity is not None:
                 out["parity"] = parity
