@@ -43,6 +43,30 @@ static inline hipError_t bgnn_zero_async(void* p, size_t bytes, hipStream_t st) 
 static inline bool bgnn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline size_t bgnn_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Counter-based dropout hash shared by every kernel that drops activations (bgnn_norm.hip, bgnn_sage.hip): element e of an
+// [N, D] activation (e = row * D + column) belongs to word pair q = e / 4 and takes its 16 bits from w0 lo, w0 hi, w1 lo, w1 hi
+// for e % 4 = 0..3.
+// dropout: 16 random bits per element, keep <=> bits >= thr (thr = round(p * 65536)); two 32-bit words per float4
+static __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+static __device__ __forceinline__ void drop_words(uint64_t q, uint64_t seed, uint32_t& w0, uint32_t& w1) {
+  const uint32_t a = fmix32((uint32_t)q * 0x9E3779B1u + (uint32_t)seed);
+  const uint32_t b = fmix32((uint32_t)(q >> 32) * 0x7FEB352Du + (uint32_t)(seed >> 32) + a);
+  w0 = fmix32(a ^ b ^ 0x2C1B3C6Du);
+  w1 = fmix32(w0 + b + 0x297A2D39u);
+}
+
+static inline void drop_consts(float p_drop, uint32_t& thr, float& scale) {
+  thr = 0u; scale = 1.f;
+  if (p_drop > 0.f) {
+    double t = (double)p_drop * 65536.0 + 0.5;
+    thr = t >= 65535.0 ? 65535u : (uint32_t)t;
+    scale = (float)(65536.0 / (65536.0 - (double)thr));
+  }
+}
+
 namespace bgnn {
 
 // ---- cross-lane moves without LDS traffic (gfx9 DPP controls) ----------------------------------

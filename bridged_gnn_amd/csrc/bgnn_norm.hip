@@ -13,18 +13,6 @@ constexpr int NT = 256;
 // fp64 atomic per column on ONE address each retire at ~25 ns apiece -- 50 us of tail under a 10 MB input
 constexpr int NREP = 8;
 
-// dropout: 16 random bits per element, keep <=> bits >= thr (thr = round(p * 65536)); two 32-bit words per float4
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-__device__ __forceinline__ void drop_words(uint64_t q, uint64_t seed, uint32_t& w0, uint32_t& w1) {
-  const uint32_t a = fmix32((uint32_t)q * 0x9E3779B1u + (uint32_t)seed);
-  const uint32_t b = fmix32((uint32_t)(q >> 32) * 0x7FEB352Du + (uint32_t)(seed >> 32) + a);
-  w0 = fmix32(a ^ b ^ 0x2C1B3C6Du);
-  w1 = fmix32(w0 + b + 0x297A2D39u);
-}
-
 struct NormParams {
   const float* x; int64_t N; int32_t D; int64_t ldx;
   const double* stats;          // [2 * D]: sum x | sum x^2
@@ -217,15 +205,6 @@ int grid_for(int64_t N, int D) {
 }
 
 bool shape_ok(int64_t N, int32_t D, int64_t ld) { return N >= 0 && D >= 4 && D <= 4 * NT && (D & 3) == 0 && ld >= D && (ld & 3) == 0; }
-
-void drop_consts(float p_drop, uint32_t& thr, float& scale) {
-  thr = 0u; scale = 1.f;
-  if (p_drop > 0.f) {
-    double t = (double)p_drop * 65536.0 + 0.5;
-    thr = t >= 65535.0 ? 65535u : (uint32_t)t;
-    scale = (float)(65536.0 / (65536.0 - (double)thr));
-  }
-}
 
 }  // namespace
 

@@ -1,0 +1,340 @@
+// GraphSAGE mean aggregation for gfx950 (wave64): forward and atomic-free backward.
+//
+// Replaces (reference, Bridged-GNN/models/backbones.py:440-498): torch_sparse `matmul(adj_t, x, reduce='mean')` inside each
+// SAGEConv plus the F.relu / F.dropout between convs and the closing F.log_softmax.  The host transforms first
+// (T = x [W_l ; W_r]^T + [0 ; b_l], one GEMM per layer: W_l is linear, so mean_j(W_l x_j) = W_l mean_j(x_j)) and this file
+// averages rows of the OUTPUT width:
+//   forward : out_i = epi( s_i * sum_{t in row i} T_l[col[t]] + T_r[i] ),   s_i = 1/deg_i (mean) or 1 (plain sum)
+//   backward: pass A (per destination) g_i from (y_i, dy_i), dT_r[i] = g_i, scratch S[i] = g_i / deg_i;
+//             pass B (per source)      dT_l[j] = sum over the out-edges of j of S[dst]  (the forward kernel, plain sum, over the
+//             by-source view) -- two launches, no float atomics, bit-identical from run to run.
+// There is no attention math: the forward is gather-bound.  Algorithmic bytes at width D: E'(4D + 4) + N(8D + 4).
+//
+// Mapping (as agg_kernel in bgnn_aggregate.hip): a group of GL = LF*EP consecutive lanes owns one output row; LF lanes span
+// the columns (float4 per lane), EP sub-groups walk different edges of the row (narrow rows), each sub-group keeps U neighbour
+// rows in flight.  Blocks are persistent over the XCD-balanced segment order of bgnn_common.h.  A launch covers at most 128
+// columns; wider rows run as column slices (one launch per slice).
+#include "bgnn_common.h"
+
+namespace {
+
+constexpr int SLICE = 128;   // columns per forward launch (LF <= 32)
+
+enum { EPI_NONE = 0, EPI_RELU = 1, EPI_LOGSOFTMAX = 2 };
+
+struct SageParams {
+  const float* tbl; int64_t ldt; int64_t n_tbl;    // neighbour table (column-offset to the slice), its stride and row count
+  const float* root; int64_t ldr;                  // optional per-row addend (column-offset to the slice)
+  const int32_t* rowptr; const int32_t* col;
+  int64_t n_rows;
+  int32_t D;                                       // columns of this slice (<= SLICE)
+  int mean;
+  float* out; int64_t ldo;                         // column-offset to the slice
+  // dropout after the ReLU: element index = row * d_full + c0 + column (the hash of bgnn_norm.hip)
+  uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_dev;
+  int32_t d_full; int32_t c0;
+};
+
+__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+// 16 dropout bits of element e (row * d_full + column)
+__device__ __forceinline__ uint32_t drop_bits(uint64_t e, uint64_t seed) {
+  uint32_t w0, w1;
+  drop_words(e >> 2, seed, w0, w1);
+  const uint32_t w = (e & 2) ? w1 : w0;
+  return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
+}
+
+template <int LF, int EP, int U, int EPI>
+__global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
+  constexpr int GL = LF * EP;            // lanes per output row
+  constexpr int GPW = 64 / GL;           // rows per wave
+  constexpr int RPB = 4 * GPW;           // rows per block iteration (4 waves)
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int g = lane / GL;
+  const int lg = lane % GL;
+  const int sub = lg / LF;
+  const int f0 = (lg % LF) * 4;
+  const bool fvalid = f0 < p.D;
+  uint64_t seed = p.seed;
+  if (EPI == EPI_RELU && p.seed_dev != nullptr) seed += *p.seed_dev;
+
+  const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
+  const bgnn::XcdRange tr = bgnn::xcd_pos_range(ntiles);
+  for (int64_t pos = tr.begin; pos < tr.end; pos += tr.step) {
+    const int64_t gt = bgnn::xcd_tile_of(pos, ntiles);
+    if (gt < 0) continue;                                       // block-uniform
+    const int64_t i = gt * RPB + wave * GPW + g;
+    const bool rvalid = i < p.n_rows;
+    const int32_t beg = rvalid ? p.rowptr[i] : 0;
+    const int32_t end = rvalid ? p.rowptr[i + 1] : 0;
+    const int32_t deg = end - beg;
+    const int32_t niter = (deg + EP * U - 1) / (EP * U);       // uniform inside the group
+
+    float4 acc = f4_zero();
+    int32_t nid[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int32_t e = beg + sub + u * EP;
+      nid[u] = e < end ? p.col[e] : -1;
+    }
+    for (int32_t it = 0; it < niter; ++it) {
+      const int32_t e0 = beg + it * (EP * U) + sub;
+      float4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        // ids outside the table are never dereferenced (a malformed CSR gives a wrong sum, not a stray read)
+        const bool ok = nid[u] >= 0 && (int64_t)nid[u] < p.n_tbl && fvalid;
+        v[u] = ok ? *reinterpret_cast<const float4*>(p.tbl + (int64_t)nid[u] * p.ldt + f0) : f4_zero();
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int32_t e = e0 + (U + u) * EP;
+        nid[u] = e < end ? p.col[e] : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
+      }
+    }
+    // sum of the EP sub-groups' partials (fixed butterfly: deterministic)
+#pragma unroll
+    for (int off = LF; off < GL; off <<= 1) {
+      acc.x += __shfl_xor(acc.x, off); acc.y += __shfl_xor(acc.y, off);
+      acc.z += __shfl_xor(acc.z, off); acc.w += __shfl_xor(acc.w, off);
+    }
+    const float s = (p.mean && deg > 0) ? 1.f / (float)deg : 1.f;
+    float o[4] = {acc.x * s, acc.y * s, acc.z * s, acc.w * s};
+    if (p.root != nullptr && rvalid && fvalid) {
+      const float4 r = *reinterpret_cast<const float4*>(p.root + i * p.ldr + f0);
+      o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w;
+    }
+    if (EPI == EPI_RELU) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = fmaxf(o[c], 0.f);
+      if (p.thr != 0u) {
+        const uint64_t e = (uint64_t)(rvalid ? i : 0) * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
+        if ((p.d_full & 3) == 0) {                              // the four columns share one word pair (as bgnn_norm.hip)
+          uint32_t w0, w1;
+          drop_words(e >> 2, seed, w0, w1);
+          const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
+#pragma unroll
+          for (int c = 0; c < 4; ++c) o[c] = bits[c] >= p.thr ? o[c] * p.keep_scale : 0.f;
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) o[c] = drop_bits(e + c, seed) >= p.thr ? o[c] * p.keep_scale : 0.f;
+        }
+      }
+    } else if (EPI == EPI_LOGSOFTMAX) {
+      // the whole row (D <= 4*LF) sits in the LF lanes of the group; every lane takes part in the cross-lane steps
+      float m = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) m = fmaxf(m, o[c]);
+      m = bgnn::group_max<LF>(m);
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) se += expf(o[c] - m);
+      se = bgnn::group_sum<LF>(se);
+      const float lse = m + logf(se);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] -= lse;
+    }
+    if (rvalid && sub == 0 && fvalid) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) if (f0 + c >= p.D) o[c] = 0.f;   // pad columns of the row leave as 0
+      *reinterpret_cast<float4*>(p.out + i * p.ldo + f0) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+  }
+}
+
+// ---- backward pass A: per destination row, g from (y, dy); dT_r = g, S = g / deg -------------------------------
+struct BwdParams {
+  const float* y; int64_t ldy;
+  const float* gy; int64_t ldgy;
+  const int32_t* rowptr;
+  int64_t n_rows;
+  int32_t D;
+  float keep_scale;
+  float* g; int64_t ldg;      // dT_r
+  float* s; int64_t lds;      // scratch
+};
+
+template <int LF, int EPI>
+__global__ __launch_bounds__(256) void sage_bwd_rows_kernel(BwdParams p) {
+  constexpr int RPB = 256 / LF;
+  const int r = threadIdx.x / LF;
+  const int f0 = (threadIdx.x % LF) * 4;
+  for (int64_t base = (int64_t)blockIdx.x * RPB; base < p.n_rows; base += (int64_t)gridDim.x * RPB) {
+    const int64_t i = base + r;
+    const bool rvalid = i < p.n_rows;
+    const int64_t ic = rvalid ? i : 0;
+    const int32_t deg = rvalid ? p.rowptr[i + 1] - p.rowptr[i] : 0;
+    const float inv = deg > 0 ? 1.f / (float)deg : 0.f;
+    if (EPI == EPI_LOGSOFTMAX) {
+      // g = dY - exp(Y) * sum(dY): one column chunk (D <= 4*LF); all lanes reach the group reduction
+      float4 y = f4_zero(), dy = f4_zero();
+      const bool fvalid = f0 < p.D && rvalid;
+      if (fvalid) {
+        y = *reinterpret_cast<const float4*>(p.y + ic * p.ldy + f0);
+        dy = *reinterpret_cast<const float4*>(p.gy + ic * p.ldgy + f0);
+      }
+      const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
+      float t = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) t += dv[c];
+      t = bgnn::group_sum<LF>(t);
+      float o[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = (f0 + c < p.D) ? dv[c] - expf(yv[c]) * t : 0.f;
+      if (fvalid) {
+        *reinterpret_cast<float4*>(p.g + i * p.ldg + f0) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(p.s + i * p.lds + f0) = make_float4(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
+      }
+    } else {
+      if (!rvalid) continue;
+      for (int f = f0; f < p.D; f += 4 * LF) {
+        const float4 y = *reinterpret_cast<const float4*>(p.y + i * p.ldy + f);
+        const float4 dy = *reinterpret_cast<const float4*>(p.gy + i * p.ldgy + f);
+        const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
+        float o[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          // ReLU then dropout: y > 0 <=> kept and positive, so no pre-activation is needed
+          o[c] = EPI == EPI_RELU ? (yv[c] > 0.f ? dv[c] * p.keep_scale : 0.f) : dv[c];
+          if (f + c >= p.D) o[c] = 0.f;
+        }
+        *reinterpret_cast<float4*>(p.g + i * p.ldg + f) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(p.s + i * p.lds + f) = make_float4(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
+      }
+    }
+  }
+}
+
+template <int LF, int EP, int U, int EPI>
+int launch_agg(const SageParams& p, hipStream_t st) {
+  constexpr int RPB = 4 * (64 / (LF * EP));
+  static const int cap = [] {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sage_agg_kernel<LF, EP, U, EPI>, 256, 0) != hipSuccess || per_cu < 1)
+      return 2048;
+    if (per_cu > 8) per_cu = 8;
+    return per_cu * prop.multiProcessorCount / 8 * 8;
+  }();
+  const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
+  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;   // multiple of 8 (XCD split)
+  if (grid < 8) grid = 8;
+  hipLaunchKernelGGL((sage_agg_kernel<LF, EP, U, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int EPI>
+int dispatch_agg(const SageParams& p, hipStream_t st) {
+  const int nv = (p.D + 3) / 4;   // float4 slots of the slice
+  if (nv <= 1) return launch_agg<1, 8, 4, EPI>(p, st);
+  if (nv <= 2) return launch_agg<2, 4, 4, EPI>(p, st);
+  if (nv <= 4) return launch_agg<4, 2, 4, EPI>(p, st);
+  if (nv <= 8) return launch_agg<8, 1, 8, EPI>(p, st);
+  if (nv <= 16) return launch_agg<16, 1, 8, EPI>(p, st);
+  return launch_agg<32, 1, 8, EPI>(p, st);
+}
+
+template <int LF, int EPI>
+int launch_bwd_rows(const BwdParams& p, hipStream_t st) {
+  constexpr int RPB = 256 / LF;
+  int64_t grid = (p.n_rows + RPB - 1) / RPB;
+  if (grid > 2048) grid = 2048;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL((sage_bwd_rows_kernel<LF, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int EPI>
+int dispatch_bwd_rows(const BwdParams& p, hipStream_t st) {
+  const int nv = (p.D + 3) / 4;
+  if (nv <= 1) return launch_bwd_rows<1, EPI>(p, st);
+  if (nv <= 2) return launch_bwd_rows<2, EPI>(p, st);
+  if (nv <= 4) return launch_bwd_rows<4, EPI>(p, st);
+  if (nv <= 8) return launch_bwd_rows<8, EPI>(p, st);
+  if (nv <= 16) return launch_bwd_rows<16, EPI>(p, st);
+  return launch_bwd_rows<32, EPI>(p, st);
+}
+
+bool ld_ok(int64_t ld, int32_t D) { return ld >= ((int64_t)D + 3) / 4 * 4 && (ld & 3) == 0; }
+
+int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root, int64_t ldr, const int32_t* rowptr,
+             const int32_t* col, int64_t n_rows, int32_t D, int mean, int epilogue, float p_drop, uint64_t seed,
+             const uint64_t* seed_dev, float* out, int64_t ldo, hipStream_t st) {
+  if (!tbl || !rowptr || !col || !out) return BGNN_E_NULL;
+  if (n_rows < 0 || n_tbl < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
+  if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
+  if (p_drop > 0.f && epilogue != EPI_RELU) return BGNN_E_SHAPE;
+  if (!ld_ok(ldt, D) || !ld_ok(ldo, D) || (root && !(ldr == 0 || ld_ok(ldr, D)))) return BGNN_E_ALIGN;
+  if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (root && !bgnn_aligned16(root))) return BGNN_E_ALIGN;
+  if (n_rows == 0) return 0;
+  for (int32_t c0 = 0; c0 < D; c0 += SLICE) {
+    SageParams p{};
+    p.tbl = tbl + c0; p.ldt = ldt; p.n_tbl = n_tbl;
+    p.root = root ? root + c0 : nullptr; p.ldr = ldr;
+    p.rowptr = rowptr; p.col = col; p.n_rows = n_rows;
+    p.D = D - c0 < SLICE ? D - c0 : SLICE;
+    p.mean = mean;
+    p.out = out + c0; p.ldo = ldo;
+    drop_consts(p_drop, p.thr, p.keep_scale);
+    p.seed = seed; p.seed_dev = seed_dev; p.d_full = D; p.c0 = c0;
+    int rc = epilogue == EPI_RELU ? dispatch_agg<EPI_RELU>(p, st)
+           : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX>(p, st) : dispatch_agg<EPI_NONE>(p, st);
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int bgnn_sage_mean_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
+                                            const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
+                                            int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                            float* out, int64_t ldo, void* stream) {
+  return agg_impl(tbl, ldt, n_tbl, root_opt, ldr, rowptr, col, n_rows, D, mean, epilogue, p_drop, seed, seed_dev_opt, out, ldo,
+                  (hipStream_t)stream);
+}
+
+extern "C" size_t bgnn_sage_mean_aggregate_bwd_workspace_bytes(int64_t n_rows, int32_t D) {
+  if (n_rows < 0 || D <= 0) return 0;
+  return (size_t)n_rows * (size_t)(((int64_t)D + 3) / 4 * 4) * sizeof(float) + 16;
+}
+
+extern "C" int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy,
+                                                const int32_t* rowptr, int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col,
+                                                int64_t n_src, int32_t D, int epilogue, float p_drop,
+                                                float* grad_tbl, int64_t ldgt, float* grad_root, int64_t ldgr,
+                                                void* ws, size_t ws_bytes, void* stream) {
+  if (!grad_y || !rowptr || !t_rowptr || !t_col || !grad_tbl || !grad_root || !ws) return BGNN_E_NULL;
+  if (epilogue != EPI_NONE && !y) return BGNN_E_NULL;
+  if (n_rows < 0 || n_src < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
+  if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
+  if (p_drop > 0.f && epilogue != EPI_RELU) return BGNN_E_SHAPE;
+  if (ws_bytes < bgnn_sage_mean_aggregate_bwd_workspace_bytes(n_rows, D)) return BGNN_E_WORKSPACE;
+  if ((y && !ld_ok(ldy, D)) || !ld_ok(ldgy, D) || !ld_ok(ldgt, D) || !ld_ok(ldgr, D)) return BGNN_E_ALIGN;
+  if ((y && !bgnn_aligned16(y)) || !bgnn_aligned16(grad_y) || !bgnn_aligned16(grad_tbl) || !bgnn_aligned16(grad_root))
+    return BGNN_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t lds = ((int64_t)D + 3) / 4 * 4;
+  float* s = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws), 16));
+  if (n_rows > 0) {
+    BwdParams p{};
+    p.y = y; p.ldy = ldy; p.gy = grad_y; p.ldgy = ldgy; p.rowptr = rowptr; p.n_rows = n_rows; p.D = D;
+    uint32_t thr;
+    drop_consts(p_drop, thr, p.keep_scale);
+    p.g = grad_root; p.ldg = ldgr; p.s = s; p.lds = lds;
+    const int rc = epilogue == EPI_RELU ? dispatch_bwd_rows<EPI_RELU>(p, st)
+                 : epilogue == EPI_LOGSOFTMAX ? dispatch_bwd_rows<EPI_LOGSOFTMAX>(p, st) : dispatch_bwd_rows<EPI_NONE>(p, st);
+    if (rc != 0) return rc;
+  }
+  // pass B: plain sum of the scratch rows over the by-source view (every id in t_col is a destination row < n_rows)
+  return agg_impl(s, lds, n_rows, nullptr, 0, t_rowptr, t_col, n_src, D, 0, EPI_NONE, 0.f, 0, nullptr, grad_tbl, ldgt, st);
+}

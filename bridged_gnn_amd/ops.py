@@ -8,7 +8,8 @@ import torch
 from . import _lib as L
 
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
-           "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4"]
+           "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
+           "sage_mean_aggregate", "sage_mean_aggregate_bwd"]
 
 
 def pad4(n):
@@ -800,3 +801,46 @@ def coalesce(edge_index, num_nodes=None):
     L.check(rc, "bgnn_coalesce_i64")
     ne = int(e_out.item())
     return ei[:, :ne].contiguous()
+
+
+SAGE_EPILOGUES = {None: 0, "none": 0, "relu": 1, "log_softmax": 2}
+
+
+def sage_mean_aggregate(tbl, rowptr, col, n_rows, D, root=None, mean=True, epilogue=None, p_drop=0.0, seed=0, seed_dev=None,
+                        out=None):
+    """GraphSAGE aggregation (models/backbones.py:440-498, bgnn.h: bgnn_sage_mean_aggregate_f32) ->
+    out [n_rows, pad4(D)] (use out[:, :D]): out[i] = epi(s_i * sum_{t in row i} tbl[col[t]] + root[i]), s_i = 1/deg_i when `mean`.
+    tbl / root / out: 2-D row-strided views (unit column stride, e.g. the two halves of one interleaved table).  (rowptr, col) is
+    a DstCSR (in-neighbours) or its `transposed()` (t_rowptr, t_dst: out-neighbours).  epilogue: None, "relu" (then dropout at
+    p_drop with the (seed, element index) hash of `bn_relu_dropout`) or "log_softmax" (D <= 128)."""
+    n_rows, D = int(n_rows), int(D)
+    if out is None:
+        out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
+    ldr = 0 if root is None else (root.stride(0) if root.shape[0] > 1 else 0)
+    rc = L.lib().bgnn_sage_mean_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr_rows(root), ldr, L.ptr(rowptr), L.ptr(col), n_rows, D,
+        1 if mean else 0, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        L.ptr(seed_dev) if seed_dev is not None else None, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_sage_mean_aggregate_f32")
+    return out
+
+
+def sage_mean_aggregate_bwd(y, grad_y, rowptr, t_rowptr, t_col, n_src, D, epilogue=None, p_drop=0.0, grad_tbl=None, grad_root=None):
+    """Backward of `sage_mean_aggregate(tbl, rowptr, col, n_rows, D, root, mean=True, epilogue, p_drop)` -> (grad_tbl [n_src, pad4(D)],
+    grad_root [n_rows, pad4(D)]).  y: the forward's output (unused without an epilogue, may be None); (t_rowptr, t_col): the view of
+    the same edges with the roles swapped (grad_tbl[j] sums grad_root[i] / deg_i over the edges j -> i).  Two launches, no atomics."""
+    n_rows, n_src, D = int(rowptr.shape[0]) - 1, int(n_src), int(D)
+    dev = grad_y.device
+    lib = L.lib()
+    if grad_tbl is None:
+        grad_tbl = torch.empty(n_src, pad4(D), dtype=torch.float32, device=dev)
+    if grad_root is None:
+        grad_root = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=dev)
+    wsb = lib.bgnn_sage_mean_aggregate_bwd_workspace_bytes(n_rows, D)
+    ws = torch.empty(max(int(wsb), 16), dtype=torch.uint8, device=dev)
+    rc = lib.bgnn_sage_mean_aggregate_bwd_f32(
+        L.ptr_rows(y), y.stride(0) if y is not None else 0, L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr), n_rows,
+        L.ptr(t_rowptr), L.ptr(t_col), n_src, D, SAGE_EPILOGUES[epilogue], float(p_drop), L.ptr_rows(grad_tbl), grad_tbl.stride(0),
+        L.ptr_rows(grad_root), grad_root.stride(0), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_sage_mean_aggregate_bwd_f32")
+    return grad_tbl, grad_root

@@ -27,7 +27,8 @@ extern "C" {
  * and the `n_fallback_opt` of `bgnn_cosine_topk_f32` / `bgnn_mlp_pair_topk_f32` is int32[2] (was int32[1]) -- a caller built
  * against the old header must be recompiled; compare bgnn_version() with the BGNN_VERSION it was built with at load time.
  * 111 adds bgnn_adaptedconv_transform_need_f32, 112 bgnn_classifier_stage_f32, 113 bgnn_adaptedconv_aggregate_bounded_f32 (all
- * call-compatible with 110). */
+ * call-compatible with 110).  The GraphSAGE entry points (bgnn_sage_mean_aggregate_f32, bgnn_sage_mean_aggregate_bwd_f32 and its
+ * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -377,6 +378,35 @@ int bgnn_adaptedconv_aggregate_heads_bwd_hub_f32(const float* h_t2s, const float
                                                  const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
                                                  const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
                                                  void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GraphSAGE mean aggregation (the --no_dtc model of main_graph_knowledge_transfer.py:326,:414-417):
+ *     models/backbones.py:440-498 -- torch_sparse matmul(adj_t, x, reduce='mean') inside each SAGEConv (PyG sage_conv),
+ *     F.relu + F.dropout(p=0.5) between convs (:467-469) and F.log_softmax (:471).
+ * The caller transforms first (T = x [W_l ; W_r]^T + [0 ; b_l]) and aggregates rows of the output width D:
+ *   out[i] = epi( s_i * sum_{t in [rowptr[i], rowptr[i+1])} tbl[col[t]] + root[i] ),  s_i = 1/deg_i if `mean` else 1,
+ * a row without edges gives epi(root[i]); root_opt NULL adds nothing, ldr == 0 broadcasts one row.  Duplicate edges count with
+ * their multiplicity, self loops as given.  A by-destination CSR (rowptr [n_rows+1], col = sources) averages in-neighbours (forward);
+ * the by-source view (t_rowptr, t_dst) averages out-neighbours (get_emb / get_logits, :473-498).  ids in col must be < n_tbl.
+ * epilogue: 0 none; 1 ReLU, then dropout with keep probability 1-p_drop (mask = the counter-based hash of bgnn_bn_relu_dropout_f32
+ * over element index row * D + column, same seed / seed_dev_opt semantics; p_drop > 0 only with epilogue 1); 2 row log_softmax
+ * (D <= 128).  Strides ldt / ldr / ldo are in floats, % 4 == 0 and >= pad4(D); pointers 16-B aligned; pad columns of out are
+ * written as 0.  D > 128 runs as 128-column slices.
+ * bgnn_sage_mean_aggregate_bwd_f32: the atomic-free backward of the same call (mean = 1, root present) -- from the forward's output
+ * y and grad_y: g = grad_y (epilogue 0), (y > 0 ? grad_y / (1 - p_drop) : 0) (epilogue 1), grad_y - exp(y) * rowsum(grad_y)
+ * (epilogue 2); grad_root[i] = g[i] (n_rows rows) and grad_tbl[j] = sum over the out-edges (j -> i) of g[i] / deg_i, walked over
+ * the by-source view (t_rowptr [n_src+1], t_col = destinations) in n_src rows.  Deterministic bits.
+ * ws: bgnn_sage_mean_aggregate_bwd_workspace_bytes(n_rows, D). */
+int bgnn_sage_mean_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
+                                 const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
+                                 int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                 float* out, int64_t ldo, void* stream);
+size_t bgnn_sage_mean_aggregate_bwd_workspace_bytes(int64_t n_rows, int32_t D);
+int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy,
+                                     const int32_t* rowptr, int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col,
+                                     int64_t n_src, int32_t D, int epilogue, float p_drop,
+                                     float* grad_tbl, int64_t ldgt, float* grad_root, int64_t ldgr,
+                                     void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
