@@ -81,6 +81,9 @@ SIGNATURES = {
     "bgnn_coalesce_i64": (_INT, [_P, _I64, _I64, _P, _P, _SZ, _P]),
     "bgnn_sage_mean_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _INT, _INT, _F32, C.c_uint64, _P,
                                              _P, _I64, _P]),
+    "bgnn_sage_mean_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _INT, _INT, _F32, C.c_uint64, _P,
+                                                  _P, _P, _I64, _P]),
+    "bgnn_rows_segment_add_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _I64, _I32, _INT, _P, _I64, _I64, _P]),
     "bgnn_sage_mean_aggregate_bwd_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_sage_mean_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _INT, _F32, _P, _I64, _P, _I64,
                                                  _P, _SZ, _P]),

@@ -14,6 +14,11 @@
 // the columns (float4 per lane), EP sub-groups walk different edges of the row (narrow rows), each sub-group keeps U neighbour
 // rows in flight.  Blocks are persistent over the XCD-balanced segment order of bgnn_common.h.  A launch covers at most 128
 // columns; wider rows run as column slices (one launch per slice).
+//
+// Two compile-time variants of the same kernel serve a destination-node partition (dist_sage.py): ROW_ID keys the dropout hash
+// on a caller-given GLOBAL row id per output row (a rank's rows then draw the masks of the whole-graph call), and OUT_ROW
+// writes output row s to dst[row[s]] (optionally adding what is there): bgnn_rows_segment_add_f32, which folds the gradient
+// rows returned by the reverse halo exchange into their owners' rows.  The plain entry point instantiates neither.
 #include "bgnn_common.h"
 
 namespace {
@@ -33,6 +38,8 @@ struct SageParams {
   // dropout after the ReLU: element index = row * d_full + c0 + column (the hash of bgnn_norm.hip)
   uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_dev;
   int32_t d_full; int32_t c0;
+  const int64_t* row_id;                           // ROW_ID: dropout row of output row i (element index row_id[i] * d_full + col)
+  const int32_t* out_row; int64_t n_out;          // OUT_ROW: output row i lands in (and its root is read from) row out_row[i]
 };
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -45,7 +52,7 @@ __device__ __forceinline__ uint32_t drop_bits(uint64_t e, uint64_t seed) {
   return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
 }
 
-template <int LF, int EP, int U, int EPI>
+template <int LF, int EP, int U, int EPI, bool ROW_ID = false, bool OUT_ROW = false>
 __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
   constexpr int GL = LF * EP;            // lanes per output row
   constexpr int GPW = 64 / GL;           // rows per wave
@@ -106,15 +113,18 @@ __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
     }
     const float s = (p.mean && deg > 0) ? 1.f / (float)deg : 1.f;
     float o[4] = {acc.x * s, acc.y * s, acc.z * s, acc.w * s};
-    if (p.root != nullptr && rvalid && fvalid) {
-      const float4 r = *reinterpret_cast<const float4*>(p.root + i * p.ldr + f0);
+    const int64_t io = OUT_ROW ? (rvalid ? (int64_t)p.out_row[i] : 0) : i;   // the row written (and whose root is added)
+    const bool ovalid = OUT_ROW ? (rvalid && io >= 0 && io < p.n_out) : rvalid;  // a row id out of range is never touched
+    if (p.root != nullptr && ovalid && fvalid) {
+      const float4 r = *reinterpret_cast<const float4*>(p.root + io * p.ldr + f0);
       o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w;
     }
     if (EPI == EPI_RELU) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] = fmaxf(o[c], 0.f);
       if (p.thr != 0u) {
-        const uint64_t e = (uint64_t)(rvalid ? i : 0) * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
+        const int64_t ih = ROW_ID ? (rvalid ? p.row_id[i] : 0) : (rvalid ? i : 0);
+        const uint64_t e = (uint64_t)ih * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
         if ((p.d_full & 3) == 0) {                              // the four columns share one word pair (as bgnn_norm.hip)
           uint32_t w0, w1;
           drop_words(e >> 2, seed, w0, w1);
@@ -140,10 +150,10 @@ __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] -= lse;
     }
-    if (rvalid && sub == 0 && fvalid) {
+    if (ovalid && sub == 0 && fvalid) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) if (f0 + c >= p.D) o[c] = 0.f;   // pad columns of the row leave as 0
-      *reinterpret_cast<float4*>(p.out + i * p.ldo + f0) = make_float4(o[0], o[1], o[2], o[3]);
+      *reinterpret_cast<float4*>(p.out + io * p.ldo + f0) = make_float4(o[0], o[1], o[2], o[3]);
     }
   }
 }
@@ -211,14 +221,14 @@ __global__ __launch_bounds__(256) void sage_bwd_rows_kernel(BwdParams p) {
   }
 }
 
-template <int LF, int EP, int U, int EPI>
+template <int LF, int EP, int U, int EPI, bool ROW_ID, bool OUT_ROW>
 int launch_agg(const SageParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
   static const int cap = [] {
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sage_agg_kernel<LF, EP, U, EPI>, 256, 0) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sage_agg_kernel<LF, EP, U, EPI, ROW_ID, OUT_ROW>, 256, 0) != hipSuccess || per_cu < 1)
       return 2048;
     if (per_cu > 8) per_cu = 8;
     return per_cu * prop.multiProcessorCount / 8 * 8;
@@ -226,20 +236,20 @@ int launch_agg(const SageParams& p, hipStream_t st) {
   const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
   int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;   // multiple of 8 (XCD split)
   if (grid < 8) grid = 8;
-  hipLaunchKernelGGL((sage_agg_kernel<LF, EP, U, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((sage_agg_kernel<LF, EP, U, EPI, ROW_ID, OUT_ROW>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
 
-template <int EPI>
+template <int EPI, bool ROW_ID = false, bool OUT_ROW = false>
 int dispatch_agg(const SageParams& p, hipStream_t st) {
   const int nv = (p.D + 3) / 4;   // float4 slots of the slice
-  if (nv <= 1) return launch_agg<1, 8, 4, EPI>(p, st);
-  if (nv <= 2) return launch_agg<2, 4, 4, EPI>(p, st);
-  if (nv <= 4) return launch_agg<4, 2, 4, EPI>(p, st);
-  if (nv <= 8) return launch_agg<8, 1, 8, EPI>(p, st);
-  if (nv <= 16) return launch_agg<16, 1, 8, EPI>(p, st);
-  return launch_agg<32, 1, 8, EPI>(p, st);
+  if (nv <= 1) return launch_agg<1, 8, 4, EPI, ROW_ID, OUT_ROW>(p, st);
+  if (nv <= 2) return launch_agg<2, 4, 4, EPI, ROW_ID, OUT_ROW>(p, st);
+  if (nv <= 4) return launch_agg<4, 2, 4, EPI, ROW_ID, OUT_ROW>(p, st);
+  if (nv <= 8) return launch_agg<8, 1, 8, EPI, ROW_ID, OUT_ROW>(p, st);
+  if (nv <= 16) return launch_agg<16, 1, 8, EPI, ROW_ID, OUT_ROW>(p, st);
+  return launch_agg<32, 1, 8, EPI, ROW_ID, OUT_ROW>(p, st);
 }
 
 template <int LF, int EPI>
@@ -268,7 +278,7 @@ bool ld_ok(int64_t ld, int32_t D) { return ld >= ((int64_t)D + 3) / 4 * 4 && (ld
 
 int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root, int64_t ldr, const int32_t* rowptr,
              const int32_t* col, int64_t n_rows, int32_t D, int mean, int epilogue, float p_drop, uint64_t seed,
-             const uint64_t* seed_dev, float* out, int64_t ldo, hipStream_t st) {
+             const uint64_t* seed_dev, float* out, int64_t ldo, hipStream_t st, const int64_t* row_id = nullptr) {
   if (!tbl || !rowptr || !col || !out) return BGNN_E_NULL;
   if (n_rows < 0 || n_tbl < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
   if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
@@ -286,7 +296,9 @@ int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root, in
     p.out = out + c0; p.ldo = ldo;
     drop_consts(p_drop, p.thr, p.keep_scale);
     p.seed = seed; p.seed_dev = seed_dev; p.d_full = D; p.c0 = c0;
-    int rc = epilogue == EPI_RELU ? dispatch_agg<EPI_RELU>(p, st)
+    p.row_id = row_id;
+    // the row id only feeds the dropout hash: without dropout (or without ids) the plain kernel runs
+    int rc = epilogue == EPI_RELU ? (row_id != nullptr && p.thr != 0u ? dispatch_agg<EPI_RELU, true>(p, st) : dispatch_agg<EPI_RELU>(p, st))
            : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX>(p, st) : dispatch_agg<EPI_NONE>(p, st);
     if (rc != 0) return rc;
   }
@@ -301,6 +313,39 @@ extern "C" int bgnn_sage_mean_aggregate_f32(const float* tbl, int64_t ldt, int64
                                             float* out, int64_t ldo, void* stream) {
   return agg_impl(tbl, ldt, n_tbl, root_opt, ldr, rowptr, col, n_rows, D, mean, epilogue, p_drop, seed, seed_dev_opt, out, ldo,
                   (hipStream_t)stream);
+}
+
+extern "C" int bgnn_sage_mean_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
+                                                 const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
+                                                 int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                                 const int64_t* row_id_opt, float* out, int64_t ldo, void* stream) {
+  return agg_impl(tbl, ldt, n_tbl, root_opt, ldr, rowptr, col, n_rows, D, mean, epilogue, p_drop, seed, seed_dev_opt, out, ldo,
+                  (hipStream_t)stream, row_id_opt);
+}
+
+extern "C" int bgnn_rows_segment_add_f32(const float* src, int64_t lds, int64_t n_src, const int32_t* seg_ptr,
+                                         const int32_t* idx, const int32_t* row, int64_t n_seg, int32_t D, int accumulate,
+                                         float* dst, int64_t ldd, int64_t n_dst, void* stream) {
+  if (!src || !seg_ptr || !idx || !row || !dst) return BGNN_E_NULL;
+  if (n_seg < 0 || n_src < 0 || n_dst < 0 || D <= 0) return BGNN_E_SHAPE;
+  if (!ld_ok(lds, D) || !ld_ok(ldd, D)) return BGNN_E_ALIGN;
+  if (!bgnn_aligned16(src) || !bgnn_aligned16(dst)) return BGNN_E_ALIGN;
+  if (n_seg == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  for (int32_t c0 = 0; c0 < D; c0 += SLICE) {
+    SageParams p{};
+    p.tbl = src + c0; p.ldt = lds; p.n_tbl = n_src;
+    p.root = accumulate ? dst + c0 : nullptr; p.ldr = ldd;      // dst[row[s]] + sum: the root half is the destination row itself
+    p.rowptr = seg_ptr; p.col = idx; p.n_rows = n_seg;
+    p.D = D - c0 < SLICE ? D - c0 : SLICE;
+    p.mean = 0;
+    p.out = dst + c0; p.ldo = ldd;
+    p.keep_scale = 1.f; p.d_full = D; p.c0 = c0;
+    p.out_row = row; p.n_out = n_dst;
+    const int rc = dispatch_agg<EPI_NONE, false, true>(p, st);
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 extern "C" size_t bgnn_sage_mean_aggregate_bwd_workspace_bytes(int64_t n_rows, int32_t D) {

@@ -9,7 +9,7 @@ from . import _lib as L
 
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
-           "sage_mean_aggregate", "sage_mean_aggregate_bwd"]
+           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add"]
 
 
 def pad4(n):
@@ -807,21 +807,28 @@ SAGE_EPILOGUES = {None: 0, "none": 0, "relu": 1, "log_softmax": 2}
 
 
 def sage_mean_aggregate(tbl, rowptr, col, n_rows, D, root=None, mean=True, epilogue=None, p_drop=0.0, seed=0, seed_dev=None,
-                        out=None):
+                        out=None, row_ids=None):
     """GraphSAGE aggregation (models/backbones.py:440-498, bgnn.h: bgnn_sage_mean_aggregate_f32) ->
     out [n_rows, pad4(D)] (use out[:, :D]): out[i] = epi(s_i * sum_{t in row i} tbl[col[t]] + root[i]), s_i = 1/deg_i when `mean`.
     tbl / root / out: 2-D row-strided views (unit column stride, e.g. the two halves of one interleaved table).  (rowptr, col) is
     a DstCSR (in-neighbours) or its `transposed()` (t_rowptr, t_dst: out-neighbours).  epilogue: None, "relu" (then dropout at
-    p_drop with the (seed, element index) hash of `bn_relu_dropout`) or "log_softmax" (D <= 128)."""
+    p_drop with the (seed, element index) hash of `bn_relu_dropout`) or "log_softmax" (D <= 128).
+    row_ids: int64 [n_rows], the GLOBAL row id of every output row (a rank's rows of a partition): the dropout element index is
+    then row_ids[i] * D + column, the masks of the whole-graph call (bgnn_sage_mean_aggregate_rows_f32); None = row i itself."""
     n_rows, D = int(n_rows), int(D)
     if out is None:
         out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
     ldr = 0 if root is None else (root.stride(0) if root.shape[0] > 1 else 0)
-    rc = L.lib().bgnn_sage_mean_aggregate_f32(
-        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr_rows(root), ldr, L.ptr(rowptr), L.ptr(col), n_rows, D,
-        1 if mean else 0, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
-        L.ptr(seed_dev) if seed_dev is not None else None, L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_sage_mean_aggregate_f32")
+    args = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr_rows(root), ldr, L.ptr(rowptr), L.ptr(col), n_rows, D,
+            1 if mean else 0, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            L.ptr(seed_dev) if seed_dev is not None else None)
+    if row_ids is None:
+        rc = L.lib().bgnn_sage_mean_aggregate_f32(*args, L.ptr_rows(out), out.stride(0), L.stream())
+        L.check(rc, "bgnn_sage_mean_aggregate_f32")
+        return out
+    assert row_ids.dtype == torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n_rows and row_ids.is_contiguous()
+    rc = L.lib().bgnn_sage_mean_aggregate_rows_f32(*args, L.ptr(row_ids), L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_sage_mean_aggregate_rows_f32")
     return out
 
 
@@ -844,3 +851,20 @@ def sage_mean_aggregate_bwd(y, grad_y, rowptr, t_rowptr, t_col, n_src, D, epilog
         L.ptr_rows(grad_root), grad_root.stride(0), L.ptr(ws), ws.numel(), L.stream())
     L.check(rc, "bgnn_sage_mean_aggregate_bwd_f32")
     return grad_tbl, grad_root
+
+
+def rows_segment_add(src, seg_ptr, idx, row, dst, D=None, accumulate=True):
+    """dst[row[s]] (+)= sum_{k in [seg_ptr[s], seg_ptr[s+1])} src[idx[k]] (bgnn.h: bgnn_rows_segment_add_f32) -> dst.
+    src / dst: 2-D float32 row-strided views with unit column stride; seg_ptr [n_seg+1], idx, row [n_seg]: int32 (distinct rows).
+    D columns (default: all of dst's; pad columns up to pad4(D) are written as 0).  No atomics: bit-identical from run to run.
+    The owner's fold of the gradient rows returned by the reverse halo exchange (`dist_sage.PartitionedGraphSAGE`)."""
+    D = int(dst.shape[1]) if D is None else int(D)
+    n_seg = int(row.shape[0])
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.dim() == 2 and dst.dim() == 2
+    assert all(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() for t in (seg_ptr, idx, row))
+    assert seg_ptr.shape[0] == n_seg + 1 and pad4(D) <= min(src.shape[1], dst.shape[1])
+    rc = L.lib().bgnn_rows_segment_add_f32(L.ptr_rows(src), src.stride(0), int(src.shape[0]), L.ptr(seg_ptr), L.ptr(idx), L.ptr(row),
+                                           n_seg, D, 1 if accumulate else 0, L.ptr_rows(dst), dst.stride(0), int(dst.shape[0]),
+                                           L.stream())
+    L.check(rc, "bgnn_rows_segment_add_f32")
+    return dst

@@ -28,7 +28,8 @@ extern "C" {
  * against the old header must be recompiled; compare bgnn_version() with the BGNN_VERSION it was built with at load time.
  * 111 adds bgnn_adaptedconv_transform_need_f32, 112 bgnn_classifier_stage_f32, 113 bgnn_adaptedconv_aggregate_bounded_f32 (all
  * call-compatible with 110).  The GraphSAGE entry points (bgnn_sage_mean_aggregate_f32, bgnn_sage_mean_aggregate_bwd_f32 and its
- * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113. */
+ * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113.  The
+ * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -407,6 +408,24 @@ int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, const float* g
                                      int64_t n_src, int32_t D, int epilogue, float p_drop,
                                      float* grad_tbl, int64_t ldgt, float* grad_root, int64_t ldgr,
                                      void* ws, size_t ws_bytes, void* stream);
+/* bgnn_sage_mean_aggregate_rows_f32: bgnn_sage_mean_aggregate_f32 for a block of rows of a larger graph (a rank's rows of a
+ * destination-node partition).  row_id_opt [n_rows] (int64) gives every output row its GLOBAL row id; the dropout element index is
+ * then row_id[i] * D + column, so a rank draws exactly the masks of the whole-graph call.  With row_id_opt NULL (or no dropout)
+ * this is bgnn_sage_mean_aggregate_f32, bit for bit.  Everything else as there.
+ * bgnn_rows_segment_add_f32: for a CSR of segments (seg_ptr [n_seg+1], idx = rows of src < n_src, row [n_seg]),
+ *     dst[row[s]] = (accumulate ? dst[row[s]] : 0) + sum_{k in [seg_ptr[s], seg_ptr[s+1])} src[idx[k]]
+ * over D columns (pad columns up to pad4(D) written as 0).  The row ids must be distinct; an id outside [0, n_dst) is skipped
+ * (its segment is never written).  No atomics: one lane group
+ * owns a segment and sums it in a fixed order, so the result is bit-identical from run to run.  Empty segments give dst[row[s]]
+ * (accumulate) or 0.  lds / ldd in floats, % 4 == 0 and >= pad4(D); src / dst 16-B aligned.  This is how the owner of a row
+ * folds the gradient rows that come back from the reverse halo exchange (a row sent to k ranks gets k rows back). */
+int bgnn_sage_mean_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
+                                      const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
+                                      int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                      const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
+int bgnn_rows_segment_add_f32(const float* src, int64_t lds, int64_t n_src, const int32_t* seg_ptr, const int32_t* idx,
+                              const int32_t* row, int64_t n_seg, int32_t D, int accumulate, float* dst, int64_t ldd, int64_t n_dst,
+                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
