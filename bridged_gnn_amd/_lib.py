@@ -68,6 +68,10 @@ SIGNATURES = {
     "bgnn_adaptedconv_aggregate_heads_bwd_hub_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32,
                                                              _P, _P, _P, _INT, _P, _P, _P, _P, _I32,
                                                              _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
+    "bgnn_adaptedconv_aggregate_heads_wide_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P, _P, _P]),
+    "bgnn_aggregate_heads_wide_bwd_workspace_bytes": (C.c_size_t, [_I64, _I32, _I64]),
+    "bgnn_adaptedconv_aggregate_heads_wide_bwd_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F32,
+                                                              _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "bgnn_l2_normalize_rows_f32": (_INT, [_P, _I64, _I32, _F32, _P, _P]),
     "bgnn_topk_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
     "bgnn_cosine_topk_f32": (_INT, [_P, _P, _I64, _I64, _I32, _I32, _INT, _P, _P, _P, _P, _SZ, _P]),
@@ -104,7 +108,7 @@ def source_hash():
 
 # keep in step with HASHED in csrc/Makefile
 _HASHED_SOURCES = ("bgnn_api.hip", "bgnn_csr.hip", "bgnn_transform.hip", "bgnn_transform_stream.hip", "bgnn_transform_cls.hip", "bgnn_aggregate.hip", "bgnn_aggregate_bwd.hip",
-                   "bgnn_aggregate_bwd_fast.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
+                   "bgnn_aggregate_bwd_fast.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
 
 
 def _sidecar_hash():

@@ -8,7 +8,7 @@ square by giving the halo rows no in-edges.  What crosses ranks, forward and bac
   * conv 0 reads the graph's INPUT features: their halo rows are resident (fetched once, `PartitionedKTGNN._input_ext`), the rank
     transforms local + halo rows itself -- no exchange; the halo rows' share of the weight gradient is part of this rank's loss;
   * later convs and the classifier stage transform the rank's own rows and send the transformed rows their consumers reference
-    through ONE all_to_all (48-byte rows for the three classifier convs); its autograd backward is the REVERSE exchange of the
+    through ONE all_to_all (6 * pad4(C) floats per row for the three classifier convs); its autograd backward is the REVERSE exchange of the
     gradient rows (dH after the aggregation's pass B), added into the owners' rows by autograd;
   * the per-domain sums behind delta (KTGNN.py:275) are all-reduced; the gradient through the domain means is a global quantity:
     every transform hands its local adjoint of delta to a hook that all-reduces it and applies +1/n_S | -1/n_T on the owned rows;
@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .dist import PartitionPlan
-from .ktgnn import _AggregateFn, _AggregateHeadsFn, _pad_cols4
+from .ktgnn import _AggregateFn, _AggregateHeadsFn, _AggregateWideHeadsFn, _pad_cols4
 
 
 class _Comm:
@@ -176,8 +176,8 @@ class PartitionedTrainer:
         if not m.training:
             raise RuntimeError("PartitionedTrainer.forward is the TRAINING forward; use dist.PartitionedKTGNN for evaluation")
         C = m.clf_base.out_channels
-        if not ops.heads_log_softmax_supported(3, C) or m.clf_base.root_weight or m.clf_base.normalize:
-            raise NotImplementedError("partitioned training: classifier convs with <= 4 classes, root_weight / normalize off")
+        if m.clf_base.root_weight or m.clf_base.normalize:
+            raise NotImplementedError("partitioned training: classifier convs with root_weight / normalize off")
         nl = self.n_local
         h = None
         for ind, conv in enumerate(m.convs):
@@ -197,7 +197,8 @@ class PartitionedTrainer:
             else:
                 h = F.dropout(F.relu(out), p=m.dropout, training=True)
             h = h.contiguous()
-        # classifier stage (KTGNN.py:432-435): three narrow convs share the graph, one exchange of 96-byte rows
+        # classifier stage (KTGNN.py:432-435): three convs share the graph, one exchange of 6 * pad4(C) floats per row (96 bytes
+        # for C <= 4, 768 bytes at C = 31); C <= 4: the narrow three-head walk, C <= 32: the wide one, beyond: three per-conv walks
         sums_h = self._global_sums(h)
         l0, bn, _, l3 = m.clf_transformer
         xt = l3(self._bn(l0(h), bn, True, 0.0)).contiguous()
@@ -214,8 +215,18 @@ class PartitionedTrainer:
         cs = (m.clf_base, m.clf_target, m.clf_target)
         a_t = torch.stack([c.a_f_t2s.weight.reshape(-1) for c in cs])
         a_s = torch.stack([c.a_f_s2t.weight.reshape(-1) for c in cs])
-        logp = _AggregateHeadsFn.apply(self.csr, self.mask_ext_u8, C, m.clf_base.negative_slope, a_t, a_s, *pairs)[:nl, :, :C]
-        return logp[:, 0], logp[:, 1], logp[:, 2]
+        if ops.heads_log_softmax_supported(3, C):
+            logp = _AggregateHeadsFn.apply(self.csr, self.mask_ext_u8, C, m.clf_base.negative_slope, a_t, a_s, *pairs)[:nl, :, :C]
+            return logp[:, 0], logp[:, 1], logp[:, 2]
+        if ops.wide_heads_supported(3, C):
+            logp = _AggregateWideHeadsFn.apply(self.csr, self.mask_ext_u8, C, m.clf_base.negative_slope, a_t, a_s,
+                                               *pairs)[:nl, :, :C]
+            return logp[:, 0], logp[:, 1], logp[:, 2]
+        outs = []
+        for j, c in enumerate(cs):
+            o = _AggregateFn.apply(pairs[2 * j], pairs[2 * j + 1], a_t[j], a_s[j], self.csr, self.mask_ext_u8, C, c.negative_slope)
+            outs.append(F.log_softmax(o[:nl, :C], dim=1))
+        return tuple(outs)
 
     # ---- loss / gradients ------------------------------------------------------------------------------------------------
     def reference_loss(self, out, y_local, train_mask_local):

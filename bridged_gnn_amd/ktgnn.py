@@ -282,6 +282,36 @@ class _AggregateHeadsFn(torch.autograd.Function):
         return (None, None, None, None, da_t, da_s, *tabs)
 
 
+class _AggregateWideHeadsFn(torch.autograd.Function):
+    """`_AggregateHeadsFn` for wide classes (4 < D <= 32, `ops.wide_heads_supported`): the three classifier convs in ONE CSR walk
+    forward (`bgnn_adaptedconv_aggregate_heads_wide_f32`, log_softmax per head in its epilogue) and one walk per backward pass;
+    only the rows' softmax state is kept, no per-edge alpha.  No host sync; workspaces come from torch (graph-capture safe).
+    inputs: `heads` (h_t2s, h_s2t) pairs of [N, pad4(D)] tables, then a_t2s / a_s2t as [heads, D] -> log-probs [N, heads, pad4(D)]."""
+
+    @staticmethod
+    def forward(ctx, csr, mask_u8, D, slope, a_t2s, a_s2t, *tables):
+        heads = len(tables) // 2
+        t2s = torch.cat(tables[0::2], dim=1)
+        s2t = torch.cat(tables[1::2], dim=1)
+        a_t2s, a_s2t = a_t2s.contiguous(), a_s2t.contiguous()
+        out, ms = ops.adaptedconv_aggregate_heads_wide(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, heads, slope)
+        ctx.save_for_backward(t2s, s2t, a_t2s, a_s2t, out, ms, mask_u8)
+        ctx.cfg = (csr, D, slope, heads)
+        return out.view(t2s.shape[0], heads, ops.pad4(D))
+
+    @staticmethod
+    def backward(ctx, grad):
+        t2s, s2t, a_t2s, a_s2t, out, ms, mask_u8 = ctx.saved_tensors
+        csr, D, slope, heads = ctx.cfg
+        ld = ops.pad4(D)
+        g = grad.reshape(out.shape).contiguous()
+        dt, ds, da_t, da_s = ops.adaptedconv_aggregate_heads_wide_bwd(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, heads, out, ms, g, slope)
+        tabs = []
+        for h in range(heads):
+            tabs += [dt[:, ld * h:ld * (h + 1)].contiguous(), ds[:, ld * h:ld * (h + 1)].contiguous()]
+        return (None, None, None, None, da_t, da_s, *tabs)
+
+
 class _TransformFn(torch.autograd.Function):
     """(h_t2s, h_s2t) = domain-shifted dense transform (KTGNN.py:275-284) through the fused HIP kernel; the backward is
     written out by hand so that it is two plain GEMMs + row reductions instead of torch differentiating the
@@ -869,6 +899,20 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
             a_t = torch.stack([c.a_f_t2s.weight.reshape(-1) for c in cs])
             a_s = torch.stack([c.a_f_s2t.weight.reshape(-1) for c in cs])
             logp = _AggregateHeadsFn.apply(csr, mask_u8, C, self.clf_base.negative_slope, a_t, a_s, *tabs)[:, :, :C]
+            return logp[:, 0], logp[:, 1], logp[:, 2], None                                             # :432,:434,:433
+        if (self.training and torch.is_grad_enabled() and not (self.clf_base.root_weight or self.clf_base.normalize)
+                and ops.wide_heads_supported(3, C) and x.dtype == torch.float32
+                and os.environ.get("BGNN_WIDE_TRAIN_HEADS", "0") == "1"):
+            # opt-in: the same stage for 4 < C <= 32 (office, 31 classes) through the wide three-head walk
+            sums_x = ops.domain_sums(_pad_cols4(x.detach()), mask_u8)
+            l0, bn, _, l3 = self.clf_transformer
+            xt = l3(bn_relu_dropout_train(l0(x), bn, True, 0.0)).contiguous()
+            tabs = (*self.clf_base._transform_autograd(x, mask_u8, sums_x), *self.clf_target._transform_autograd(x, mask_u8, sums_x),
+                    *self.clf_target._transform_autograd(xt, mask_u8))
+            cs = (self.clf_base, self.clf_target, self.clf_target)
+            a_t = torch.stack([c.a_f_t2s.weight.reshape(-1) for c in cs])
+            a_s = torch.stack([c.a_f_s2t.weight.reshape(-1) for c in cs])
+            logp = _AggregateWideHeadsFn.apply(csr, mask_u8, C, self.clf_base.negative_slope, a_t, a_s, *tabs)[:, :, :C]
             return logp[:, 0], logp[:, 1], logp[:, 2], None                                             # :432,:434,:433
         if self.clf_base.root_weight or self.clf_base.normalize or torch.is_grad_enabled() or self.training:
             logits_base = self.clf_base(x, None, central_mask=central_mask, csr=csr)                      # :432

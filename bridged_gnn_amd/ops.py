@@ -9,7 +9,8 @@ from . import _lib as L
 
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
-           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add"]
+           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "wide_heads_supported",
+           "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd"]
 
 
 def pad4(n):
@@ -690,6 +691,48 @@ def adaptedconv_aggregate_heads_bwd(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, hea
         L.ptr(out), L.ptr(state_ms), L.ptr(grad_out), int(bool(log_softmax)), L.ptr(dh_t2s), L.ptr(dh_s2t),
         L.ptr(da_t2s), L.ptr(da_s2t), L.ptr(ws), wsb, L.stream())
     L.check(rc, "bgnn_adaptedconv_aggregate_heads_bwd_f32")
+    return dh_t2s, dh_s2t, da_t2s, da_s2t
+
+
+def wide_heads_supported(heads, D):
+    """Envelope of the wide three-head classifier walk (bgnn.h: bgnn_adaptedconv_aggregate_heads_wide_f32): 4 < D <= 32."""
+    return heads in (2, 3) and 4 < int(D) <= 32
+
+
+def adaptedconv_aggregate_heads_wide(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, heads, negative_slope=0.1):
+    """`heads` interleaved wide convs ([N, heads*pad4(D)] tables, a_* [heads, D]) in one CSR walk, log_softmax per head:
+    -> (log-probs [N, heads*pad4(D)] (pad columns 0), state_ms [N, heads, 2] for the backward)."""
+    lib = L.lib()
+    N, ld = csr.num_nodes, pad4(D)
+    assert t2s.shape == (N, heads * ld) and s2t.shape == t2s.shape and t2s.is_contiguous() and s2t.is_contiguous()
+    out = torch.empty(N, heads * ld, dtype=torch.float32, device=t2s.device)
+    ms = torch.empty(N, heads, 2, dtype=torch.float32, device=t2s.device)
+    rc = lib.bgnn_adaptedconv_aggregate_heads_wide_f32(
+        L.ptr(t2s), L.ptr(s2t), ld, L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col), L.ptr(mask_u8),
+        N, int(D), int(heads), float(negative_slope), L.ptr(out), L.ptr(ms), L.stream())
+    L.check(rc, "bgnn_adaptedconv_aggregate_heads_wide_f32")
+    return out, ms
+
+
+def adaptedconv_aggregate_heads_wide_bwd(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, heads, out, state_ms, grad_out,
+                                         negative_slope=0.1):
+    """backward of `adaptedconv_aggregate_heads_wide` (grad_out = dL/dlog-probs, [N, heads*pad4(D)]):
+    -> (dh_t2s, dh_s2t [N, heads*pad4(D)], da_t2s, da_s2t [heads, D]); deterministic (no float atomics)."""
+    lib = L.lib()
+    dev = t2s.device
+    N, ld = csr.num_nodes, pad4(D)
+    assert t2s.shape == (N, heads * ld) and t2s.is_contiguous() and s2t.is_contiguous() and out.is_contiguous() and grad_out.is_contiguous()
+    da_t2s = torch.empty(heads, D, dtype=torch.float32, device=dev)
+    da_s2t = torch.empty(heads, D, dtype=torch.float32, device=dev)
+    dh_t2s, dh_s2t = torch.empty_like(t2s), torch.empty_like(s2t)
+    t_rowptr, _, t_dst = csr.transposed()
+    wsb = lib.bgnn_aggregate_heads_wide_bwd_workspace_bytes(N, heads, ld)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    rc = lib.bgnn_adaptedconv_aggregate_heads_wide_bwd_f32(
+        L.ptr(t2s), L.ptr(s2t), ld, L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col), L.ptr(mask_u8),
+        L.ptr(t_rowptr), L.ptr(t_dst), N, int(D), int(heads), float(negative_slope), L.ptr(out), L.ptr(state_ms), L.ptr(grad_out),
+        L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), L.ptr(ws), wsb, L.stream())
+    L.check(rc, "bgnn_adaptedconv_aggregate_heads_wide_bwd_f32")
     return dh_t2s, dh_s2t, da_t2s, da_s2t
 
 

@@ -380,6 +380,31 @@ int bgnn_adaptedconv_aggregate_heads_bwd_hub_f32(const float* h_t2s, const float
                                                  const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
                                                  void* ws, size_t ws_bytes, void* stream);
 
+/* The classifier stage's three-head walk for WIDE classes (KT-GNN trained on office, 31 classes; ABI 113, additive): `heads`
+ * (2 or 3) interleaved convs, 4 < D <= 32, tables / out [N][heads][ldh] with ldh = pad4(D), a_* [heads][D].  One CSR walk for all
+ * heads (each in-neighbour id read once), per head the GATv2 logit, an online softmax (alpha = p / (s + 1e-16)), the weighted sum
+ * and the log_softmax over the D classes (KTGNN.py:435); pad columns of `out` are written 0.  `state_ms` [N][heads][2] receives
+ * each row's (max, sum) for the backward; nothing per edge is written.  A row with no in-edges gives log_softmax(0) = -log D.
+ * Outside the envelope (D <= 4, D > 32, heads not 2 | 3, ldh != pad4(D)): BGNN_E_SHAPE.  No workspace. */
+int bgnn_adaptedconv_aggregate_heads_wide_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
+                                              const float* a_t2s, const float* a_s2t,
+                                              const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                              int64_t N, int32_t D, int32_t heads, float negative_slope,
+                                              float* out, float* state_ms, void* stream);
+/* Its pull-form backward (grad_out = dL/dlogp, [N][heads][ldh]): the row-local log_softmax adjoint first, alpha rebuilt from
+ * state_ms; pass A over destinations, pass B over sources (the by-source view t_rowptr / t_dst).  Every dH row (pad columns 0) is
+ * written exactly once; da_* [heads][D] are written (not accumulated) from per-block partial sums added in a fixed order, so two
+ * identical calls are bitwise equal (N = 0: da_* are written as zeros).  Same envelope.  ws: bgnn_aggregate_heads_wide_bwd_workspace_bytes(N, heads, ldh). */
+size_t bgnn_aggregate_heads_wide_bwd_workspace_bytes(int64_t N, int32_t heads, int64_t ldh);
+int bgnn_adaptedconv_aggregate_heads_wide_bwd_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
+                                                  const float* a_t2s, const float* a_s2t,
+                                                  const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                                  const int32_t* t_rowptr, const int32_t* t_dst,
+                                                  int64_t N, int32_t D, int32_t heads, float negative_slope,
+                                                  const float* out, const float* state_ms, const float* grad_out,
+                                                  float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
+                                                  void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * GraphSAGE mean aggregation (the --no_dtc model of main_graph_knowledge_transfer.py:326,:414-417):
  *     models/backbones.py:440-498 -- torch_sparse matmul(adj_t, x, reduce='mean') inside each SAGEConv (PyG sage_conv),
