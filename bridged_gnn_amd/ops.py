@@ -10,7 +10,8 @@ from . import _lib as L
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
            "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "wide_heads_supported",
-           "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd"]
+           "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd", "pair_csr", "pair_mlp_stats", "pair_mlp_loss",
+           "pair_mlp_segsum", "pair_mlp_eval", "PAIR_MLP_WIDTH"]
 
 
 def pad4(n):
@@ -911,3 +912,105 @@ def rows_segment_add(src, seg_ptr, idx, row, dst, D=None, accumulate=True):
                                            L.stream())
     L.check(rc, "bgnn_rows_segment_add_f32")
     return dst
+
+
+# ---- similarity-learner pair passes (bgnn.h: bgnn_pair_mlp_*, csrc/bgnn_pair_mlp.hip) -------------------------------------------
+PAIR_MLP_WIDTH = 128          # u = Linear(2H, 128) output width of Similar_v2(mode='mlp'), models/models.py:918
+
+
+def _pair_ws(P, dev):
+    return torch.empty(int(L.lib().bgnn_pair_mlp_workspace_bytes(int(P))), dtype=torch.uint8, device=dev)
+
+
+def pair_csr(idx_by, idx_other, n_by, n_other):
+    """Pairs grouped by `idx_by` (the by-destination CSR build of bgnn_build_dst_csr over the edges idx_other -> idx_by, self
+    loops kept, stable): -> (rowptr int32 [n_by+1], perm int32 [P] = pair ids, input order inside a node).  No host read."""
+    lib = L.lib()
+    P = int(idx_by.shape[0])
+    N = max(int(n_by), int(n_other))
+    if P + N >= 1 << 31:
+        # rowptr / perm are int32 and the build takes P + N slots; the pair passes would otherwise clamp wrapped ids silently
+        raise ValueError(f"pair list too large for int32 CSR offsets: P + N = {P + N} >= 2^31")
+    dev = idx_by.device
+    ei = torch.stack((idx_other, idx_by)).contiguous()
+    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(P + N, dtype=torch.int32, device=dev)
+    perm = torch.empty(P + N, dtype=torch.int32, device=dev)
+    e_out = torch.empty(1, dtype=torch.int64, device=dev)
+    wsb = lib.bgnn_csr_workspace_bytes(N, P)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    rc = lib.bgnn_build_dst_csr(L.ptr(ei), P, N, 0, L.ptr(rowptr), L.ptr(col), L.ptr(perm), L.ptr(e_out), L.ptr(ws), wsb, L.stream())
+    L.check(rc, "bgnn_build_dst_csr")
+    return rowptr[:int(n_by) + 1], perm[:P]
+
+
+def _pm_tables(A, B, idx1, idx2):
+    assert A.dtype == torch.float32 and B.dtype == torch.float32 and A.shape[1] == PAIR_MLP_WIDTH == B.shape[1]
+    assert idx1.dtype == torch.int64 and idx2.dtype == torch.int64 and idx1.shape == idx2.shape and idx1.dim() == 1
+    assert idx1.is_contiguous() and idx2.is_contiguous()
+    return (L.ptr_rows(A), A.stride(0), int(A.shape[0]), L.ptr_rows(B), B.stride(0), int(B.shape[0]), L.ptr(idx1), L.ptr(idx2),
+            int(idx1.shape[0]))
+
+
+def pair_mlp_stats(A, B, idx1, idx2, momentum=0.1, running_mean=None, running_var=None):
+    """BN2's batch statistics of u_p = A[idx1[p]] + B[idx2[p]] -> fp64 [256] (mean, biased variance); updates the running
+    buffers (fp32 [128]) in place like nn.BatchNorm1d in train mode."""
+    P = int(idx1.shape[0])
+    if P <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size [{P}, {PAIR_MLP_WIDTH}]")
+    stats = torch.empty(2 * PAIR_MLP_WIDTH, dtype=torch.float64, device=A.device)
+    ws = _pair_ws(P, A.device)
+    rc = L.lib().bgnn_pair_mlp_stats_f32(*_pm_tables(A, B, idx1, idx2), float(momentum), L.ptr(running_mean), L.ptr(running_var),
+                                         L.ptr(stats), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_pair_mlp_stats_f32")
+    return stats
+
+
+def pair_mlp_loss(A, B, idx1, idx2, y_u8, stats, gamma2, beta2, w2, b2, eps=1e-5):
+    """-> (p [P], dl [P] = d mean-BCE / d logit, sums fp64 [392]) (bgnn.h: bgnn_pair_mlp_loss_f32 for the layout of sums)."""
+    P = int(idx1.shape[0])
+    assert y_u8.dtype == torch.uint8 and y_u8.shape == (P,)
+    dev = A.device
+    p = torch.empty(P, dtype=torch.float32, device=dev)
+    dl = torch.empty(P, dtype=torch.float32, device=dev)
+    sums = torch.empty(3 * PAIR_MLP_WIDTH + 8, dtype=torch.float64, device=dev)
+    ws = _pair_ws(P, dev)
+    t = _pm_tables(A, B, idx1, idx2)
+    rc = L.lib().bgnn_pair_mlp_loss_f32(*t[:8], L.ptr(y_u8), t[8], L.ptr(stats), L.ptr(gamma2), L.ptr(beta2),
+                                        L.ptr(w2), L.ptr(b2), float(eps), L.ptr(p), L.ptr(dl), L.ptr(sums), L.ptr(ws), ws.numel(),
+                                        L.stream())
+    L.check(rc, "bgnn_pair_mlp_loss_f32")
+    return p, dl, sums
+
+
+def pair_mlp_segsum(own, other, rowptr, perm, idx_other, dl, stats, sums, gamma2, beta2, w2, eps=1e-5, out=None):
+    """S [n_own, 128]: per node of `own`, the sum of du_p over its pairs (rowptr / perm from `pair_csr`)."""
+    n_own = int(rowptr.shape[0]) - 1
+    assert n_own == own.shape[0] and own.shape[1] == PAIR_MLP_WIDTH == other.shape[1]
+    assert rowptr.dtype == torch.int32 and perm.dtype == torch.int32 and idx_other.dtype == torch.int64
+    if out is None:
+        out = torch.empty(n_own, PAIR_MLP_WIDTH, dtype=torch.float32, device=own.device)
+    rc = L.lib().bgnn_pair_mlp_segsum_f32(L.ptr_rows(own), own.stride(0), n_own, L.ptr_rows(other), other.stride(0), int(other.shape[0]),
+                                          L.ptr(rowptr), L.ptr(perm), L.ptr(idx_other), int(idx_other.shape[0]), L.ptr(dl),
+                                          L.ptr(stats), L.ptr(sums), L.ptr(gamma2), L.ptr(beta2), L.ptr(w2), float(eps),
+                                          L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_pair_mlp_segsum_f32")
+    return out
+
+
+def pair_mlp_eval(A, B, idx1, idx2, scale2, shift2, w2, b2, y_u8=None):
+    """Eval-mode scores p [P] (running statistics: BN2 as scale2 / shift2) and, with labels, fp64 counts [TP, FP, FN]."""
+    P = int(idx1.shape[0])
+    dev = A.device
+    p = torch.empty(P, dtype=torch.float32, device=dev)
+    counts = torch.empty(4, dtype=torch.float64, device=dev) if y_u8 is not None else None
+    if P == 0:
+        if counts is not None:
+            counts.zero_()
+        return p, counts
+    ws = _pair_ws(P, dev)
+    t = _pm_tables(A, B, idx1, idx2)
+    rc = L.lib().bgnn_pair_mlp_eval_f32(*t[:8], L.ptr(y_u8), t[8], L.ptr(scale2), L.ptr(shift2), L.ptr(w2), L.ptr(b2),
+                                        L.ptr(p), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_pair_mlp_eval_f32")
+    return p, None if counts is None else counts[:3]

@@ -29,7 +29,8 @@ extern "C" {
  * 111 adds bgnn_adaptedconv_transform_need_f32, 112 bgnn_classifier_stage_f32, 113 bgnn_adaptedconv_aggregate_bounded_f32 (all
  * call-compatible with 110).  The GraphSAGE entry points (bgnn_sage_mean_aggregate_f32, bgnn_sage_mean_aggregate_bwd_f32 and its
  * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113.  The
- * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32. */
+ * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32, and for the
+ * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -506,6 +507,40 @@ int bgnn_gather_rows_f32(const float* src, int64_t src_rows, int64_t ld_src, con
 size_t bgnn_coalesce_workspace_bytes(int64_t E);
 int bgnn_coalesce_i64(int64_t* edge_index, int64_t E, int64_t num_nodes, int64_t* E_out_dev,
                       void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Train-mode pair passes of the mlp similarity scorer Similar_v2(mode='mlp')      models/models.py:913-920, :949-951, :967-970
+ * under train_adv_few_shot's BCE (scripts.py:36-50), for the similarity-learner training of bridged_gnn_amd/simlearner.py.
+ * BN1 (batch statistics) and Linear(2H, 128) are per-node work done by the caller: u_p = A[idx1[p]] + B[idx2[p]] with
+ * A [nA, 128] and B [nB, 128] row-strided fp32 tables (16-B aligned, ld >= 128, ld % 4 == 0); idx1 / idx2 int64 [P], out-of-range
+ * ids are clamped.  Every column sum is fp64 over a grid fixed by P in a fixed order (no atomics): results are run-to-run
+ * identical.  ws: bgnn_pair_mlp_workspace_bytes(P).  P <= 1 is BGNN_E_SHAPE in train mode (torch raises on one value per channel).
+ * stats:  stats[0:128] = batch mean of u, stats[128:256] = biased variance (fp64); with run_mean_opt / run_var_opt the
+ *         nn.BatchNorm1d running update (momentum, unbiased variance P / (P - 1)) of BN2.
+ * loss:   BN2 (stats, eps), ReLU, w2 dot, b2 (device scalar), sigmoid -> p_out [P]; dl_out [P] = d(mean BCE) / d logit along
+ *         torch's chain ((p - y) / max((1 - p) p, 1e-12) / P * (1 - p) p: exactly 0 where p is 0 or 1); y uint8 [P] (0 / 1).
+ *         sums [392] fp64: [0:128) sum dy, [128:256) sum dy * x2, [256:384) sum dl * h (= dw2), then sum dl (= db2), sum of the
+ *         BCE terms (log clamp -100), TP, FP, FN at p > 0.5; dy = dl * w2 * [BN2 output > 0] (sum dy = dbeta2, sum dy x2 = dgamma2).
+ * segsum: S[n] = sum over the pairs of node n (CSR rowptr [n_own+1] / perm [P] = pair ids, e.g. bgnn_build_dst_csr(eperm) of the
+ *         list by n) of du_p = g2 rstd2 (dy_p - sum dy / P - x2_p sum(dy x2) / P), u_p = own[n] + other[idx_other[p]]; every row
+ *         written once (zero rows for nodes without pairs).  Called with (A, B, idx2) for S1 and (B, A, idx1) for S2.
+ * eval:   running-statistics form: BN2 as scale2 / shift2, p_out [P]; with y_opt, counts_opt[0:3] = TP, FP, FN (fp64).    */
+size_t bgnn_pair_mlp_workspace_bytes(int64_t P);
+int bgnn_pair_mlp_stats_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* idx1,
+                            const int64_t* idx2, int64_t P, float momentum, float* run_mean_opt, float* run_var_opt, double* stats,
+                            void* ws, size_t ws_bytes, void* stream);
+int bgnn_pair_mlp_loss_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* idx1,
+                           const int64_t* idx2, const uint8_t* y, int64_t P, const double* stats, const float* g2, const float* be2,
+                           const float* w2, const float* b2, float eps, float* p_out, float* dl_out, double* sums, void* ws,
+                           size_t ws_bytes, void* stream);
+int bgnn_pair_mlp_segsum_f32(const float* own, int64_t ld_own, int64_t n_own, const float* other, int64_t ld_other, int64_t n_other,
+                             const int32_t* rowptr, const int32_t* perm, const int64_t* idx_other, int64_t P, const float* dl,
+                             const double* stats, const double* sums, const float* g2, const float* be2, const float* w2, float eps,
+                             float* S, int64_t ld_s, void* stream);
+int bgnn_pair_mlp_eval_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* idx1,
+                           const int64_t* idx2, const uint8_t* y_opt, int64_t P, const float* scale2, const float* shift2,
+                           const float* w2, const float* b2, float* p_out, double* counts_opt, void* ws, size_t ws_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }
