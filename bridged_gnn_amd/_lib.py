@@ -94,6 +94,11 @@ SIGNATURES = {
                                        _SZ, _P]),
     "bgnn_pair_mlp_segsum_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _F32, _P, _I64, _P]),
     "bgnn_pair_mlp_eval_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "bgnn_pair_cos_loss_workspace_bytes": (_SZ, [_I64]),
+    "bgnn_pair_cos_count_workspace_bytes": (_SZ, [_I64, _I64]),
+    "bgnn_pair_cos_loss_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "bgnn_pair_cos_segsum_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "bgnn_pair_cos_count_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _SZ, _P]),
     "bgnn_sage_mean_aggregate_bwd_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_sage_mean_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _INT, _F32, _P, _I64, _P, _I64,
                                                  _P, _SZ, _P]),
@@ -114,7 +119,7 @@ def source_hash():
 
 # keep in step with HASHED in csrc/Makefile
 _HASHED_SOURCES = ("bgnn_api.hip", "bgnn_csr.hip", "bgnn_transform.hip", "bgnn_transform_stream.hip", "bgnn_transform_cls.hip", "bgnn_aggregate.hip", "bgnn_aggregate_bwd.hip",
-                   "bgnn_aggregate_bwd_fast.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_pair_mlp.hip", "bgnn_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
+                   "bgnn_aggregate_bwd_fast.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_pair_mlp.hip", "bgnn_pair_cos.hip", "bgnn_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
 
 
 def _sidecar_hash():

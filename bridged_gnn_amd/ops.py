@@ -11,7 +11,8 @@ __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "a
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
            "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "wide_heads_supported",
            "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd", "pair_csr", "pair_mlp_stats", "pair_mlp_loss",
-           "pair_mlp_segsum", "pair_mlp_eval", "PAIR_MLP_WIDTH"]
+           "pair_mlp_segsum", "pair_mlp_eval", "PAIR_MLP_WIDTH", "pair_cos_loss", "pair_cos_segsum", "pair_cos_count",
+           "PAIR_COS_WIDTH"]
 
 
 def pad4(n):
@@ -1014,3 +1015,64 @@ def pair_mlp_eval(A, B, idx1, idx2, scale2, shift2, w2, b2, y_u8=None):
                                         L.ptr(p), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
     L.check(rc, "bgnn_pair_mlp_eval_f32")
     return p, None if counts is None else counts[:3]
+
+
+# ---- cosine similarity-learner pair passes (bgnn.h: bgnn_pair_cos_*, csrc/bgnn_pair_cos.hip) ------------------------------------
+PAIR_COS_WIDTH = 128          # q = u + biasatt(u): biasatt is Linear(128, 64) -> Linear(64, 128), models/models.py:70-74
+
+
+def _pc_table(T):
+    assert T.dtype == torch.float32 and T.dim() == 2 and T.shape[1] == PAIR_COS_WIDTH and T.stride(1) == 1
+    return L.ptr_rows(T), T.stride(0), int(T.shape[0])
+
+
+def pair_cos_loss(A, B, idx1, idx2, y_u8):
+    """Train-mode pair pass over normalised tables: -> (p [P], dl [P] = d mean-BCE / d cos, sums fp64 [4] = BCE sum, TP, FP, FN)."""
+    P = int(idx1.shape[0])
+    assert idx1.dtype == torch.int64 and idx2.dtype == torch.int64 and idx1.shape == idx2.shape and idx1.dim() == 1
+    assert idx1.is_contiguous() and idx2.is_contiguous() and y_u8.dtype == torch.uint8 and y_u8.shape == (P,)
+    if P < 1:
+        raise ValueError("pair_cos_loss: empty pair list")
+    dev = A.device
+    p = torch.empty(P, dtype=torch.float32, device=dev)
+    dl = torch.empty(P, dtype=torch.float32, device=dev)
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(L.lib().bgnn_pair_cos_loss_workspace_bytes(P)), dtype=torch.uint8, device=dev)
+    rc = L.lib().bgnn_pair_cos_loss_f32(*_pc_table(A), *_pc_table(B), L.ptr(idx1), L.ptr(idx2), L.ptr(y_u8), P, L.ptr(p), L.ptr(dl),
+                                        L.ptr(sums), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_pair_cos_loss_f32")
+    return p, dl, sums
+
+
+def pair_cos_segsum(other, rowptr, perm, idx_other, dl, out=None):
+    """G [n_own, 128]: per node, sum of dl[p] * other[idx_other[p]] over its pairs (rowptr / perm from `pair_csr`); atomic-free."""
+    n_own = int(rowptr.shape[0]) - 1
+    P = int(idx_other.shape[0])
+    assert rowptr.dtype == torch.int32 and perm.dtype == torch.int32 and idx_other.dtype == torch.int64 and dl.dtype == torch.float32
+    assert perm.shape[0] == P and dl.shape[0] == P and idx_other.is_contiguous() and dl.is_contiguous()
+    if out is None:
+        out = torch.empty(n_own, PAIR_COS_WIDTH, dtype=torch.float32, device=other.device)
+    if n_own == 0:
+        return out
+    if P == 0:
+        return out.zero_()
+    rc = L.lib().bgnn_pair_cos_segsum_f32(*_pc_table(other), L.ptr(rowptr), L.ptr(perm), L.ptr(idx_other), P, L.ptr(dl), n_own,
+                                          L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_pair_cos_segsum_f32")
+    return out
+
+
+def pair_cos_count(A, B, rows1, rows2, lab1, lab2):
+    """int64 [4] = TP, FP, FN, TN of (sigmoid(A[rows1[i]] . B[rows2[j]]) > 0.5) against lab1[rows1[i]] == lab2[rows2[j]] over the
+    whole product rows1 x rows2 (eval_within_domain / eval_cross_domain's Cartesian lists, never materialised)."""
+    assert rows1.dtype == torch.int64 and rows2.dtype == torch.int64 and rows1.dim() == 1 and rows2.dim() == 1
+    assert lab1.dtype == torch.int64 and lab2.dtype == torch.int64
+    assert lab1.shape[0] == A.shape[0] and lab2.shape[0] == B.shape[0] and lab1.is_contiguous() and lab2.is_contiguous()
+    rows1, rows2 = rows1.contiguous(), rows2.contiguous()
+    m1, m2 = int(rows1.shape[0]), int(rows2.shape[0])
+    counts = torch.empty(4, dtype=torch.int64, device=A.device)
+    ws = torch.empty(max(1, int(L.lib().bgnn_pair_cos_count_workspace_bytes(m1, m2))), dtype=torch.uint8, device=A.device)
+    rc = L.lib().bgnn_pair_cos_count_f32(*_pc_table(A), *_pc_table(B), L.ptr(rows1), m1, L.ptr(rows2), m2, L.ptr(lab1), L.ptr(lab2),
+                                         L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_pair_cos_count_f32")
+    return counts

@@ -7,7 +7,8 @@ reference with strict=True and into `bridge.BridgeScorer` without conversion.  T
 passes of csrc/bgnn_pair_mlp.hip (`_PairMlpFn`; derivation in DESIGN.md section 11).  Everything else is per-node torch.
 
 Supported: version v2, backbone 'mlp', sim_mode 'mlp', eval_mode 'sampling', shuffle=False samplers (what the office recipes
-run, run.sh #2/#3).  v1, sim_mode 'cosine', backbone 'gnn', eval_mode 'all' and shuffling raise NotImplementedError.
+run, run.sh #2/#3).  sim_mode 'cosine', backbone 'gnn', eval_mode 'all' and shuffling raise NotImplementedError.  The v1 learner
+(Adversarial_Learner, the cosine scorer Similar) is bridged_gnn_amd.simlearner_v1.
 """
 import copy
 import os

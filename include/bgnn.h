@@ -30,7 +30,8 @@ extern "C" {
  * call-compatible with 110).  The GraphSAGE entry points (bgnn_sage_mean_aggregate_f32, bgnn_sage_mean_aggregate_bwd_f32 and its
  * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113.  The
  * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32, and for the
- * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size. */
+ * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size, and for the cosine
+ * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -541,6 +542,34 @@ int bgnn_pair_mlp_eval_f32(const float* A, int64_t lda, int64_t nA, const float*
                            const int64_t* idx2, const uint8_t* y_opt, int64_t P, const float* scale2, const float* shift2,
                            const float* w2, const float* b2, float* p_out, double* counts_opt, void* ws, size_t ws_bytes,
                            void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
+ * Pair passes of the cosine similarity scorer Similar (v1)                        models/models.py:67-169
+ * under train_adv_few_shot's BCE (scripts.py:36-50) and the Cartesian evaluation of eval_within_domain / eval_cross_domain
+ * (scripts.py:98-190), for bridged_gnn_amd/simlearner_v1.py.  q = u + biasatt(u), u = lin_self(z) and the row normalisation
+ * q^ = q / max(|q|, 1e-8) are per-node work done by the caller: A [nA, 128], B [nB, 128] are normalised row-strided fp32
+ * tables (16-B aligned, ld >= 128, ld % 4 == 0); out-of-range ids are clamped.  No atomics: results are run-to-run identical.
+ * loss:   cos_p = A[idx1[p]] . B[idx2[p]], p_out [P] = sigmoid(cos_p) (fp32), dl_out [P] = d(mean BCE) / d cos_p along torch's
+ *         chain ((p - y) / max((1 - p) p, 1e-12) / P * (1 - p) p); y uint8 [P] (0 / 1).  sums [4] fp64 in a fixed order: sum of
+ *         the BCE terms (log clamp -100), TP, FP, FN at p > 0.5.  ws: bgnn_pair_cos_loss_workspace_bytes(P).  P >= 1.
+ * segsum: G[n] = sum over the pairs of node n (CSR rowptr [n_own+1] / perm [P] = pair ids, e.g. the pair CSR of the list by n)
+ *         of dl[p] * other[idx_other[p]], fp64 accumulation; every row of G [n_own, 128] written once (zero rows for nodes
+ *         without pairs).
+ * count:  counts [4] int64 = TP, FP, FN, TN of (sigmoid(A[rows1[i]] . B[rows2[j]]) > 0.5 in fp32) against
+ *         (lab1[rows1[i]] == lab2[rows2[j]]) over every (i, j) of rows1 [m1] x rows2 [m2] (int64 ids; lab1 [nA], lab2 [nB]
+ *         int64), no pair materialised; m1 or m2 may be 0.  ws: bgnn_pair_cos_count_workspace_bytes(m1, m2).             */
+size_t bgnn_pair_cos_loss_workspace_bytes(int64_t P);
+size_t bgnn_pair_cos_count_workspace_bytes(int64_t m1, int64_t m2);
+int bgnn_pair_cos_loss_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* idx1,
+                           const int64_t* idx2, const uint8_t* y, int64_t P, float* p_out, float* dl_out, double* sums, void* ws,
+                           size_t ws_bytes, void* stream);
+int bgnn_pair_cos_segsum_f32(const float* other, int64_t ld_other, int64_t n_other, const int32_t* rowptr, const int32_t* perm,
+                             const int64_t* idx_other, int64_t P, const float* dl, int64_t n_own, float* G, int64_t ld_g,
+                             void* stream);
+int bgnn_pair_cos_count_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* rows1,
+                            int64_t m1, const int64_t* rows2, int64_t m2, const int64_t* lab1, const int64_t* lab2, long long* counts,
+                            void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
