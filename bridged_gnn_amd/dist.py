@@ -28,6 +28,10 @@ import weakref
 import numpy as np
 import torch
 import torch.distributed as dist
+import torch.nn.functional as F
+
+from . import ops
+from .ktgnn import _pad_cols4, bn_eval_affine
 
 __all__ = ["partition_nodes", "PartitionPlan", "HaloExchange", "PartitionedKTGNN", "all_gather_rows", "shard_range"]
 
@@ -242,7 +246,6 @@ class HaloExchange:
         if self.mode == "allgather" and (p.world > 1 or self.always):
             return self._start_allgather(big)
         if big.is_cuda and big.dtype == torch.float32 and big.shape[1] % 4 == 0 and big.stride(1) == 1:
-            from . import ops
             send = ops.gather_rows(big, self.send_rows)              # [sum(send_splits), ld]
         else:                                                        # host tensors (gloo tests of the host logic)
             send = big.index_select(0, self.send_rows)
@@ -315,7 +318,6 @@ class PartitionedKTGNN:
 
     def __init__(self, model, edge_index, central_mask, rank, world, device, owner=None, group=None,
                  always_communicate=False, cache_input_halo=True, halo_mode="auto"):
-        from . import ops
         # cache_input_halo: the FIRST conv reads the graph's input features, which do not change between forwards (the
         # reference trains 300 epochs on one `data.x`).  Their halo rows are fetched once per version of x (same send
         # lists, same all_to_all) and kept next to the local rows; every forward then transforms local + halo rows itself
@@ -359,7 +361,6 @@ class PartitionedKTGNN:
         """(1) local-source edges of every row (interior rows finish, boundary rows park their state) while the
         exchange is in flight; (2) wait; (3) remote-source edges of the boundary rows.  Lists = several convs that
         share the exchange."""
-        from . import ops
         p = self.plan
         single = not isinstance(convs, (list, tuple))
         if single:
@@ -394,7 +395,6 @@ class PartitionedKTGNN:
     def _input_ext(self, x):
         """[x local rows ; x halo rows] (columns padded to a multiple of 4) for the current version of the input features:
         the halo is fetched on first use and again whenever x is another tensor object or was written in place."""
-        from .ktgnn import _pad_cols4
         key = self._x_ext_key
         if key is None or key[0]() is not x or key[1] != x._version:
             xp = _pad_cols4(x)
@@ -413,8 +413,6 @@ class PartitionedKTGNN:
     def _conv_resident_halo(self, conv, x, epilogue=None, out_sums=None, arena=None):
         """First conv with resident input halo: all-reduce of the domain sums, transform of local + halo rows, ONE
         aggregation launch over the complete local CSR -- no per-forward row exchange."""
-        from . import ops
-        from .ktgnn import _pad_cols4
         p = self.plan
         xp = _pad_cols4(x)
         # the (all-reduced) domain sums of the static input features are kept with their halo: per version of x one
@@ -442,8 +440,6 @@ class PartitionedKTGNN:
         return out[:, : conv.out_channels], sums
 
     def _conv(self, conv, x, epilogue=None, sums=None, out_sums=None, arena=None):
-        from . import ops
-        from .ktgnn import _pad_cols4
         p = self.plan
         xp = _pad_cols4(x)
         if sums is None:
@@ -469,11 +465,9 @@ class PartitionedKTGNN:
         logp_target_hat) for those rows.  With `cache_input_halo` the halo rows of x are re-fetched whenever x_local is
         a different tensor or was modified in place (`_version`); a captured HIP graph cannot see that check, so
         re-capture after changing x."""
-        import torch.nn.functional as F
         m = self.model
         if m.training:
             raise NotImplementedError("partitioned forward is eval-only (BN batch statistics would need an all-reduce)")
-        from . import ops
         x = x_local.float().contiguous()
         s_h = both = None
         # every float64 accumulator of this forward comes out of ONE zero fill; the two sums that travel in the
@@ -482,7 +476,6 @@ class PartitionedKTGNN:
         arena = ops.ZeroArena(self.device, (len(m.convs) + 3) * (2 * ops.pad4(width) + 2))
         for ind, conv in enumerate(m.convs):
             if m.use_bn:
-                from .ktgnn import bn_eval_affine
                 sc, sh = bn_eval_affine(m.bns[ind])
                 last = ind == len(m.convs) - 1
                 # fused sums in the epilogue (one pass fewer over the rank-local activations; neutral on one GPU)
@@ -497,91 +490,42 @@ class PartitionedKTGNN:
                 x, _ = run(conv, x, arena=arena)
                 x = F.relu(x)
             x = x.contiguous()
-        # the two classifier inputs (h and T(h)) are both row-local once the hidden conv is done: their domain
-        # sums travel in ONE all-reduce
-        from . import ops
-        from .ktgnn import _pad_cols4
-        # h1; T's last Linear is folded into the conv weights; its rank-local domain sums come out of the GEMM epilogue
-        adjacent = both is not None and x.shape[1] == m.clf_transformer[0].weight.shape[0]
-        m._fold_transformer()
-        dout, din = m._tf_w0.shape
-        pack_t = m._composed_target_pack(ops.pad4(dout))
-        raw = None
-        if not (self.world > 1 or self.always) and s_h is not None:
-            # nothing to all-reduce: the three convs' narrow tables in ONE pass over h (bgnn_classifier_stage_f32), as the single-GPU
-            # forward does.  (With ranks the fused kernel would need the all-reduced sums of h BEFORE the pass and of T's hidden
-            # activation AFTER it -- two all-reduces instead of one; a rank's second pass over its 1/N of h costs less.)
-            res = self._classifier_stage(x, None, s_h, None, arena=arena, fuse=True)
-            if res is not None:
-                logp, fused = res
-                if not fused:
-                    logp = F.log_softmax(logp, dim=2)
-                return logp[:, 0], logp[:, 1], logp[:, 2]
-        if (adjacent and x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[1] == din
-                and ops.linear_narrow_supported(din, dout, pack_t)):
-            # fused pair: h1 never reaches HBM; stage A leaves 12 floats per row + the rank-local sums of h1, stage B
-            # (in _classifier_stage, after the all-reduce) finishes the narrow tables
-            s_t = both[s_h.numel():]
-            raw = ops.linear_narrow_transform(x, m._tf_w0, m._tf_b0, self.mask_u8, s_t, pack_t, relu=True)
-            xt = None
-        else:
-            xt, s_t = m._transformer_hidden_eval(x, self.mask_u8, want_sums=True, sums_out=both[s_h.numel():] if adjacent else None)
-            xt = xt.contiguous()
-        if s_h is None:
-            s_h = ops.domain_sums(_pad_cols4(x), self.mask_u8)
-        if raw is None and (s_t is None or s_t.numel() != 2 * _pad_cols4(xt).shape[1] + 2):
-            s_t = ops.domain_sums(_pad_cols4(xt), self.mask_u8)
-        if not (adjacent and s_t.data_ptr() == both[s_h.numel():].data_ptr()):
-            both = torch.cat((s_h, s_t))
-        if self.world > 1 or self.always:
-            both = self._all_reduce(both)
-        s_h, s_t = both[: s_h.numel()], both[s_h.numel():]
-        logp, fused = self._classifier_stage(x, xt, s_h, s_t, raw=raw, pack_t=pack_t)
-        if not fused:
-            logp = F.log_softmax(logp, dim=2)                                    # one launch for the three heads
-        return logp[:, 0], logp[:, 1], logp[:, 2]
-
-    def _classifier_stage(self, x, xt, s_h, s_t, raw=None, pack_t=None, arena=None, fuse=False):
-        """clf_base(x), clf_target(x), clf_target(T(x)) (KTGNN.py:432-434; `xt` = hidden activation h1 of T, whose
-        last Linear is folded into the packed weights) with ONE halo exchange: the six narrow
-        tables are interleaved column-wise in one allocation (row = [base | target | target-hat] x pad4(C) floats),
-        so a halo row carries all three convs' values."""
-        from . import ops
-        from .ktgnn import _pad_cols4
-        m, p = self.model, self.plan
-        C = m.clf_base.out_channels
-        ld = ops.pad4(C)
-        big = torch.empty(2 * p.n_local + p.n_halo, 3 * ld, dtype=torch.float32, device=self.device)
-        views = [(big[p.n_local:, j * ld:(j + 1) * ld], big[:, j * ld:(j + 1) * ld]) for j in range(3)]   # (h_t2s, h_s2t)
-        if fuse:
-            if not m._classifier_stage_fused(x, self.mask_u8, s_h, views, arena):
-                return None                                          # outside the kernel's envelope: the caller takes the separate launches
-        else:
-            m.clf_base.transform(x, self.mask_u8, sums=s_h, partner=m.clf_target, out=[views[0], views[1]])
-            if raw is not None:                                      # stage B of the fused linear -> narrow transform
-                ops.narrow_transform_finish(raw, self.mask_u8, s_t, pack_t, views[2])
-            else:
-                xtp = _pad_cols4(xt)
-                ops.adaptedconv_transform(xtp, self.mask_u8, None, m._composed_target_pack(xtp.shape[1]), out=[views[2]], sums=s_t)
-        self.halo.start(big)
-        akey = (m.clf_base._versions(), m.clf_target._versions())
-        if getattr(m, "_a3_key", None) != akey:                      # same cache as the single-GPU forward
-            convs = (m.clf_base, m.clf_target, m.clf_target)
-            m._a3 = (torch.stack([c.a_f_t2s.weight.detach().reshape(-1) for c in convs]).contiguous(),
-                     torch.stack([c.a_f_s2t.weight.detach().reshape(-1) for c in convs]).contiguous())
-            m._a3_key = akey
-        a_t2s, a_s2t = m._a3
-        out3 = torch.empty(p.n_local, 3 * ld, dtype=torch.float32, device=self.device)
+        # classifier stage (classifier_stage.py): its two inputs (h and T(h)) are both row-local once the hidden conv is done, so
+        # their domain sums travel in ONE all-reduce, between stage A and stage B of head 2.  One allocation
+        # [h_s2t local | h_t2s local | halo] x [base | target | target-hat]: a halo row carries all three convs' values
+        stage, p = m._stage, self.plan
+        big = torch.empty(2 * p.n_local + p.n_halo, 3 * stage.ld, dtype=torch.float32, device=self.device)
         h_t2s, h_s2t = p.table_views(big)                            # interleaved [rows, 3*ld] tables
+        views = stage.views(h_t2s, h_s2t)
+        a = s_t = None
+        if not (self.world > 1 or self.always) and s_h is not None:
+            # nothing to all-reduce: ONE pass over h as on a single GPU.  (With ranks that kernel would need the all-reduced sums of h
+            # BEFORE the pass and of T's hidden activation AFTER it: two all-reduces; a rank's second pass over its 1/N of h costs less.)
+            a = stage.one_pass(x, self.mask_u8, s_h, views, arena)
+        if a is None:
+            # T's rank-local domain sums come out of stage A's epilogue, next to those of h in the arena when the hidden conv left them
+            adjacent = both is not None and x.shape[1] == m.clf_transformer[0].weight.shape[0]
+            a = stage.target_stage_a(x, self.mask_u8, both[s_h.numel():] if adjacent else None)
+            if s_h is None:
+                s_h = ops.domain_sums(_pad_cols4(x), self.mask_u8)
+            if not (adjacent and a[2].data_ptr() == both[s_h.numel():].data_ptr()):
+                both = torch.cat((s_h, a[2]))
+            if self.world > 1 or self.always:
+                both = self._all_reduce(both)
+            s_h, s_t = both[: s_h.numel()], both[s_h.numel():]
+            stage.pair_tables(x, self.mask_u8, s_h, views)
+        stage.target_stage_b(a, self.mask_u8, views[2], s_t)
+        # ONE halo exchange of the interleaved tables and the two-part walk of all three heads
+        self.halo.start(big)
+        a_t2s, a_s2t = stage.attention()
+        out3 = torch.empty(p.n_local, 3 * stage.ld, dtype=torch.float32, device=self.device)
         st = self._state3
         if st is None or st.shape[0] < 3 * p.n_local:
             st = self._state3 = torch.empty(3 * p.n_local, 2, dtype=torch.float32, device=self.device)
-        fused = ops.heads_log_softmax_supported(3, C)                # KTGNN.py:435 in the epilogue of the finishing launches
-        kw = dict(n_dst=p.n_local, out=out3, heads=3, log_softmax=fused)
-        slope = m.clf_base.negative_slope
-        ops.adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, self.csr_L, self.mask_u8, C, slope,
+        kw = dict(n_dst=p.n_local, out=out3, heads=3, log_softmax=stage.fused_log_softmax)   # KTGNN.py:435 in the finishing launches
+        ops.adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, self.csr_L, self.mask_u8, stage.C, stage.slope,
                                   row_begin=0, row_end=p.n_local, state_ms=st, part=1, park_begin=p.n_interior, **kw)
         self.halo.wait()
-        ops.adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, self.csr_R, self.mask_u8, C, slope,
+        ops.adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, self.csr_R, self.mask_u8, stage.C, stage.slope,
                                   row_begin=p.n_interior, row_end=p.n_local, state_ms=st, part=2, **kw)
-        return out3.view(p.n_local, 3, ld)[:, :, :C], fused          # [n_local, 3, C]: base, target, target-hat
+        return stage.finish(out3)                                    # base, target, target-hat

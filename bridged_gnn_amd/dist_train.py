@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .dist import PartitionPlan
-from .ktgnn import _AggregateFn, _AggregateHeadsFn, _AggregateWideHeadsFn, _pad_cols4
+from .ktgnn import _AggregateFn, _pad_cols4
 
 
 class _Comm:
@@ -175,8 +175,8 @@ class PartitionedTrainer:
         m = self.model
         if not m.training:
             raise RuntimeError("PartitionedTrainer.forward is the TRAINING forward; use dist.PartitionedKTGNN for evaluation")
-        C = m.clf_base.out_channels
-        if m.clf_base.root_weight or m.clf_base.normalize:
+        stage = m._stage
+        if not stage.plain:
             raise NotImplementedError("partitioned training: classifier convs with root_weight / normalize off")
         nl = self.n_local
         h = None
@@ -199,34 +199,12 @@ class PartitionedTrainer:
             h = h.contiguous()
         # classifier stage (KTGNN.py:432-435): three convs share the graph, one exchange of 6 * pad4(C) floats per row (96 bytes
         # for C <= 4, 768 bytes at C = 31); C <= 4: the narrow three-head walk, C <= 32: the wide one, beyond: three per-conv walks
-        sums_h = self._global_sums(h)
-        l0, bn, _, l3 = m.clf_transformer
-        xt = l3(self._bn(l0(h), bn, True, 0.0)).contiguous()
-        sums_t = self._global_sums(xt)
-        tabs = [m.clf_base._transform_autograd(h, self.mask_u8, sums_h, self._mean_hook),
-                m.clf_target._transform_autograd(h, self.mask_u8, sums_h, self._mean_hook),
-                m.clf_target._transform_autograd(xt, self.mask_u8, sums_t, self._mean_hook)]
-        ld = tabs[0][0].shape[1]
-        both = torch.cat([t[0] for t in tabs] + [t[1] for t in tabs], dim=1)      # [n_local, 6 ld]: t2s x3 | s2t x3
+        tabs = stage.train_tables(h, self.mask_u8, self._global_sums(h), self._bn, self._global_sums, self._mean_hook)
+        ld = stage.ld
+        both = torch.cat(tabs[0::2] + tabs[1::2], dim=1)                          # [n_local, 6 ld]: t2s x3 | s2t x3
         ext = torch.cat((both, self._halo_of(both)))
-        pairs = []
-        for j in range(3):
-            pairs += [ext[:, j * ld:(j + 1) * ld], ext[:, (3 + j) * ld:(4 + j) * ld]]
-        cs = (m.clf_base, m.clf_target, m.clf_target)
-        a_t = torch.stack([c.a_f_t2s.weight.reshape(-1) for c in cs])
-        a_s = torch.stack([c.a_f_s2t.weight.reshape(-1) for c in cs])
-        if ops.heads_log_softmax_supported(3, C):
-            logp = _AggregateHeadsFn.apply(self.csr, self.mask_ext_u8, C, m.clf_base.negative_slope, a_t, a_s, *pairs)[:nl, :, :C]
-            return logp[:, 0], logp[:, 1], logp[:, 2]
-        if ops.wide_heads_supported(3, C):
-            logp = _AggregateWideHeadsFn.apply(self.csr, self.mask_ext_u8, C, m.clf_base.negative_slope, a_t, a_s,
-                                               *pairs)[:nl, :, :C]
-            return logp[:, 0], logp[:, 1], logp[:, 2]
-        outs = []
-        for j, c in enumerate(cs):
-            o = _AggregateFn.apply(pairs[2 * j], pairs[2 * j + 1], a_t[j], a_s[j], self.csr, self.mask_ext_u8, C, c.negative_slope)
-            outs.append(F.log_softmax(o[:nl, :C], dim=1))
-        return tuple(outs)
+        pairs = [ext[:, k * ld:(k + 1) * ld] for j in range(3) for k in (j, 3 + j)]
+        return stage.train_aggregate(stage.train_walk(), self.csr, self.mask_ext_u8, pairs, nl)
 
     # ---- loss / gradients ------------------------------------------------------------------------------------------------
     def reference_loss(self, out, y_local, train_mask_local):

@@ -25,7 +25,6 @@ from . import ops
 __all__ = ["Linear", "AdaptedConv", "KTGNN_no_complement"]
 
 
-
 def _plist(module):
     """the module's parameters as a cached list: `module.parameters()` walks the module tree (named_modules / _named_members) on every
     call -- 0.15 ms of host time per forward at ~60 calls.  Parameter OBJECTS are registered once (construction); moves and in-place
@@ -195,7 +194,7 @@ class _BnReluDropFn(torch.autograd.Function):
                                        seed_dev=_DROPOUT_STEP[0])
         if track:
             # the kernel wrote running_mean / running_var through raw pointers: their `_version` did not move, so the
-            # caches keyed by it (bn_eval_affine, KTGNN_no_complement._fold_transformer) would go stale with frozen affine
+            # caches keyed by it (bn_eval_affine, ClassifierStage.fold_transformer) would go stale with frozen affine
             # parameters -- bump the versions the way an in-place torch op would
             torch.autograd.graph.increment_version((bn.running_mean, bn.running_var))
             bn._bgnn_affine = None
@@ -680,6 +679,7 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
         self.edge_index1 = self.edge_index2 = self.edge_index = None
         self._csr = None
         self._arena = None
+        self._stage = classifier_stage.ClassifierStage(self)
 
     def reset_parameters(self):
         for conv in self.convs:
@@ -768,110 +768,11 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
         self._xsum_cache = (weakref.ref(x), x._version, weakref.ref(central_mask), central_mask._version, sums)
         return sums
 
-    def _fold_transformer(self):
-        """eval BatchNorm of clf_transformer folded into its first Linear (re-folded when a parameter / buffer changes)."""
-        l0, bn, _, l3 = self.clf_transformer
-        key = tuple((p.data_ptr(), p._version) for p in _plist(self.clf_transformer)) + \
-            (bn.running_mean._version, bn.running_var._version)
-        if getattr(self, "_tf_key", None) != key:
-            s = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach()
-            self._tf_w0 = (l0.weight.detach() * s[:, None]).float().contiguous()
-            self._tf_w0t = self._tf_w0.t().contiguous()
-            self._tf_b0 = (l0.bias.detach() * s + bn.bias.detach() - bn.running_mean * s).float().contiguous()
-            self._tf_key = key
-            self._tf_pack = None
-
-    def _transformer_hidden_eval(self, x, mask_u8=None, want_sums=False, sums_out=None):
-        """h1 = relu(BN(Linear0(x))) of clf_transformer (eval; BN folded: BN(Wx+b) = (s*W)x + (s*b + t)).  Inside the
-        envelope of `ops.linear` the W-stationary MFMA kernel applies bias + ReLU and, with `want_sums`, accumulates the
-        per-domain column sums of h1 in its epilogue; other shapes go through the library GEMM."""
-        self._fold_transformer()
-        sums = None
-        dout, din = self._tf_w0.shape
-        if x.dtype == torch.float32 and x.stride(1) == 1 and ops.linear_supported(din, dout):
-            if want_sums:
-                sums = sums_out if sums_out is not None else torch.zeros(2 * dout + 2, dtype=torch.float64, device=x.device)
-            h1 = ops.linear(x, self._tf_w0, self._tf_b0, relu=True, mask_u8=mask_u8 if want_sums else None, colsum=sums)
-        elif hasattr(torch, "_addmm_activation"):
-            h1 = torch._addmm_activation(self._tf_b0, x, self._tf_w0t, use_gelu=False)
-        else:
-            h1 = F.relu(torch.addmm(self._tf_b0, x, self._tf_w0t))
-        return (h1, sums) if want_sums else h1
-
-    def _transformer_to_target_tables(self, x, mask_u8, out, arena=None, all_reduce=None, sums_out=None):
-        """clf_target on clf_transformer(x) (:433) -> its narrow (h_t2s, h_s2t) tables in `out`.  Inside the envelope of
-        the fused pair the hidden activation h1 = relu(BN(Linear0(x))) never reaches HBM (stage A: raw per-row products +
-        domain sums of h1; `all_reduce` hook for partitioned graphs; stage B: bias + domain shift).  Otherwise h1 is
-        materialised by `_transformer_hidden_eval` and goes through the ordinary transform."""
-        self._fold_transformer()
-        dout, din = self._tf_w0.shape
-        pack = self._composed_target_pack(ops.pad4(dout))
-        n_s = 2 * ops.pad4(dout) + 2
-        if sums_out is None:
-            sums_out = arena.take(n_s) if arena is not None else torch.zeros(n_s, dtype=torch.float64, device=x.device)
-        if (x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[1] == din and ops.linear_narrow_supported(din, dout, pack)
-                and os.environ.get("BGNN_FUSED_TARGET", "1") != "0"):
-            raw = ops.linear_narrow_transform(x, self._tf_w0, self._tf_b0, mask_u8, sums_out, pack, relu=True)
-            sums1 = all_reduce(sums_out) if all_reduce is not None else sums_out
-            ops.narrow_transform_finish(raw, mask_u8, sums1, pack, out)
-            return
-        h1, sums1 = self._transformer_hidden_eval(x, mask_u8, want_sums=True, sums_out=sums_out)
-        h1p = _pad_cols4(h1)
-        if sums1 is None:
-            sums1 = ops.domain_sums(h1p, mask_u8)
-        if all_reduce is not None:
-            sums1 = all_reduce(sums1)
-        ops.adaptedconv_transform(h1p, mask_u8, None, self._composed_target_pack(h1p.shape[1]), out=[out], sums=sums1)
-
-    def _classifier_stage_fused(self, x, mask_u8, sums_h, views, arena, all_reduce=None):
-        """the three convs' narrow tables from ONE pass over x (bgnn_classifier_stage_f32): clf_base / clf_target on x and stage A of
-        clf_target on clf_transformer(x); stage B after the (optionally all-reduced) sums of the hidden activation.  -> False when the
-        shape is outside the kernel's envelope (the caller then takes the separate launches)."""
-        if sums_h is None or x.dtype != torch.float32 or x.stride(1) != 1:
-            return False
-        self._fold_transformer()
-        dout, din = self._tf_w0.shape
-        if x.shape[1] != din or dout != 128:
-            return False
-        pack_t = self._composed_target_pack(ops.pad4(dout))
-        pair = self.clf_base.packed(x.shape[1], self.clf_target)
-        if not ops.classifier_stage_supported(x, pair, self._tf_w0, pack_t):
-            return False
-        n_s = 2 * ops.pad4(dout) + 2
-        sums_out = arena.take(n_s) if arena is not None else torch.zeros(n_s, dtype=torch.float64, device=x.device)
-        raw = ops.classifier_stage(x, mask_u8, sums_h, pair, [views[0], views[1]], self._tf_w0, self._tf_b0, sums_out, pack_t, relu=True)
-        sums1 = all_reduce(sums_out) if all_reduce is not None else sums_out
-        ops.narrow_transform_finish(raw, mask_u8, sums1, pack_t, views[2])
-        return True
+    def _transformer_to_target_tables(self, x, mask_u8, out, arena=None, sums_out=None):
+        return self._stage.target_tables(x, mask_u8, out, arena, sums_out)
 
     def _composed_target_pack(self, din_pad):
-        """clf_target evaluated on x' = h1.W3^T + b3 without materialising x' (the last Linear of clf_transformer is
-        affine): W x' + b = (W W3) h1 + (W b3 + b); [x' || d'].g = h1.(W3^T g_x) + b3.g_x + d.(W3^T g_d) with d the
-        domain-mean difference of h1 (d' = W3 d).  Packed once per weight version."""
-        c, l3 = self.clf_target, self.clf_transformer[3]
-        key = (din_pad, c._versions(), l3.weight._version, l3.bias._version, l3.weight.data_ptr())
-        if getattr(self, "_tf_pack", None) is None or self._tf_pack[0] != key:
-            W3, b3 = l3.weight.detach(), l3.bias.detach()
-            hd = c.head()
-            din = W3.shape[0]
-
-            def comp_gate(g):
-                g = g.reshape(-1)
-                return torch.cat((W3.t() @ g[:din], W3.t() @ g[din:])), float((b3 * g[:din]).sum().item())
-            g1, c1 = comp_gate(hd["g_s2t"])
-            g2, c2 = comp_gate(hd["g_t2s"])
-            head = {"W_s": hd["W_s"] @ W3, "W_t": hd["W_t"] @ W3,
-                    "b_s": hd["W_s"] @ b3 + (hd["b_s"] if hd["b_s"] is not None else 0),
-                    "b_t": hd["W_t"] @ b3 + (hd["b_t"] if hd["b_t"] is not None else 0),
-                    "g_s2t": g1, "g_t2s": g2, "gate_const": (c1, c2)}
-            self._tf_pack = (key, ops.pack_transform_heads([head], din_pad))
-        return self._tf_pack[1]
-
-    def _transformer_eval(self, x):
-        """clf_transformer in eval mode (BatchNorm folded into the first Linear -- exact algebra:
-        BN(Wx+b) = (s*W)x + (s*b + t))."""
-        l3 = self.clf_transformer[3]
-        return F.linear(self._transformer_hidden_eval(x), l3.weight, l3.bias)
+        return self._stage.composed_target_pack(din_pad)
 
     def forward(self, data):
         x, central_mask = data.x, data.central_mask
@@ -879,84 +780,38 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
         x, sums_h = self._hidden(x, csr, central_mask, want_sums=True)
         x = x.contiguous()
         mask_u8 = _as_u8(central_mask).contiguous()
-        C = self.clf_base.out_channels
-        if (self.training and torch.is_grad_enabled() and not (self.clf_base.root_weight or self.clf_base.normalize)
-                and ops.heads_log_softmax_supported(3, C) and x.dtype == torch.float32
-                and os.environ.get("BGNN_FUSED_TRAIN_HEADS", "1") != "0"):
+        stage = self._stage                                    # classifier_stage.py: head order, table layout, shared routines
+        train = self.training and torch.is_grad_enabled()
+        walk = stage.train_walk(opt_in=True) if (train and stage.plain and x.dtype == torch.float32) else None
+        if walk is not None:
             # training step (main_graph_knowledge_transfer.py:39-68): the three classifier convs share the graph -> one CSR
             # walk forward and one per backward pass for all three; h's domain sums are formed once for both convs on h
             sums_x = ops.domain_sums(_pad_cols4(x.detach()), mask_u8)
-            l0, bn, _, l3 = self.clf_transformer
-            xt = l3(bn_relu_dropout_train(l0(x), bn, True, 0.0)).contiguous()
-            if _TransformPairFn.supported(x, self.clf_base, self.clf_target):
-                prm = [t for c in (self.clf_base, self.clf_target)
-                       for t in (c.lin_s.weight, c.lin_s.bias, c.lin_t.weight, c.lin_t.bias, c.a_g_s2t.weight, c.a_g_t2s.weight)]
-                tabs_x = _TransformPairFn.apply(x, mask_u8, self.clf_base, self.clf_target, sums_x, *prm)
-            else:
-                tabs_x = (*self.clf_base._transform_autograd(x, mask_u8, sums_x), *self.clf_target._transform_autograd(x, mask_u8, sums_x))
-            tabs = (*tabs_x, *self.clf_target._transform_autograd(xt, mask_u8))
-            cs = (self.clf_base, self.clf_target, self.clf_target)
-            a_t = torch.stack([c.a_f_t2s.weight.reshape(-1) for c in cs])
-            a_s = torch.stack([c.a_f_s2t.weight.reshape(-1) for c in cs])
-            logp = _AggregateHeadsFn.apply(csr, mask_u8, C, self.clf_base.negative_slope, a_t, a_s, *tabs)[:, :, :C]
-            return logp[:, 0], logp[:, 1], logp[:, 2], None                                             # :432,:434,:433
-        if (self.training and torch.is_grad_enabled() and not (self.clf_base.root_weight or self.clf_base.normalize)
-                and ops.wide_heads_supported(3, C) and x.dtype == torch.float32
-                and os.environ.get("BGNN_WIDE_TRAIN_HEADS", "0") == "1"):
-            # opt-in: the same stage for 4 < C <= 32 (office, 31 classes) through the wide three-head walk
-            sums_x = ops.domain_sums(_pad_cols4(x.detach()), mask_u8)
-            l0, bn, _, l3 = self.clf_transformer
-            xt = l3(bn_relu_dropout_train(l0(x), bn, True, 0.0)).contiguous()
-            tabs = (*self.clf_base._transform_autograd(x, mask_u8, sums_x), *self.clf_target._transform_autograd(x, mask_u8, sums_x),
-                    *self.clf_target._transform_autograd(xt, mask_u8))
-            cs = (self.clf_base, self.clf_target, self.clf_target)
-            a_t = torch.stack([c.a_f_t2s.weight.reshape(-1) for c in cs])
-            a_s = torch.stack([c.a_f_s2t.weight.reshape(-1) for c in cs])
-            logp = _AggregateWideHeadsFn.apply(csr, mask_u8, C, self.clf_base.negative_slope, a_t, a_s, *tabs)[:, :, :C]
-            return logp[:, 0], logp[:, 1], logp[:, 2], None                                             # :432,:434,:433
-        if self.clf_base.root_weight or self.clf_base.normalize or torch.is_grad_enabled() or self.training:
+            tabs = stage.train_tables(x, mask_u8, sums_x, bn_relu_dropout_train)
+            return (*stage.train_aggregate(walk, csr, mask_u8, tabs), None)                              # :432,:434,:433
+        if not stage.plain or torch.is_grad_enabled() or self.training:
             logits_base = self.clf_base(x, None, central_mask=central_mask, csr=csr)                      # :432
             logits_target = self.clf_target(x, None, central_mask=central_mask, csr=csr)                  # :434
             # the folded / raw-kernel eval form has no autograd: with grad enabled (fine-tuning with frozen BN, input
             # attribution) the module itself runs -- eval-mode BatchNorm is autograd-safe
             needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in _plist(self.clf_transformer)))
-            if self.training and torch.is_grad_enabled():
+            if train:
                 l0, bn, _, l3 = self.clf_transformer
                 xt = l3(bn_relu_dropout_train(l0(x), bn, True, 0.0))
             else:
-                xt = self.clf_transformer(x) if (self.training or needs_grad) else self._transformer_eval(x)
+                xt = self.clf_transformer(x) if (self.training or needs_grad) else stage.transformer_eval(x)
             logits_hat = self.clf_target(xt.contiguous(), None, central_mask=central_mask, csr=csr)       # :433
-        else:
-            # the three classifier convs share the graph: their six narrow tables are interleaved per node
-            # ([N, 3*pad4(C)]), clf_base/clf_target(x) come from ONE pass over x, and ONE aggregation launch walks the
-            # CSR for all three heads (in-neighbour ids and 48-B rows read once)
-            C = self.clf_base.out_channels
-            ld = ops.pad4(C)
-            N = x.shape[0]
-            t2s = torch.empty(N, 3 * ld, dtype=torch.float32, device=x.device)
-            s2t = torch.empty(N, 3 * ld, dtype=torch.float32, device=x.device)
-            views = [(t2s[:, j * ld:(j + 1) * ld], s2t[:, j * ld:(j + 1) * ld]) for j in range(3)]
-            arena = self._arena
-            if not self._classifier_stage_fused(x, mask_u8, sums_h, views, arena):
-                self.clf_base.transform(x, mask_u8, sums=sums_h, partner=self.clf_target, out=[views[0], views[1]])
-                # clf_target(T(x)) (:433): T's last Linear is folded into the conv's packed weights, so only
-                # h1 = relu(BN(Linear0(x))) is materialised
-                self._transformer_to_target_tables(x, mask_u8, views[2], arena)
-            akey = (self.clf_base._versions(), self.clf_target._versions())
-            if getattr(self, "_a3_key", None) != akey:           # stacked attention vectors, re-packed when a weight changes
-                cs = (self.clf_base, self.clf_target, self.clf_target)
-                self._a3 = (torch.stack([c.a_f_t2s.weight.detach().reshape(-1) for c in cs]).contiguous(),
-                            torch.stack([c.a_f_s2t.weight.detach().reshape(-1) for c in cs]).contiguous())
-                self._a3_key = akey
-            fused = ops.heads_log_softmax_supported(3, C)          # :435 inside the aggregation's epilogue
-            out3 = ops.adaptedconv_aggregate(t2s, s2t, self._a3[0], self._a3[1], csr, mask_u8, C,
-                                             self.clf_base.negative_slope, heads=3, log_softmax=fused)
-            logp = out3.view(N, 3, ld)[:, :, :C]
-            if not fused:
-                logp = F.log_softmax(logp, dim=2)                                                       # one launch for :435
-            return logp[:, 0], logp[:, 1], logp[:, 2], None                                             # :432,:434,:433
-        return (F.log_softmax(logits_base, dim=1), F.log_softmax(logits_target, dim=1),
-                F.log_softmax(logits_hat, dim=1), None)                                                  # :435
+            return (F.log_softmax(logits_base, dim=1), F.log_softmax(logits_target, dim=1),
+                    F.log_softmax(logits_hat, dim=1), None)                                              # :435
+        # the six narrow tables interleaved per node ([N, 3*pad4(C)]), clf_base/clf_target(x) from ONE pass over x, and ONE
+        # aggregation launch that walks the CSR for all three heads (in-neighbour ids and 48-B rows read once)
+        t2s = torch.empty(x.shape[0], 3 * stage.ld, dtype=torch.float32, device=x.device)
+        s2t = torch.empty_like(t2s)
+        stage.eval_tables(x, mask_u8, sums_h, stage.views(t2s, s2t), self._arena)
+        a_t2s, a_s2t = stage.attention()
+        out3 = ops.adaptedconv_aggregate(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, stage.C, stage.slope, heads=3,
+                                         log_softmax=stage.fused_log_softmax)
+        return (*stage.finish(out3), None)                                                               # :432,:434,:433
 
     def graphed(self, data, warmup=2):
         """Capture the eval forward on `data` into a HIP graph and return a zero-argument callable that replays it
@@ -986,9 +841,7 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
         which a replayed HIP graph does not advance)"""
         for c in list(self.convs) + [self.clf_base, self.clf_target]:
             c._pack_key = None
-        self._tf_key = None
-        self._tf_pack = None
-        self._a3_key = None
+        self._stage.drop_caches()
         for bn in list(self.bns) + [self.clf_transformer[1]]:      # eval-mode scale / shift (bn_eval_affine)
             bn._bgnn_affine = None
         _forget_plists(self)
@@ -1053,3 +906,6 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
     def get_emb(self, data):
         """KTGNN.py:436-465."""
         return self._hidden(data.x, self._prepare(data), data.central_mask)
+
+
+from . import classifier_stage  # noqa: E402  (it builds on the autograd functions defined above)
