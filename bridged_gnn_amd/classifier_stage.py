@@ -97,7 +97,9 @@ class ClassifierStage:
     def composed_target_pack(self, din_pad):
         """clf_target evaluated on x' = h1.W3^T + b3 without materialising x' (the last Linear of clf_transformer is
         affine): W x' + b = (W W3) h1 + (W b3 + b); [x' || d'].g = h1.(W3^T g_x) + b3.g_x + d.(W3^T g_d) with d the
-        domain-mean difference of h1 (d' = W3 d).  Packed once per weight version."""
+        domain-mean difference of h1 (d' = W3 d).  Packed once per weight version.  The gate constants b3.g_x stay 0-dim device
+        tensors (`pack_transform_heads` copies them into its fp32 table: the same value as through a Python float), so a re-pack
+        after a weight update does not wait for the device."""
         c, l3 = self.convs[1], self.model.clf_transformer[3]
         key = (din_pad, c._versions(), l3.weight._version, l3.bias._version, l3.weight.data_ptr())
         if self._tf_pack is None or self._tf_pack[0] != key:
@@ -107,7 +109,7 @@ class ClassifierStage:
 
             def comp_gate(g):
                 g = g.reshape(-1)
-                return torch.cat((W3.t() @ g[:din], W3.t() @ g[din:])), float((b3 * g[:din]).sum().item())
+                return torch.cat((W3.t() @ g[:din], W3.t() @ g[din:])), (b3 * g[:din]).sum()
             g1, c1 = comp_gate(hd["g_s2t"])
             g2, c2 = comp_gate(hd["g_t2s"])
             head = {"W_s": hd["W_s"] @ W3, "W_t": hd["W_t"] @ W3,

@@ -1076,3 +1076,147 @@ def pair_cos_count(A, B, rows1, rows2, lab1, lab2):
                                          L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
     L.check(rc, "bgnn_pair_cos_count_f32")
     return counts
+
+
+# ---- step 2's loss and metric passes (bgnn.h: bgnn_step2_*, csrc/bgnn_step2.hip) -------------------------------------------------
+STEP2_TERMS = ("total", "nll_s", "nll_t", "nll_t_hat", "kl", "n_train", "n_target")     # layout of the loss pass's fp64 [8] output
+
+
+def _s2_table(T, N=None, C=None):
+    assert T.dtype == torch.float32 and T.dim() == 2 and T.stride(1) == 1 and T.stride(0) >= T.shape[1], \
+        "step-2 tables are fp32 [N, C] with unit column stride"
+    assert (N is None or T.shape[0] == N) and (C is None or T.shape[1] == C), "step-2 tables must have one shape"
+    return L.ptr_rows(T), T.stride(0)
+
+
+def _s2_rows(y, *masks):
+    N = int(y.shape[0])
+    assert y.dtype == torch.int64 and y.dim() == 1 and y.is_contiguous()
+    for m in masks:
+        assert m.dtype == torch.uint8 and m.shape == (N,) and m.is_contiguous(), "step-2 masks are contiguous uint8 [N]"
+    return N
+
+
+def _s2_ws(N, C, dev):
+    return torch.empty(int(L.lib().bgnn_step2_loss_workspace_bytes(N, C)), dtype=torch.uint8, device=dev)
+
+
+def as_u8(mask):
+    """bool / uint8 mask -> contiguous uint8 (a reinterpreting view for bool: no copy, no launch)"""
+    return (mask.view(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+
+
+class _Step2LossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp_s, lp_t, lp_h, y, train_u8, central_u8, Lambda):
+        N = _s2_rows(y, train_u8, central_u8)
+        C = int(lp_s.shape[1])
+        if N < 1 or C < 1:
+            raise ValueError("step2_loss: empty table")
+        dev = lp_s.device
+        terms = torch.empty(8, dtype=torch.float64, device=dev)
+        ws = _s2_ws(N, C, dev)
+        rc = L.lib().bgnn_step2_loss_f32(*_s2_table(lp_s, N, C), *_s2_table(lp_t, N, C), *_s2_table(lp_h, N, C), N, C, L.ptr(y),
+                                         L.ptr(train_u8), L.ptr(central_u8), float(Lambda), L.ptr(terms), L.ptr(ws), ws.numel(),
+                                         L.stream())
+        L.check(rc, "bgnn_step2_loss_f32")
+        ctx.save_for_backward(lp_t, lp_h, y, train_u8, central_u8, terms)
+        ctx.Lambda = float(Lambda)
+        ctx.mark_non_differentiable(terms)
+        return terms[0].float(), terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        lp_t, lp_h, y, train_u8, central_u8, terms = ctx.saved_tensors
+        N, C = lp_t.shape
+        gs, gt, gh = (torch.empty(N, C, dtype=torch.float32, device=lp_t.device) for _ in range(3))
+        g = g.reshape(1).float().contiguous()
+        rc = L.lib().bgnn_step2_loss_bwd_f32(*_s2_table(lp_t), *_s2_table(lp_h), N, C, L.ptr(y), L.ptr(train_u8), L.ptr(central_u8),
+                                             ctx.Lambda, L.ptr(terms), L.ptr(g), L.ptr(gs), L.ptr(gt), L.ptr(gh), C, L.stream())
+        L.check(rc, "bgnn_step2_loss_bwd_f32")
+        return gs, gt, gh, None, None, None, None
+
+
+def step2_loss(lp_s, lp_t, lp_t_hat, y, train_mask, central_mask, Lambda=1.0, return_terms=False):
+    """Step 2's training loss (main_graph_knowledge_transfer.py:44-54) in one HIP pass forward and one backward:
+        (2 nll(lp_s | train) + nll(lp_t | train & ~central) + nll(lp_t_hat | train & ~central)) / 4 + Lambda KL_batchmean(lp_t_hat || lp_t)
+    -> 0-dim fp32 loss (differentiable w.r.t. the three tables).  With `return_terms` also the pass's fp64 [8] vector, laid out as
+    STEP2_TERMS (total, the three NLL means, the KL term without Lambda, the two row counts).  Masks: bool or uint8 [N].  No host
+    synchronisation, no boolean indexing, fixed-order fp64 sums (two calls are bitwise equal), no memset node: usable as the
+    `loss_fn` of `graphed_train_step`.  An empty selection gives NaN for its mean, like F.nll_loss."""
+    loss, terms = _Step2LossFn.apply(lp_s, lp_t, lp_t_hat, y.contiguous(), as_u8(train_mask), as_u8(central_mask), Lambda)
+    return (loss, terms) if return_terms else loss
+
+
+class _Step2NllFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, y, mask_u8):
+        N = _s2_rows(y, mask_u8)
+        C = int(lp.shape[1])
+        if N < 1 or C < 1:
+            raise ValueError("step2_nll: empty table")
+        terms = torch.empty(2, dtype=torch.float64, device=lp.device)
+        ws = _s2_ws(N, C, lp.device)
+        rc = L.lib().bgnn_step2_nll_f32(*_s2_table(lp, N, C), N, C, L.ptr(y), L.ptr(mask_u8), L.ptr(terms), L.ptr(ws), ws.numel(), L.stream())
+        L.check(rc, "bgnn_step2_nll_f32")
+        ctx.save_for_backward(y, mask_u8, terms)
+        ctx.shape = (N, C)
+        ctx.mark_non_differentiable(terms)
+        return terms[0].float(), terms
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        y, mask_u8, terms = ctx.saved_tensors
+        N, C = ctx.shape
+        out = torch.empty(N, C, dtype=torch.float32, device=y.device)
+        g = g.reshape(1).float().contiguous()
+        rc = L.lib().bgnn_step2_nll_bwd_f32(N, C, L.ptr(y), L.ptr(mask_u8), L.ptr(terms), L.ptr(g), L.ptr(out), C, L.stream())
+        L.check(rc, "bgnn_step2_nll_bwd_f32")
+        return out, None, None
+
+
+def step2_nll(lp, y, mask, return_terms=False):
+    """F.nll_loss(lp[mask], y[mask]) (train_noDTC, main_graph_knowledge_transfer.py:269) without compacting rows -> 0-dim fp32 loss;
+    `return_terms`: also fp64 [2] = (mean, row count)."""
+    loss, terms = _Step2NllFn.apply(lp, y.contiguous(), as_u8(mask))
+    return (loss, terms) if return_terms else loss
+
+
+def step2_counts(tables, y, sel_u8, combos, out=None):
+    """Confusion counts of per-row argmax predictions: tables = up to three [N, C] log-prob tables (None for unused slots), sel_u8
+    uint8 [N] with bit b = row is in selection b, combos = [(table index, selection bit), ...] (at most 8)
+    -> int64 [len(combos), C, C], counts[k, true, predicted].  Ties go to the lowest index."""
+    tables = list(tables) + [None] * (3 - len(tables))
+    first = next(t for t in tables if t is not None)
+    N, C = int(first.shape[0]), int(first.shape[1])
+    assert _s2_rows(y, sel_u8) == N and 1 <= len(combos) <= 8
+    code = 0
+    for k, (tb, bit) in enumerate(combos):
+        assert 0 <= tb <= 2 and tables[tb] is not None and 0 <= bit <= 7
+        code |= (tb | (bit << 2)) << (8 * k)
+    if out is None:
+        out = torch.empty(len(combos), C, C, dtype=torch.int64, device=first.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == len(combos) * C * C
+    args = []
+    for t in tables:
+        args += list(_s2_table(t, N, C)) if t is not None else [None, 0]
+    rc = L.lib().bgnn_step2_counts_f32(*args, N, C, L.ptr(y), L.ptr(sel_u8), code, len(combos), L.ptr(out), L.stream())
+    L.check(rc, "bgnn_step2_counts_f32")
+    return out
+
+
+def step2_auc(score, y, sel):
+    """roc_auc_score(y[sel], score[sel]) for binary labels as a 0-dim fp64 DEVICE tensor (NaN when one class is absent): the
+    tie-aware rank statistic, a tied positive / negative pair counting 1/2.  The per-node arrays stay on the device: torch sorts the
+    negatives' scores, one HIP pass counts, for every positive row, the negatives below it and level with it (integers)."""
+    N = int(score.shape[0])
+    assert score.dtype == torch.float32 and score.dim() == 1 and y.shape == (N,) and sel.shape == (N,)
+    score = score.contiguous()
+    sel = sel.bool()
+    neg, pos = sel & (y == 0), sel & (y == 1)
+    keys = torch.where(neg, score, torch.full_like(score, float("inf"))).sort().values
+    n_neg = neg.sum().reshape(1)
+    out = torch.empty(2, dtype=torch.int64, device=score.device)
+    rc = L.lib().bgnn_step2_auc_count_f32(L.ptr(score), L.ptr(as_u8(pos)), N, L.ptr(keys), L.ptr(n_neg), L.ptr(out), L.stream())
+    L.check(rc, "bgnn_step2_auc_count_f32")
+    return out[0].double() / (2.0 * out[1].double() * n_neg[0].double())

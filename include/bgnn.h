@@ -31,7 +31,8 @@ extern "C" {
  * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113.  The
  * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32, and for the
  * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size, and for the cosine
- * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes. */
+ * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
+ * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -570,6 +571,42 @@ int bgnn_pair_cos_segsum_f32(const float* other, int64_t ld_other, int64_t n_oth
 int bgnn_pair_cos_count_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* rows1,
                             int64_t m1, const int64_t* rows2, int64_t m2, const int64_t* lab1, const int64_t* lab2, long long* counts,
                             void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Step 2's loss and metric counts                              main_graph_knowledge_transfer.py:39-142, :265-300
+ * for bridged_gnn_amd/transfer.py.  Tables are fp32 log-probabilities [N, C] with a row stride (ld >= C, unit column stride, no
+ * alignment requirement, any C >= 1); y int64 [N]; masks uint8 [N] (0 / 1).  A label outside [0, C) on a selected row selects
+ * nothing (the driver refuses such graphs at set-up).  No host synchronisation, no row compaction; scratch and outputs are cleared
+ * by kernels, never by a memset node, so every entry may be captured into a HIP graph.
+ * loss:      replaces :44-54.  terms [8] fp64 = total, nll(lp_s | train), nll(lp_t | train & ~central), nll(lp_t^ | train & ~central),
+ *            KL_batchmean(lp_t^ || lp_t) = sum exp(lp_t)(lp_t - lp_t^) / N, #train, #train & ~central, 0;
+ *            total = (2 nll_s + nll_t + nll_t^) / 4 + lambda KL.  An empty selection makes its mean NaN (0 / 0), as F.nll_loss
+ *            does.  fp64 sums in a fixed order without atomics: two calls are bitwise equal.  ws: bgnn_step2_loss_workspace_bytes.
+ * loss_bwd:  replaces loss.backward() for :54: writes every element of the three gradient tables g_s, g_t, g_h [N, C] (row stride
+ *            ld_g), scaled by grad_out[0] (device fp32 scalar); `terms` is the forward's output (the row counts are read from it).
+ * nll:       replaces :269 (train_noDTC): terms [2] fp64 = nll(lp | mask), #mask.   nll_bwd: its gradient table.
+ * counts:    replaces what :82-105, :125-131 and :285-295 hand to sklearn.  One pass over the rows: per-row argmax of each table
+ *            that is needed (ties -> the lowest index), then counts [K, C, C] int64, counts[k][true][predicted], for K <= 8
+ *            combinations; byte k of `combos` = table index 0..2 | selection bit 0..7 << 2; sel uint8 [N]: bit b set = the row
+ *            is in selection b.  Tables that no combination names may be NULL.
+ * auc_count: the rank statistic of roc_auc_score(y, score): out [2] int64 = sum over the rows with pos[r] of
+ *            2 #{negatives with a smaller score} + #{negatives with an equal score}, and #positive rows; neg_sorted [>= *n_neg] are
+ *            the negatives' scores in ascending order, n_neg a device int64.  AUC = out[0] / (2 out[1] *n_neg).            */
+size_t bgnn_step2_loss_workspace_bytes(int64_t N, int32_t C);
+int bgnn_step2_loss_f32(const float* lp_s, int64_t ld_s, const float* lp_t, int64_t ld_t, const float* lp_h, int64_t ld_h, int64_t N,
+                        int32_t C, const int64_t* y, const uint8_t* train_mask, const uint8_t* central_mask, double lambda,
+                        double* terms, void* ws, size_t ws_bytes, void* stream);
+int bgnn_step2_loss_bwd_f32(const float* lp_t, int64_t ld_t, const float* lp_h, int64_t ld_h, int64_t N, int32_t C, const int64_t* y,
+                            const uint8_t* train_mask, const uint8_t* central_mask, double lambda, const double* terms,
+                            const float* grad_out, float* g_s, float* g_t, float* g_h, int64_t ld_g, void* stream);
+int bgnn_step2_nll_f32(const float* lp, int64_t ld, int64_t N, int32_t C, const int64_t* y, const uint8_t* mask, double* terms, void* ws,
+                       size_t ws_bytes, void* stream);
+int bgnn_step2_nll_bwd_f32(int64_t N, int32_t C, const int64_t* y, const uint8_t* mask, const double* terms, const float* grad_out,
+                           float* g, int64_t ld_g, void* stream);
+int bgnn_step2_counts_f32(const float* t0, int64_t ld0, const float* t1, int64_t ld1, const float* t2, int64_t ld2, int64_t N, int32_t C,
+                          const int64_t* y, const uint8_t* sel, uint64_t combos, int32_t K, long long* counts, void* stream);
+int bgnn_step2_auc_count_f32(const float* score, const uint8_t* pos, int64_t N, const float* neg_sorted, const int64_t* n_neg,
+                             long long* out, void* stream);
 
 #ifdef __cplusplus
 }
