@@ -174,6 +174,38 @@ def _pad_cols4(t):
 _DROPOUT_STEP = [None]
 
 
+class DropoutSeedFeed:
+    """What `_DROPOUT_STEP[0]` holds while a whole EPOCH is captured (`transfer.train_gnn(graphed=True)`): `words`, an int64 device
+    tensor with one word per dropout layer of the model, in forward order.  Each dropout layer takes the next word as its
+    `seed_dev` and bakes the host seed 0 into the graph, so the mask of a replay is decided by what the graph loads into the words
+    (the seeds an eager run would have drawn from the host generator: `optim.draw_dropout_seeds`); nothing is drawn on the host."""
+
+    def __init__(self, words):
+        assert words.dtype == torch.int64 and words.dim() == 1 and words.is_contiguous()
+        self.words, self.taken = words, 0
+
+    def rewind(self):
+        self.taken = 0
+
+    def take(self):
+        if self.taken >= self.words.numel():
+            raise RuntimeError(f"the model has more dropout layers than the {self.words.numel()} seed words prepared for the captured epoch")
+        w = self.words[self.taken:self.taken + 1]
+        self.taken += 1
+        return w
+
+
+def dropout_seed(p_drop, step_word=True):
+    """-> (seed baked on the host, device word added to it | None) of one dropout layer: eager -- a draw from the host generator (no
+    sync) and None; inside `graphed_train_step` -- a draw and its step counter (`step_word`: layers that take one); with a
+    `DropoutSeedFeed` -- 0 and the layer's word of the feed."""
+    src = _DROPOUT_STEP[0]
+    if isinstance(src, DropoutSeedFeed):
+        return 0, (src.take() if p_drop > 0 else None)
+    seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p_drop > 0 else 0   # host generator: no sync
+    return seed, (src if step_word else None)
+
+
 class _BnReluDropFn(torch.autograd.Function):
     """Training-mode `BatchNorm1d` -> `F.relu` -> `F.dropout` (KTGNN.py:420-430; clf_transformer's BN + ReLU with p = 0) as
     two streaming HIP launches forward and two backward (torch: eight launches and three saved [N, D] intermediates).
@@ -181,7 +213,7 @@ class _BnReluDropFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn, relu, p_drop):
-        seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p_drop > 0 else 0   # host generator: no sync
+        seed, seed_dev = dropout_seed(p_drop)
         track = bn.track_running_stats and bn.running_mean is not None
         mom = 0.0
         if track:
@@ -191,7 +223,7 @@ class _BnReluDropFn(torch.autograd.Function):
         y, stats = ops.bn_relu_dropout(x, weight.detach() if weight is not None else None,
                                        bias.detach() if bias is not None else None, bn.eps, relu, p_drop, seed, mom,
                                        bn.running_mean if track else None, bn.running_var if track else None,
-                                       seed_dev=_DROPOUT_STEP[0])
+                                       seed_dev=seed_dev)
         if track:
             # the kernel wrote running_mean / running_var through raw pointers: their `_version` did not move, so the
             # caches keyed by it (bn_eval_affine, ClassifierStage.fold_transformer) would go stale with frozen affine
@@ -200,7 +232,7 @@ class _BnReluDropFn(torch.autograd.Function):
             bn._bgnn_affine = None
         ctx.save_for_backward(x, weight, bias, stats)
         ctx.cfg = (bn.eps, relu, p_drop, seed)
-        ctx.seed_dev = _DROPOUT_STEP[0]
+        ctx.seed_dev = seed_dev
         return y
 
     @staticmethod

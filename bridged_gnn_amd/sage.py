@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .ktgnn import Linear
+from .ktgnn import Linear, dropout_seed
 
 __all__ = ["SAGEConv", "GraphSAGE", "SageGraph"]
 
@@ -58,13 +58,13 @@ def _pack(w_l, b_l, w_r):
     return wcat, bcat
 
 
-def _layer_forward(x, wcat, bcat, D, view, epilogue, p_drop, seed):
+def _layer_forward(x, wcat, bcat, D, view, epilogue, p_drop, seed, seed_dev=None):
     N = x.shape[0]
     Dp = ops.pad4(D)
     T = _transform(x, wcat, bcat)
     rowptr, col = view[0], view[1]
     return ops.sage_mean_aggregate(T[:, :Dp], rowptr, col, N, D, root=T[:, Dp:], mean=True, epilogue=epilogue,
-                                   p_drop=p_drop, seed=seed)
+                                   p_drop=p_drop, seed=seed, seed_dev=seed_dev)
 
 
 class _SageLayerFn(torch.autograd.Function):
@@ -72,10 +72,10 @@ class _SageLayerFn(torch.autograd.Function):
     dW = dT^T x, db_l = column sums of dT_r, dx = dT [W_l ; W_r])."""
 
     @staticmethod
-    def forward(ctx, x, w_l, b_l, w_r, view, epilogue, p_drop, seed):
+    def forward(ctx, x, w_l, b_l, w_r, view, epilogue, p_drop, seed, seed_dev=None):
         D = w_l.shape[0]
         wcat, bcat = _pack(w_l.detach(), b_l.detach() if b_l is not None else None, w_r.detach() if w_r is not None else None)
-        y = _layer_forward(x.detach(), wcat, bcat, D, view, epilogue, p_drop, seed)
+        y = _layer_forward(x.detach(), wcat, bcat, D, view, epilogue, p_drop, seed, seed_dev)
         ctx.save_for_backward(x, wcat)
         ctx.y, ctx.view, ctx.cfg = y, view, (D, epilogue, p_drop, b_l is not None, w_r is not None)
         return y[:, :D]
@@ -108,7 +108,7 @@ class _SageLayerFn(torch.autograd.Function):
                 gx = ops.linear(dT, wcat.t().contiguous(), torch.zeros(din, dtype=torch.float32, device=x.device))
             else:
                 gx = dT.mm(wcat)
-        return gx, gw_l, gb_l, gw_r, None, None, None, None
+        return gx, gw_l, gb_l, gw_r, None, None, None, None, None
 
 
 class SAGEConv(nn.Module):
@@ -142,14 +142,14 @@ class SAGEConv(nn.Module):
         torch_epi = self.normalize or (epilogue == "log_softmax" and D > 128)
         kern_epi = None if torch_epi else epilogue
         kern_p = p_drop if kern_epi == "relu" else 0.0
-        seed = int(torch.empty((), dtype=torch.int64).random_().item()) if kern_p > 0 else 0   # host generator: no sync
+        seed, seed_dev = dropout_seed(kern_p, step_word=False)       # a captured epoch: 0 and this layer's device word
         view = graph.view(out_neighbours)
         x = x.float()
         if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in (w_l, b_l, w_r))):
-            out = _SageLayerFn.apply(x, w_l, b_l, w_r, view, kern_epi, float(kern_p), seed)
+            out = _SageLayerFn.apply(x, w_l, b_l, w_r, view, kern_epi, float(kern_p), seed, seed_dev)
         else:
             wcat, bcat = _pack(w_l.detach(), b_l.detach() if b_l is not None else None, w_r.detach() if w_r is not None else None)
-            out = _layer_forward(x, wcat, bcat, D, view, kern_epi, float(kern_p), seed)[:, :D]
+            out = _layer_forward(x, wcat, bcat, D, view, kern_epi, float(kern_p), seed, seed_dev)[:, :D]
         if torch_epi:
             if self.normalize:
                 out = F.normalize(out, p=2.0, dim=-1)

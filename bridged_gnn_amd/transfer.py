@@ -15,8 +15,9 @@ What runs differently underneath:
     comparison (`loss_target < best`, on fp32 values).
 
 Additive keyword arguments (defaults keep the reference's behaviour): `dropout=0.5` (the reference fixes it at :179),
-`verbose=True`, `ckpt_dir='../ckpt'`, `history=None` (a dict that receives the per-epoch scores and the best epoch), and `--gpu`
-now selects the device (the reference parses it and then hard-codes cuda:1, :36).
+`verbose=True`, `ckpt_dir='../ckpt'`, `history=None` (a dict that receives the per-epoch scores and the best epoch), `graphed=False`
+(`--graphed`: every epoch is one replay of a captured HIP graph, see `_GraphedEpoch`; the run is the eager run), and `--gpu` now
+selects the device (the reference parses it and then hard-codes cuda:1, :36).
 
 Deviations from the reference, all on paths the reference cannot complete:
   * `train` / `train_gnn` with `gnn != 'KTGNN'` raise NotImplementedError (in the reference those branches die on an undefined
@@ -325,6 +326,109 @@ class _History:
         return [(terms[i], counts[i], auc[i]) for i in range(n)]
 
 
+_AUC_GRAPHED_MAX_ROWS = 1 << 15
+
+
+class _GraphedEpoch:
+    """One epoch of `train_gnn` / `train_gnn_noDTC` -- zero-grad, train forward, loss, backward, Adam, eval forward, counts (and AUCs),
+    the epoch's `_History` row -- captured into ONE HIP graph on one stream; `replay()` is one submission and waits for nothing.
+    What makes the replayed run the eager run:
+      * warm-up and capture leave no trace: parameters, BatchNorm buffers (`num_batches_tracked` included), optimizer state and both
+        generators are put back afterwards, so epoch 1 starts from the state the eager run's epoch 1 starts from;
+      * the optimizer is `optim.FusedAdam`: its step number is a device word advanced inside the graph, its learning rate comes
+        from a device table that a real StepLR filled (`optim.lr_table`);
+      * the dropout seeds are the ones the eager run would draw from the host generator (`optim.draw_dropout_seeds`, drawn before
+        the loop, the generator left where the eager run leaves it) in a device table; the graph loads row `step - 1` into the
+        words of a `ktgnn.DropoutSeedFeed` and the kernels add them to a baked seed of 0;
+      * the packed / folded weight copies are dropped before the capture and again between the update and the eval forward, so their
+        rebuild is part of the graph and runs on every replay;
+      * terms, counts and AUCs are copied to row `(step - 1) % cap` of the history by device-indexed copies inside the graph.
+    `loss_of(model_output) -> (loss, terms)`; `evaluate(counts_out, auc_out)` is the eval forward + count launch."""
+
+    def __init__(self, data, model, optimizer, hist, num_epoch, layers, loss_of, evaluate):
+        from .ktgnn import _DROPOUT_STEP, DropoutSeedFeed
+        from .optim import draw_dropout_seeds
+        dev = data.x.device
+        self.model, self.opt, self.hist = model, optimizer, hist
+        drop_caches = getattr(model, "_drop_param_caches", lambda: None)
+        self._drop_caches = drop_caches
+        step = optimizer.step_word
+        rows = max(int(num_epoch), 1)
+        seeds_dev = torch.empty(rows, max(layers, 1), dtype=torch.int64, device=dev)       # filled after the capture: read at replay
+        words = torch.empty(max(layers, 1), dtype=torch.int64, device=dev)
+        feed = DropoutSeedFeed(words)
+        counts_stage = torch.empty_like(hist.counts[0])
+        auc_stage = torch.empty_like(hist.auc[0]) if hist.auc is not None else None
+        if auc_stage is not None and data.x.shape[0] > _AUC_GRAPHED_MAX_ROWS:
+            raise NotImplementedError(f"graphed=True with metric='auc' covers graphs of up to {_AUC_GRAPHED_MAX_ROWS} nodes: beyond that "
+                                      "`ops.step2_auc` reduces with a multi-block torch sum, whose memset node must not be captured")
+        cap = hist.cap
+
+        def epoch():
+            step.add_(1)
+            row = step - 1
+            if layers:
+                words.copy_(seeds_dev.index_select(0, row.clamp(0, rows - 1)).view(-1))
+            feed.rewind()
+            model.train()
+            model.zero_grad(set_to_none=True)
+            loss, terms = loss_of(model(data))
+            loss.backward()
+            optimizer.step(advance=False)
+            drop_caches()                                  # the weights moved, their host-side version counters did not
+            evaluate(counts_stage, auc_stage)
+            slot = row.remainder(cap)
+            hist.terms.index_copy_(0, slot, terms.view(1, -1))
+            hist.counts.index_copy_(0, slot, counts_stage.unsqueeze(0))
+            if auc_stage is not None:
+                hist.auc.index_copy_(0, slot, auc_stage.view(1, -1))
+            if feed.taken != layers:
+                raise RuntimeError(f"graphed=True: the training forward took {feed.taken} dropout seeds, {layers} were prepared "
+                                   "(a dropout layer outside the HIP kernels' envelope draws from the device generator)")
+
+        rng, rng_dev = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+        state = {k: v.clone() for k, v in model.state_dict().items()}
+        seeds_dev.zero_()
+        _DROPOUT_STEP[0] = feed
+        try:
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):                  # kernel attributes, workspaces, library handles: settled before the capture
+                drop_caches()
+                epoch()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            model.zero_grad(set_to_none=True)              # the captured backward allocates the gradients the replays write
+            drop_caches()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                epoch()
+        finally:
+            _DROPOUT_STEP[0] = None
+        optimizer.flush()                                  # the gradients' addresses, known now
+        model.load_state_dict(state)
+        optimizer.zero_state()
+        torch.set_rng_state(rng)
+        torch.cuda.set_rng_state(rng_dev, dev)
+        drop_caches()
+        if layers and num_epoch:
+            seeds_dev.copy_(draw_dropout_seeds(num_epoch, layers))      # the host generator moves as in the eager loop
+        self._keep = (seeds_dev, words, counts_stage, auc_stage)
+
+    def replay(self):
+        self.graph.replay()
+
+    def finish(self):
+        """after the last epoch: the trained parameters are in the model; forget the graph's copies of them"""
+        self._drop_caches()
+        self.model.zero_grad(set_to_none=True)
+
+
+def _graphed_optimizer(model, lr, wd, num_epoch, step_size, gamma):
+    from .optim import FusedAdam, lr_table
+    return FusedAdam(model.parameters(), lr=lr, weight_decay=wd, lr_table=lr_table(lr, num_epoch, step_size, gamma))
+
+
 def _say(verbose, *a):
     if verbose:
         print(*a)
@@ -346,13 +450,14 @@ def _summary(final_acc, best_acc, verbose):
 
 def train_gnn(args, dataset, data, save=False, repeat=3, num_epoch=200, gnn='GCN', seed=None, step_size=100, gamma=0.1,
               num_layer=2, hidden=64, lr=1e-3, wd=5e-3, use_shceduler=True, step=1, Lambda=1., f1_average='macro', metric='f1', noDTC=False,
-              dropout=0.5, verbose=True, ckpt_dir='../ckpt', history=None):
+              dropout=0.5, verbose=True, ckpt_dir='../ckpt', history=None, graphed=False):
     """main_graph_knowledge_transfer.py:143-262 -> (loss_bucket, res_bucket_each).  `gnn='KTGNN'` only (the other backbones cannot
     get past `train` in the reference).  The model is `KTGNN_no_complement` built as at :179, Adam(lr, wd), StepLR(step_size, gamma);
     the best epoch is the one with the lowest `loss_target` (nll of lp_t^, :238); `save=True` writes
     {ckpt_dir}/model_{gnn}_{args.dataset_name}_best.ckpt at every improvement.  One eval forward per epoch serves both `test` and
     `get_each_clf_res`.  With `verbose=False, save=False` no epoch waits for the device.  `history` (a dict) receives 'eval_res'
-    (per epoch [train, val, test]), 'best_epoch' (0-based, of the last repeat), 'best_acc' and 'final_acc'."""
+    (per epoch [train, val, test]), 'best_epoch' (0-based, of the last repeat), 'best_acc' and 'final_acc'.  `graphed=True`: every
+    epoch is one replay of a HIP graph captured per repeat (`_GraphedEpoch`): the same run, launch cost paid once."""
     if gnn != 'KTGNN':
         if gnn in ('MLP', 'GCN', 'GraphSAGE', 'GAT', 'GATv2'):
             raise NotImplementedError(f"train_gnn(gnn={gnn!r}): the reference's train() fails on an undefined loss_kl for every backbone "
@@ -389,8 +494,15 @@ def train_gnn(args, dataset, data, save=False, repeat=3, num_epoch=200, gnn='GCN
                 print(data)
                 print('[Dataset-{}] train_num:{}, val_num:{}, test_num:{}, class_num:{}'.format(
                     args.dataset_name, data.train_mask.sum().item(), data.val_mask.sum().item(), data.test_mask.sum().item(), C))
-            optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
-            scheduler = StepLR(optimizer, step_size=step_size, gamma=gamma) if use_shceduler else None
+            if graphed:
+                if dropout > 0 and not (hidden % 4 == 0 and 4 <= hidden <= 1024 and num_layer > 1):
+                    raise NotImplementedError("graphed=True with dropout needs hidden % 4 == 0 and 4 <= hidden <= 1024 (the fused "
+                                              "BatchNorm / ReLU / dropout kernel, whose masks come from the host generator's seeds)")
+                optimizer = _graphed_optimizer(model, lr, wd, num_epoch, step_size if use_shceduler else None, gamma)
+                scheduler = None
+            else:
+                optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
+                scheduler = StepLR(optimizer, step_size=step_size, gamma=gamma) if use_shceduler else None
             best_acc = {'train': 0, 'val': 0, 'test': 0, 'loss': 666}
             res_bucket_each = {'source&target': [], 'target': [], 'target_hat': []}
             eval_hist, best_epoch = [], [None]
@@ -426,16 +538,26 @@ def train_gnn(args, dataset, data, save=False, repeat=3, num_epoch=200, gnn='GCN
                         if save:                                                        # every=1: the model is still this epoch's
                             torch.save(model.state_dict(), os.path.join(ckpt_dir, f'model_{gnn}_{args.dataset_name}_best.ckpt'))
 
+            ge = None
+            if graphed:
+                ge = _GraphedEpoch(data, model, optimizer, hist, num_epoch, len(model.convs) if dropout > 0 else 0,
+                                   lambda o: ops.step2_loss(o[0], o[1], o[2], plan.y, plan.train_u8, plan.central_u8, Lambda, return_terms=True),
+                                   lambda counts, auc: _eval_dtc(data, model, plan, counts_out=counts, auc_out=auc))
             for epoch in range(1, 1 + num_epoch):
                 t0[0] = time.time()
                 terms_slot, counts_slot, auc_slot = hist.slot()
-                terms_slot.copy_(_train_step(data, model, optimizer, plan, Lambda))
-                _eval_dtc(data, model, plan, counts_out=counts_slot, auc_out=auc_slot)
+                if ge is not None:
+                    ge.replay()                          # the graph writes this epoch's row itself
+                else:
+                    terms_slot.copy_(_train_step(data, model, optimizer, plan, Lambda))
+                    _eval_dtc(data, model, plan, counts_out=counts_slot, auc_out=auc_slot)
                 if scheduler is not None:
                     scheduler.step()
                 if hist.full:
                     consume()
             consume()
+            if ge is not None:
+                ge.finish()
             _say(verbose, '[Run-{} score] {}'.format(train_id, best_acc))
             for k in final_acc:
                 final_acc[k].append(best_acc[k])
@@ -478,11 +600,11 @@ def test_noDTC(data, model, gnn=None, metric='f1', f1_average='macro'):
 
 def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gnn='GCN', seed=None, num_layer=2, hidden=64,
                     lr=1e-3, wd=5e-3, use_scheduler=True, step=1, step_size=100, gamma=0.1, metric='f1', f1_average='macro',
-                    dropout=0.5, verbose=True, ckpt_dir='../ckpt', history=None):
+                    dropout=0.5, verbose=True, ckpt_dir='../ckpt', history=None, graphed=False):
     """main_graph_knowledge_transfer.py:302-396 for `gnn='GraphSAGE'` (what `main` passes under --no_dtc): `sage.GraphSAGE`,
     Adam(lr, wd), optional StepLR, best epoch by the lowest `loss_train` (:374); `save=True` writes
     {ckpt_dir}/model_{gnn}_{args.dataset_name}_share_best.ckpt.  Returns None like the reference; `history` (a dict) receives
-    'loss_train', 'eval_res', 'best_epoch', 'best_acc', 'final_acc'."""
+    'loss_train', 'eval_res', 'best_epoch', 'best_acc', 'final_acc'.  `graphed=True`: as in `train_gnn`."""
     if gnn != 'GraphSAGE':
         if gnn in ('MLP', 'GCN', 'GAT', 'GATv2', 'KTGNN'):
             raise NotImplementedError(f"train_gnn_noDTC(gnn={gnn!r}): only the GraphSAGE backbone (the one `main` uses) is implemented")
@@ -515,8 +637,12 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
                 print(data)
                 print('[Dataset-{}] train_num:{}, val_num:{}, test_num:{}, class_num:{}'.format(
                     dataset, data.train_mask.sum().item(), data.val_mask.sum().item(), data.test_mask.sum().item(), dataset.num_classes))
-            optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
-            scheduler = StepLR(optimizer, step_size=step_size, gamma=gamma) if use_scheduler else None
+            if graphed:
+                optimizer = _graphed_optimizer(model, lr, wd, num_epoch, step_size if use_scheduler else None, gamma)
+                scheduler = None
+            else:
+                optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
+                scheduler = StepLR(optimizer, step_size=step_size, gamma=gamma) if use_scheduler else None
             best_acc = {'train': 0, 'val': 0, 'test': 0, 'loss': 666}
             eval_hist, loss_hist, best_epoch = [], [], [None]
             hist = _History(dev, num_epoch, 2, len(_PLAIN_COMBOS), C, metric == 'auc', 1 if (verbose or save) else 0)
@@ -541,16 +667,26 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
                         if save:
                             torch.save(model.state_dict(), os.path.join(ckpt_dir, f'model_{gnn}_{args.dataset_name}_share_best.ckpt'))
 
+            ge = None
+            if graphed:
+                ge = _GraphedEpoch(data, model, optimizer, hist, num_epoch, len(model.convs) - 1 if dropout > 0 else 0,
+                                   lambda lp: ops.step2_nll(lp, plan.y, plan.train_u8, return_terms=True),
+                                   lambda counts, auc: _eval_plain(data, model, plan, counts_out=counts, auc_out=auc))
             for epoch in range(1, 1 + num_epoch):
                 t0[0] = time.time()
                 terms_slot, counts_slot, auc_slot = hist.slot()
-                terms_slot.copy_(_train_step_noDTC(data, model, optimizer, plan, gnn)[1])
-                _eval_plain(data, model, plan, counts_out=counts_slot, auc_out=auc_slot)
+                if ge is not None:
+                    ge.replay()
+                else:
+                    terms_slot.copy_(_train_step_noDTC(data, model, optimizer, plan, gnn)[1])
+                    _eval_plain(data, model, plan, counts_out=counts_slot, auc_out=auc_slot)
                 if scheduler is not None:
                     scheduler.step()
                 if hist.full:
                     consume()
             consume()
+            if ge is not None:
+                ge.finish()
             _say(verbose, '[Run-{} score] {}'.format(train_id, best_acc))
             for k in final_acc:
                 final_acc[k].append(best_acc[k])
@@ -569,6 +705,7 @@ _FLAGS = {
     "save": (None, False, None, "write the best epoch's parameters"),
     "to_undirected": (None, False, None, "add every edge's reverse before training"),
     "no_dtc": (None, False, None, "train GraphSAGE on the bridged graph instead of KTGNN"),
+    "graphed": (None, False, None, "run every epoch as one replay of a captured HIP graph (the same run, launch cost paid once)"),
     "num_layer": (int, 2, None, None),
     "num_epoch": (int, 300, None, None),
     "hidden_dim": (int, 64, None, None),
@@ -607,10 +744,12 @@ def main(args=None, verbose=True):
         if args.no_dtc:
             return train_gnn_noDTC(args, dataset, data, save=False, repeat=1, num_epoch=args.num_epoch, gnn='GraphSAGE', seed=0,
                                    num_layer=args.num_layer, hidden=args.hidden_dim, lr=1e-3, wd=5e-3, use_scheduler=False, step=1,
-                                   step_size=step_size, gamma=gamma, metric=args.eval_metric, f1_average='macro', verbose=verbose)
+                                   step_size=step_size, gamma=gamma, metric=args.eval_metric, f1_average='macro', verbose=verbose,
+                                   graphed=getattr(args, "graphed", False))
         return train_gnn(args, dataset, data, save=False, repeat=1, num_epoch=args.num_epoch, step_size=step_size, gamma=gamma,
                          gnn=args.model_name, seed=0, num_layer=args.num_layer, hidden=args.hidden_dim, lr=1e-3, wd=5e-3,
-                         use_shceduler=True, step=1, Lambda=1., metric=args.eval_metric, f1_average='macro', verbose=verbose)
+                         use_shceduler=True, step=1, Lambda=1., metric=args.eval_metric, f1_average='macro', verbose=verbose,
+                         graphed=getattr(args, "graphed", False))
 
 
 if __name__ == '__main__':

@@ -608,6 +608,23 @@ int bgnn_step2_counts_f32(const float* t0, int64_t ld0, const float* t1, int64_t
 int bgnn_step2_auc_count_f32(const float* score, const uint8_t* pos, int64_t N, const float* neg_sorted, const int64_t* n_neg,
                              long long* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-tensor Adam with device-resident step and schedule    main_graph_knowledge_transfer.py:205, :67, :353, :274
+ * for bridged_gnn_amd/optim.py (`torch.optim.Adam(params, lr, weight_decay)` built at :205 / :353, stepped at :67 / :274, its
+ * learning rate moved by the StepLR of :206 / :354).  ONE launch updates every tensor: records [n_tensors][5] int64 = device
+ * addresses of parameter, gradient, exp_avg, exp_avg_sq and the element count (fp32 tensors, contiguous, any alignment; a 0
+ * gradient address skips the tensor, as torch skips a parameter without .grad); chunk_map [n_chunks][2] int32 = (tensor, chunk
+ * within it), one chunk of bgnn_adam_chunk_elems() consecutive elements per block, every chunk of every tensor listed once.
+ * step: device int64, the 1-based number of this step; it is read, never written (the caller advances it, inside the same
+ * captured graph if there is one).  lr_table: device fp64 [lr_len], the rate of step s is lr_table[min(s, lr_len) - 1].
+ * Arithmetic of torch's _single_tensor_adam (amsgrad=False, maximize=False, L2 weight decay added to the gradient, eps added after
+ * the bias-corrected square root); bias corrections in fp64 from the step.  No atomics, no scratch, nothing to clear: safe
+ * inside a captured HIP graph, where only the addresses are baked in.                                                        */
+int64_t bgnn_adam_chunk_elems(void);
+int bgnn_adam_step_f32(const void* records, int32_t n_tensors, const int32_t* chunk_map, int64_t n_chunks, const int64_t* step,
+                       const double* lr_table, int64_t lr_len, double beta1, double beta2, double eps, double weight_decay,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
