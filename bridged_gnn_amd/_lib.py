@@ -94,6 +94,8 @@ SIGNATURES = {
                                        _SZ, _P]),
     "bgnn_pair_mlp_segsum_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _F32, _P, _I64, _P]),
     "bgnn_pair_mlp_eval_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "bgnn_pair_mlp_count_workspace_bytes": (_SZ, [_I64, _I64]),
+    "bgnn_pair_mlp_count_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "bgnn_pair_cos_loss_workspace_bytes": (_SZ, [_I64]),
     "bgnn_pair_cos_count_workspace_bytes": (_SZ, [_I64, _I64]),
     "bgnn_pair_cos_loss_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _SZ, _P]),

@@ -8,6 +8,8 @@
 // 64+4l..64+4l+3 of a 128-float row (two float4 loads; 16 lanes cover one 512-byte row contiguously).  A block has 16 groups.
 // Column sums are kept per lane in fp64 and reduced in a fixed order: groups of a block through LDS, then blocks by one thread
 // per column block (column_sum).  The grid of the pair passes depends on P only, so every sum is run-to-run identical.
+// The count pass (section 5) is the Cartesian evaluation: TP / FP / FN / TN of the eval-mode scorer over a whole product
+// rows1 x rows2 as a register-tiled fp32 vector kernel, 128 x 128 pairs per 256-thread block, no pair materialised.
 #include "bgnn_common.h"
 
 namespace {
@@ -19,6 +21,20 @@ constexpr int PM_MAX_BLOCKS = 1024;
 constexpr int STAT_W = 2 * U;          // per block: sum u, sum u^2
 constexpr int LOSS_W = 3 * U + 8;      // per block: sum dy, sum dy*xh, sum dl*h, then dl, bce, tp, fp, fn (+3 pad)
 constexpr int EVAL_W = 4;              // tp, fp, fn (+1 pad)
+
+// count pass tiling (as the cosine count of bgnn_pair_cos.hip)
+constexpr int CT = 128;                // rows1 and rows2 per tile
+constexpr int KC = 32;                 // reduction chunk staged in LDS
+constexpr int LDT = CT + 4;            // padded LDS row (k-major): breaks the bank pattern of the transposing stores
+constexpr int CNT_MAX_BLOCKS = 2048;
+constexpr int CNT_W = 4;               // per block: tp, fp, fn, tn (int64)
+
+__host__ __device__ inline int64_t cnt_tiles(int64_t m1, int64_t m2) { return ((m1 + CT - 1) / CT) * ((m2 + CT - 1) / CT); }
+
+__host__ __device__ inline int cnt_blocks(int64_t m1, int64_t m2) {
+  const int64_t t = cnt_tiles(m1, m2);
+  return (int)(t < CNT_MAX_BLOCKS ? (t < 1 ? 1 : t) : CNT_MAX_BLOCKS);
+}
 
 __host__ __device__ inline int pm_blocks(int64_t P) {
   const int64_t b = (P + GPB - 1) / GPB;
@@ -298,6 +314,145 @@ __global__ __launch_bounds__(256) void pm_eval_kernel(const float* __restrict__ 
   block_partials(red, EVAL_W, part);
 }
 
+// ---- 5. eval over a whole product rows1 x rows2: confusion counts, no pair list ------------------------------------------
+// logit(i, j) = b2 + sum_c w2[c] relu(scale2[c] (A[rows1[i]][c] + B[rows2[j]][c]) + shift2[c]).  BN2 is folded into the staged
+// tables once per tile and chunk: a' = fma(scale2, A, shift2) on the rows1 side, b' = scale2 * B on the rows2 side, so a pair and
+// column cost an add, a max and an fma with the block-uniform w2[c] (the adds and fmas on float2 lanes: packed fp32 issue).
+// The columns are accumulated in ascending order into one fp32 sum per pair; the predicate is pm_eval_kernel's
+// 1 / (1 + expf(-logit)) > 0.5f.  (pm_eval_kernel forms fma(a + b, scale2, shift2) and sums 16 lane partials of 8 columns
+// each: a different rounding of the same real number, so the two passes may disagree on pairs whose logit is within fp32
+// rounding of 0 -- DESIGN.md section 11.)
+// Thread (tx, ty) of a 16 x 16 block owns tile rows {4ty + a, 64 + 4ty + a} and tile columns {4tx + b, 64 + 4tx + b}, a, b < 4;
+// each 32-wide chunk of both sides is stored k-major in LDS, so a thread's 16 operands of a k-step are four float4 reads (the
+// rows1 side a broadcast inside each 16-lane group, the rows2 side 64 consecutive dwords per group).  Rows past m1 / m2 are
+// staged as zeros and masked out of the counts.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ int tile_off(int t4, int i) { return i < 4 ? 4 * t4 + i : 64 + 4 * t4 + (i - 4); }
+
+template <bool SHIFTED>
+__device__ __forceinline__ void stage_chunk(const float* __restrict__ T, int64_t ld, int64_t nT, const int64_t* __restrict__ rows,
+                                            int64_t m, int64_t base, int k0, const float* __restrict__ scale2,
+                                            const float* __restrict__ shift2, float* __restrict__ S) {
+  // 128 rows x 32 floats = 1024 float4; 4 per thread.  Thread t: row t / 8 (+ 32 i), float4 (t % 8) of the chunk
+  const int t = threadIdx.x;
+  const int c4 = t % 8;
+  const float4 sc = *reinterpret_cast<const float4*>(scale2 + k0 + 4 * c4);
+  float4 sh = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (SHIFTED) sh = *reinterpret_cast<const float4*>(shift2 + k0 + 4 * c4);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = t / 8 + 32 * i;
+    const int64_t gi = base + r;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (gi < m) {
+      v = *reinterpret_cast<const float4*>(T + clampi(rows[gi], nT) * ld + k0 + 4 * c4);
+      if (SHIFTED) {
+        v.x = fmaf(sc.x, v.x, sh.x); v.y = fmaf(sc.y, v.y, sh.y); v.z = fmaf(sc.z, v.z, sh.z); v.w = fmaf(sc.w, v.w, sh.w);
+      } else {
+        v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w;
+      }
+    }
+    S[(4 * c4 + 0) * LDT + r] = v.x;
+    S[(4 * c4 + 1) * LDT + r] = v.y;
+    S[(4 * c4 + 2) * LDT + r] = v.z;
+    S[(4 * c4 + 3) * LDT + r] = v.w;
+  }
+}
+
+__global__ __launch_bounds__(256) void pm_count_kernel(const float* __restrict__ A, int64_t lda, int64_t nA, const float* __restrict__ B,
+                                                       int64_t ldb, int64_t nB, const int64_t* __restrict__ rows1, int64_t m1,
+                                                       const int64_t* __restrict__ rows2, int64_t m2, const int64_t* __restrict__ lab1,
+                                                       const int64_t* __restrict__ lab2, const float* __restrict__ scale2,
+                                                       const float* __restrict__ shift2, const float* __restrict__ w2,
+                                                       const float* __restrict__ b2, long long* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float As[KC * LDT];
+  __shared__ __attribute__((aligned(16))) float Bs[KC * LDT];
+  __shared__ float Ws[U];
+  __shared__ long long red[256 * CNT_W];
+  const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+  if (threadIdx.x < U) Ws[threadIdx.x] = w2[threadIdx.x];   // visible after the first chunk's barrier
+  const float bias2 = b2[0];
+  const int64_t tiles_n = (m2 + CT - 1) / CT;
+  const int64_t ntiles = cnt_tiles(m1, m2);
+  long long tp = 0, fp = 0, fn = 0, tn = 0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t base1 = (tile / tiles_n) * CT, base2 = (tile % tiles_n) * CT;
+    f32x2 acc[8][4];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[a][b] = f32x2{0.f, 0.f};
+    for (int k0 = 0; k0 < U; k0 += KC) {
+      __syncthreads();                                   // the previous chunk (or tile) is consumed
+      stage_chunk<true>(A, lda, nA, rows1, m1, base1, k0, scale2, shift2, As);
+      stage_chunk<false>(B, ldb, nB, rows2, m2, base2, k0, scale2, shift2, Bs);
+      __syncthreads();
+#pragma unroll 2
+      for (int k = 0; k < KC; ++k) {
+        const float4 a0 = *reinterpret_cast<const float4*>(As + k * LDT + 4 * ty);
+        const float4 a1 = *reinterpret_cast<const float4*>(As + k * LDT + 64 + 4 * ty);
+        const float4 b0 = *reinterpret_cast<const float4*>(Bs + k * LDT + 4 * tx);
+        const float4 b1 = *reinterpret_cast<const float4*>(Bs + k * LDT + 64 + 4 * tx);
+        const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        const f32x2 bv[4] = {f32x2{b0.x, b0.y}, f32x2{b0.z, b0.w}, f32x2{b1.x, b1.y}, f32x2{b1.z, b1.w}};
+        const float w = Ws[k0 + k];
+        const f32x2 wv = f32x2{w, w};
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+          const f32x2 aa = f32x2{av[a], av[a]};
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const f32x2 x = aa + bv[b];
+            const f32x2 h = f32x2{fmaxf(x.x, 0.f), fmaxf(x.y, 0.f)};
+            acc[a][b] = __builtin_elementwise_fma(wv, h, acc[a][b]);
+          }
+        }
+      }
+    }
+    int64_t la[8], lb[8];
+    bool va[8], vb[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int64_t gi = base1 + tile_off(ty, i), gj = base2 + tile_off(tx, i);
+      va[i] = gi < m1;
+      vb[i] = gj < m2;
+      la[i] = va[i] ? lab1[clampi(rows1[gi], nA)] : 0;
+      lb[i] = vb[i] ? lab2[clampi(rows2[gj], nB)] : 0;
+    }
+    int ctp = 0, cfp = 0, cfn = 0, ctn = 0;
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        if (!(va[a] && vb[b])) continue;
+        const float logit = ((b & 1) ? acc[a][b / 2].y : acc[a][b / 2].x) + bias2;
+        const bool pos = 1.f / (1.f + expf(-logit)) > 0.5f;
+        const bool same = la[a] == lb[b];
+        ctp += (pos && same);
+        cfp += (pos && !same);
+        cfn += (!pos && same);
+        ctn += (!pos && !same);
+      }
+    tp += ctp; fp += cfp; fn += cfn; tn += ctn;
+  }
+  long long* r = red + threadIdx.x * CNT_W;
+  r[0] = tp; r[1] = fp; r[2] = fn; r[3] = tn;
+  __syncthreads();
+  if (threadIdx.x < CNT_W) {
+    long long s = 0;
+    for (int t = 0; t < 256; ++t) s += red[t * CNT_W + threadIdx.x];
+    part[(int64_t)blockIdx.x * CNT_W + threadIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(64) void pm_count_finish_kernel(const long long* __restrict__ part, int nblk, long long* __restrict__ counts) {
+  if (threadIdx.x >= CNT_W) return;
+  long long s = 0;
+  for (int b = 0; b < nblk; ++b) s += part[(int64_t)b * CNT_W + threadIdx.x];
+  counts[threadIdx.x] = s;
+}
+
 bool rows_ok(const float* t, int64_t ld) { return bgnn_aligned16(t) && ld >= U && ld % 4 == 0; }
 
 }  // namespace
@@ -375,5 +530,33 @@ extern "C" int bgnn_pair_mlp_eval_f32(const float* A, int64_t lda, int64_t nA, c
     hipLaunchKernelGGL(pm_sum_partials_kernel, dim3(EVAL_W), dim3(256), 0, st, part, nblk, EVAL_W, counts_opt);
     BGNN_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+extern "C" size_t bgnn_pair_mlp_count_workspace_bytes(int64_t m1, int64_t m2) {
+  return (size_t)cnt_blocks(m1, m2) * CNT_W * sizeof(long long);
+}
+
+extern "C" int bgnn_pair_mlp_count_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB,
+                                       const int64_t* rows1, int64_t m1, const int64_t* rows2, int64_t m2, const int64_t* lab1,
+                                       const int64_t* lab2, const float* scale2, const float* shift2, const float* w2,
+                                       const float* b2, long long* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (!A || !B || !lab1 || !lab2 || !scale2 || !shift2 || !w2 || !b2 || !counts || !ws) return BGNN_E_NULL;
+  if (m1 < 0 || m2 < 0 || nA <= 0 || nB <= 0) return BGNN_E_SHAPE;
+  if ((m1 > 0 && !rows1) || (m2 > 0 && !rows2)) return BGNN_E_NULL;
+  if (!rows_ok(A, lda) || !rows_ok(B, ldb) || !bgnn_aligned16(scale2) || !bgnn_aligned16(shift2)) return BGNN_E_ALIGN;
+  if (ws_bytes < bgnn_pair_mlp_count_workspace_bytes(m1, m2)) return BGNN_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (m1 == 0 || m2 == 0) {
+    const hipError_t e = hipMemsetAsync(counts, 0, CNT_W * sizeof(long long), st);
+    return e == hipSuccess ? 0 : (int)e;
+  }
+  const int nblk = cnt_blocks(m1, m2);
+  long long* part = (long long*)ws;
+  hipLaunchKernelGGL(pm_count_kernel, dim3(nblk), dim3(256), 0, st, A, lda, nA, B, ldb, nB, rows1, m1, rows2, m2, lab1, lab2, scale2,
+                     shift2, w2, b2, part);
+  BGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pm_count_finish_kernel, dim3(1), dim3(64), 0, st, part, nblk, counts);
+  BGNN_LAUNCH_CHECK();
   return 0;
 }

@@ -11,7 +11,7 @@ __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "a
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
            "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "wide_heads_supported",
            "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd", "pair_csr", "pair_mlp_stats", "pair_mlp_loss",
-           "pair_mlp_segsum", "pair_mlp_eval", "PAIR_MLP_WIDTH", "pair_cos_loss", "pair_cos_segsum", "pair_cos_count",
+           "pair_mlp_segsum", "pair_mlp_eval", "pair_mlp_count", "PAIR_MLP_WIDTH", "pair_cos_loss", "pair_cos_segsum", "pair_cos_count",
            "PAIR_COS_WIDTH"]
 
 
@@ -1015,6 +1015,29 @@ def pair_mlp_eval(A, B, idx1, idx2, scale2, shift2, w2, b2, y_u8=None):
                                         L.ptr(p), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
     L.check(rc, "bgnn_pair_mlp_eval_f32")
     return p, None if counts is None else counts[:3]
+
+
+def pair_mlp_count(A, B, rows1, rows2, lab1, lab2, scale2, shift2, w2, b2):
+    """int64 [4] = TP, FP, FN, TN of the eval-mode scorer (`pair_mlp_eval`'s sigmoid(logit) > 0.5 on u = A[rows1[i]] + B[rows2[j]])
+    against lab1[rows1[i]] == lab2[rows2[j]] over the whole product rows1 x rows2 (eval_within_domain_v2 / eval_cross_domain_v2's
+    eval_mode='all' lists, never materialised)."""
+    assert A.dtype == torch.float32 and B.dtype == torch.float32 and A.dim() == 2 and B.dim() == 2
+    assert A.shape[1] == PAIR_MLP_WIDTH == B.shape[1] and A.stride(1) == 1 and B.stride(1) == 1
+    assert rows1.dtype == torch.int64 and rows2.dtype == torch.int64 and rows1.dim() == 1 and rows2.dim() == 1
+    assert lab1.dtype == torch.int64 and lab2.dtype == torch.int64
+    assert lab1.shape[0] == A.shape[0] and lab2.shape[0] == B.shape[0] and lab1.is_contiguous() and lab2.is_contiguous()
+    for v in (scale2, shift2, w2):
+        assert v.dtype == torch.float32 and v.shape == (PAIR_MLP_WIDTH,) and v.is_contiguous()
+    assert b2.dtype == torch.float32 and b2.numel() == 1
+    rows1, rows2 = rows1.contiguous(), rows2.contiguous()
+    m1, m2 = int(rows1.shape[0]), int(rows2.shape[0])
+    counts = torch.empty(4, dtype=torch.int64, device=A.device)
+    ws = torch.empty(max(1, int(L.lib().bgnn_pair_mlp_count_workspace_bytes(m1, m2))), dtype=torch.uint8, device=A.device)
+    rc = L.lib().bgnn_pair_mlp_count_f32(L.ptr_rows(A), A.stride(0), int(A.shape[0]), L.ptr_rows(B), B.stride(0), int(B.shape[0]),
+                                         L.ptr(rows1), m1, L.ptr(rows2), m2, L.ptr(lab1), L.ptr(lab2), L.ptr(scale2), L.ptr(shift2),
+                                         L.ptr(w2), L.ptr(b2), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_pair_mlp_count_f32")
+    return counts
 
 
 # ---- cosine similarity-learner pair passes (bgnn.h: bgnn_pair_cos_*, csrc/bgnn_pair_cos.hip) ------------------------------------

@@ -6,9 +6,11 @@ reference with strict=True and into `bridge.BridgeScorer` without conversion.  T
 128) -> BN2 -> ReLU -> Linear(128, 1) -> sigmoid -> BCE over 40 000-pair lists -- runs as per-node products plus the HIP pair
 passes of csrc/bgnn_pair_mlp.hip (`_PairMlpFn`; derivation in DESIGN.md section 11).  Everything else is per-node torch.
 
-Supported: version v2, backbone 'mlp', sim_mode 'mlp', eval_mode 'sampling', shuffle=False samplers (what the office recipes
-run, run.sh #2/#3).  sim_mode 'cosine', backbone 'gnn', eval_mode 'all' and shuffling raise NotImplementedError.  The v1 learner
-(Adversarial_Learner, the cosine scorer Similar) is bridged_gnn_amd.simlearner_v1.
+Supported: version v2, backbone 'mlp', sim_mode 'mlp', eval_mode 'sampling' (balanced pair lists, what the office recipes run,
+run.sh #2/#3) and 'all' (every pair of the Cartesian split products, counted by the product pass of csrc/bgnn_pair_mlp.hip without
+a pair list), evaluation metrics 'f1' and 'acc', shuffle=False samplers.  sim_mode 'cosine', backbone 'gnn', shuffling, metric
+'auc', conf_lower_bound and a training metric other than 'f1' raise NotImplementedError.  The v1 learner (Adversarial_Learner, the
+cosine scorer Similar) is bridged_gnn_amd.simlearner_v1.
 """
 import copy
 import os
@@ -310,20 +312,32 @@ class Similar_v2(nn.Module):
         return _PairMlpFn.apply(z1, z2, idx1, idx2, y, bn1.weight, bn1.bias, l1.weight, l1.bias, bn2.weight, bn2.bias, l2.weight,
                                 l2.bias, bn1, bn2)
 
-    def pair_scores(self, z1, z2, idx1, idx2, y_pair=None):
-        """Eval-mode (running statistics) sigmoid scores of the pairs and, with labels, [TP, FP, FN] -- no autograd."""
+    def _eval_tables(self, z1, z2):
+        """The eval-mode separable form (running statistics): u = A[i] + B[j] per pair, then BN2 as the per-column affine
+        (scale2, shift2) -> (A [n1, 128], B [n2, 128], scale2, shift2, w2 [128], b2 [1])."""
         bn1, l1, bn2, _, l2 = self.lin_self
         H = z1.shape[1]
+        s1 = bn1.weight / torch.sqrt(bn1.running_var + bn1.eps)
+        t1 = bn1.bias - bn1.running_mean * s1
+        A = F.linear(z1 * s1[:H] + t1[:H], l1.weight[:, :H]).contiguous()
+        B = F.linear(z2 * s1[H:] + t1[H:], l1.weight[:, H:], l1.bias).contiguous()
+        s2 = (bn2.weight / torch.sqrt(bn2.running_var + bn2.eps)).contiguous()
+        t2 = (bn2.bias - bn2.running_mean * s2).contiguous()
+        return A, B, s2, t2, l2.weight.reshape(-1).contiguous(), l2.bias.reshape(-1).contiguous()
+
+    def pair_scores(self, z1, z2, idx1, idx2, y_pair=None):
+        """Eval-mode (running statistics) sigmoid scores of the pairs and, with labels, [TP, FP, FN] -- no autograd."""
         with torch.no_grad():
-            s1 = bn1.weight / torch.sqrt(bn1.running_var + bn1.eps)
-            t1 = bn1.bias - bn1.running_mean * s1
-            A = F.linear(z1 * s1[:H] + t1[:H], l1.weight[:, :H]).contiguous()
-            B = F.linear(z2 * s1[H:] + t1[H:], l1.weight[:, H:], l1.bias).contiguous()
-            s2 = (bn2.weight / torch.sqrt(bn2.running_var + bn2.eps)).contiguous()
-            t2 = (bn2.bias - bn2.running_mean * s2).contiguous()
+            A, B, s2, t2, w2, b2 = self._eval_tables(z1, z2)
             y = None if y_pair is None else y_pair.to(torch.uint8).reshape(-1).contiguous()
-            return ops.pair_mlp_eval(A, B, idx1.contiguous(), idx2.contiguous(), s2, t2, l2.weight.reshape(-1).contiguous(),
-                                     l2.bias.reshape(-1).contiguous(), y)
+            return ops.pair_mlp_eval(A, B, idx1.contiguous(), idx2.contiguous(), s2, t2, w2, b2, y)
+
+    def pair_counts(self, z1, z2, rows1, rows2, lab1, lab2):
+        """Eval-mode int64 [TP, FP, FN, TN] of (score > 0.5) against lab1[rows1[i]] == lab2[rows2[j]] over the whole product
+        rows1 x rows2 (int64 row ids into z1 / z2; lab1 / lab2 per node) -- no pair list, no autograd."""
+        with torch.no_grad():
+            A, B, s2, t2, w2, b2 = self._eval_tables(z1, z2)
+            return ops.pair_mlp_count(A, B, rows1, rows2, lab1.long().contiguous(), lab2.long().contiguous(), s2, t2, w2, b2)
 
     def _scores(self, z1, z2, idx1, idx2):
         if self.training:
@@ -622,18 +636,87 @@ def train_adv_few_shot(epoch, data_src, data_tar, model, optimizer_src_tar, opti
 
 
 def _check_eval(metric, eval_mode, conf_lower_bound):
-    if metric != "f1":
+    if eval_mode not in ("sampling", "all"):
+        raise NotImplementedError("Not Implemented Eval Mode:{}".format(eval_mode))
+    if metric == "auc":
         _unsupported(f"metric={metric!r}")
-    if eval_mode != "sampling":
-        _unsupported(f"eval_mode={eval_mode!r}")
+    if metric not in ("f1", "acc"):
+        raise NotImplementedError("NotImplemented Metric:{}".format(metric))
     if conf_lower_bound is not None:
         _unsupported("conf_lower_bound")
 
 
+def _rows(mask):
+    return torch.nonzero(mask).reshape(-1).contiguous()
+
+
+def _all_masks_within(data, split):
+    """eval_mode='all' inside one domain (scripts.py:374-375): (mask of rows1 = every labelled node, mask of rows2 = the split)"""
+    return data.train_mask | data.val_mask | data.test_mask, data.val_mask if split == "val" else data.test_mask
+
+
+def _all_masks_cross(data_src, data_tar, split):
+    """eval_mode='all' across the domains (scripts.py:317-318, :326-327): the two products ((source mask, target mask), ...)"""
+    if split == "val":
+        return ((data_src.val_mask, data_tar.train_mask | data_tar.val_mask),
+                (data_src.train_mask, data_tar.val_mask))
+    return ((data_src.test_mask, data_tar.train_mask | data_tar.test_mask | data_tar.val_mask),
+            (data_src.train_mask | data_src.val_mask, data_tar.test_mask))
+
+
+def _pair_score(tp, fp, fn, tn, metric):
+    """f1_score(average='binary') / accuracy_score of the pair predictions from their confusion counts"""
+    if metric == "f1":
+        return f1_from_counts(tp, fp, fn)
+    total = float(tp) + float(fp) + float(fn) + float(tn)
+    return 0.0 if total == 0.0 else (float(tp) + float(tn)) / total
+
+
+def _list_score(counts, P, metric):
+    """the list pass counts [TP, FP, FN] of P pairs; TN is the rest"""
+    tp, fp, fn = counts.tolist()
+    return _pair_score(tp, fp, fn, P - tp - fp - fn, metric)
+
+
+def _clf_score(model, data, z, mask_2, metric):
+    """macro f1 (metric 'f1') or accuracy (metric 'acc', scripts.py:411-413) of the node classifier on the split"""
+    y2 = data.y[mask_2]
+    pred = model.source_learner.sim_net.classify(z)[mask_2].max(1)[1] if model.source_clf else torch.zeros_like(y2)
+    if metric == "acc":
+        return 0.0 if y2.numel() == 0 else float((pred == y2).double().mean().item())
+    return macro_f1(y2, pred)
+
+
+def _encode(model, data, domain):
+    if domain == "source":
+        return model.source_learner.backbone(data.x, data.edge_index)
+    return model.target_learner.encode(data)[0]
+
+
+def _within_all(data, model, split, z, metric):
+    mask_1, mask_2 = _all_masks_within(data, split)
+    tp, fp, fn, tn = model.source_learner.sim_net.pair_counts(z, z, _rows(mask_1), _rows(mask_2), data.y, data.y).tolist()
+    return _pair_score(tp, fp, fn, tn, metric), _clf_score(model, data, z, mask_2, metric)
+
+
+def _cross_all_counts(data_src, data_tar, model, split, z_src, z_tar):
+    """int64 [TP, FP, FN, TN] over the two products of eval_cross_domain_v2's concatenated 'all' list"""
+    sim = model.source_learner.sim_net
+    (m_s1, m_t1), (m_s2, m_t2) = _all_masks_cross(data_src, data_tar, split)
+    return (sim.pair_counts(z_src, z_tar, _rows(m_s1), _rows(m_t1), data_src.y, data_tar.y)
+            + sim.pair_counts(z_src, z_tar, _rows(m_s2), _rows(m_t2), data_src.y, data_tar.y))
+
+
 def eval_within_domain_v2(data, model, pair_enumerator=None, split="test", domain="target", conf_lower_bound=None, metric="f1",
                           eval_mode="sampling"):
-    """scripts.py:374-420 (eval_mode='sampling') -> (pair f1, classifier macro f1 on the split)"""
+    """scripts.py:372-416 -> (pair score, classifier score on the split); metric 'f1' (binary f1 / macro f1) or 'acc'.
+    eval_mode='sampling' scores a balanced list from `pair_enumerator`; 'all' counts every pair of (train | val | test) x split
+    and does not use `pair_enumerator`."""
     _check_eval(metric, eval_mode, conf_lower_bound)
+    if eval_mode == "all":
+        with torch.no_grad():
+            model.eval()
+            return _within_all(data, model, split, _encode(model, data, domain), metric)
     mask_2 = data.val_mask if split == "val" else data.test_mask
     num_classes = int(data.y.max().item()) + 1
     dev = data.x.device
@@ -641,39 +724,45 @@ def eval_within_domain_v2(data, model, pair_enumerator=None, split="test", domai
                                                                               shuffle=False))
     with torch.no_grad():
         model.eval()
-        sim = model.source_learner.sim_net
-        if domain == "source":
-            z = model.source_learner.backbone(data.x, data.edge_index)
-        else:
-            z, _ = model.target_learner.encode(data)
-        _, counts = sim.pair_scores(z, z, idx1, idx2, data.y[idx1] == data.y[idx2])
-        score_clf = 0.0
-        if model.source_clf:
-            pred_clf = sim.classify(z)[mask_2].max(1)[1]
-            score_clf = macro_f1(data.y[mask_2], pred_clf)
-        else:
-            score_clf = macro_f1(data.y[mask_2], torch.zeros_like(data.y[mask_2]))
-    return _f1(counts), score_clf
+        z = _encode(model, data, domain)
+        _, counts = model.source_learner.sim_net.pair_scores(z, z, idx1, idx2, data.y[idx1] == data.y[idx2])
+        score_clf = _clf_score(model, data, z, mask_2, metric)
+    return _list_score(counts, int(idx1.shape[0]), metric), score_clf
 
 
 def eval_cross_domain_v2(data_src, data_tar, model, pair_enumerator=None, split="test", conf_lower_bound=None, metric="f1",
                          eval_mode="sampling"):
-    """scripts.py:315-371 (eval_mode='sampling') -> pair f1"""
+    """scripts.py:315-367 -> pair score ('f1' or 'acc').  eval_mode='all' counts the reference's two products (source split x
+    target, source train(+val) x target split) and does not use `pair_enumerator`."""
     _check_eval(metric, eval_mode, conf_lower_bound)
+    if eval_mode == "all":
+        with torch.no_grad():
+            model.eval()
+            z_src, z_tar = _encode(model, data_src, "source"), _encode(model, data_tar, "target")
+            return _pair_score(*_cross_all_counts(data_src, data_tar, model, split, z_src, z_tar).tolist(), metric)
     num_classes = int(data_tar.y.max().item()) + 1
     dev = data_src.x.device
     idx1, idx2 = (_dev_idx(t, dev) for t in pair_enumerator.balanced_sampling(max_class_num=num_classes, sample_size=100000,
                                                                               shuffle=False))
     with torch.no_grad():
         model.eval()
-        z_src = model.source_learner.backbone(data_src.x, data_src.edge_index)
-        z_tar, _ = model.target_learner.encode(data_tar)
+        z_src, z_tar = _encode(model, data_src, "source"), _encode(model, data_tar, "target")
         _, counts = model.source_learner.sim_net.pair_scores(z_src, z_tar, idx1, idx2, data_src.y[idx1] == data_tar.y[idx2])
-    return _f1(counts)
+    return _list_score(counts, int(idx1.shape[0]), metric)
 
 
 def eval_adv_v2(data_src, data_tar, model, split="test", metric="f1", enu_list=None, eval_mode="sampling"):
-    """scripts.py:422-429 -> (pair_src, clf_src, pair_tar, clf_tar, pair_cross)"""
+    """scripts.py:418-426 -> (pair_src, clf_src, pair_tar, clf_tar, pair_cross).  With eval_mode='all' each domain is encoded
+    once for the three evaluations and `enu_list` is not used."""
+    if eval_mode == "all":
+        _check_eval(metric, eval_mode, None)
+        with torch.no_grad():
+            model.eval()
+            z_src, z_tar = _encode(model, data_src, "source"), _encode(model, data_tar, "target")
+            ps, cs = _within_all(data_src, model, split, z_src, metric)
+            pt, ct = _within_all(data_tar, model, split, z_tar, metric)
+            pc = _pair_score(*_cross_all_counts(data_src, data_tar, model, split, z_src, z_tar).tolist(), metric)
+        return ps, cs, pt, ct, pc
     enu_src, enu_tar, enu_cross = enu_list
     ps, cs = eval_within_domain_v2(data_src, model, split=split, domain="source", metric=metric, pair_enumerator=enu_src,
                                    eval_mode=eval_mode)

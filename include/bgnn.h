@@ -526,8 +526,15 @@ int bgnn_coalesce_i64(int64_t* edge_index, int64_t E, int64_t num_nodes, int64_t
  * segsum: S[n] = sum over the pairs of node n (CSR rowptr [n_own+1] / perm [P] = pair ids, e.g. bgnn_build_dst_csr(eperm) of the
  *         list by n) of du_p = g2 rstd2 (dy_p - sum dy / P - x2_p sum(dy x2) / P), u_p = own[n] + other[idx_other[p]]; every row
  *         written once (zero rows for nodes without pairs).  Called with (A, B, idx2) for S1 and (B, A, idx1) for S2.
- * eval:   running-statistics form: BN2 as scale2 / shift2, p_out [P]; with y_opt, counts_opt[0:3] = TP, FP, FN (fp64).    */
+ * eval:   running-statistics form: BN2 as scale2 / shift2, p_out [P]; with y_opt, counts_opt[0:3] = TP, FP, FN (fp64).
+ * count:  the running-statistics form over every (i, j) of rows1 [m1] x rows2 [m2] (int64 ids), no pair materialised:
+ *         counts [4] int64 = TP, FP, FN, TN of (sigmoid(b2 + sum_c w2[c] relu(scale2[c] (A[rows1[i]][c] + B[rows2[j]][c]) +
+ *         shift2[c])) > 0.5 in fp32, eval's predicate) against (lab1[rows1[i]] == lab2[rows2[j]]) (lab1 [nA], lab2 [nB] int64).
+ *         BN2 is folded into the tables (scale2 A + shift2, scale2 B) and the columns summed in ascending order, so a pair
+ *         whose logit is within fp32 rounding of 0 may be counted differently from eval.  scale2 / shift2 16-B aligned; m1 or
+ *         m2 may be 0.  ws: bgnn_pair_mlp_count_workspace_bytes(m1, m2).                                                     */
 size_t bgnn_pair_mlp_workspace_bytes(int64_t P);
+size_t bgnn_pair_mlp_count_workspace_bytes(int64_t m1, int64_t m2);
 int bgnn_pair_mlp_stats_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* idx1,
                             const int64_t* idx2, int64_t P, float momentum, float* run_mean_opt, float* run_var_opt, double* stats,
                             void* ws, size_t ws_bytes, void* stream);
@@ -543,6 +550,10 @@ int bgnn_pair_mlp_eval_f32(const float* A, int64_t lda, int64_t nA, const float*
                            const int64_t* idx2, const uint8_t* y_opt, int64_t P, const float* scale2, const float* shift2,
                            const float* w2, const float* b2, float* p_out, double* counts_opt, void* ws, size_t ws_bytes,
                            void* stream);
+int bgnn_pair_mlp_count_f32(const float* A, int64_t lda, int64_t nA, const float* B, int64_t ldb, int64_t nB, const int64_t* rows1,
+                            int64_t m1, const int64_t* rows2, int64_t m2, const int64_t* lab1, const int64_t* lab2,
+                            const float* scale2, const float* shift2, const float* w2, const float* b2, long long* counts, void* ws,
+                            size_t ws_bytes, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------
