@@ -21,7 +21,7 @@ from .data import Data
 
 __all__ = ["BridgeScorer", "add_topk_sim_cross_domain_edges", "add_topk_sim_within_domain_edges", "sharded_cosine_topk_edges",
            "merge_graphs", "pair_enumeration", "check_added_edges_cross_domain_validity",
-           "check_added_edges_within_domain_validity", "align_e_sim_to_edges", "reorder", "eval_bridged_Graph",
+           "check_added_edges_within_domain_validity", "align_e_sim_to_edges", "fused_edge_flags", "reorder", "eval_bridged_Graph",
            "eval_homophily", "gen_bridged_graph"]
 
 _BN_EPS = 1e-5
@@ -349,47 +349,109 @@ def _filter_report(verbose, *a):
         print(*a)
 
 
+def _node_tables(data, probs_clf, dev, with_train):
+    """per-node operands of the fused pass: features, inverse row norms, argmax class and label as int32 (+ the train mask)"""
+    x = data.x.to(dev).float().contiguous()
+    t = (x, ops.row_inv_norms(x), probs_clf.argmax(dim=1).to(torch.int32), data.y.to(dev).to(torch.int32))
+    return t + (ops.as_u8(data.train_mask.to(dev)),) if with_train else t
+
+
+def fused_edge_flags(edge_index_added, e_sim, data_from, data_to, probs_clf_from, probs_clf_to, within, thres_conf_quantile,
+                     thres_feat_sim):
+    """`ops.edge_validity` on the filters' own arguments -> (flags [E] uint8, the five cumulative removal counts, sim [E]).
+    `e_sim`: one similarity per edge, or the pair (e_sim_mat, idx_mat) of [n_to, k] top-k tables to look each edge up in."""
+    if not edge_index_added.is_cuda:
+        raise RuntimeError("fused=True runs the HIP edge-validity pass and needs GPU tensors; there is no CPU path "
+                           f"(got a {edge_index_added.device} edge list) -- use fused=False on the CPU")
+    dev = edge_index_added.device
+    nodes_to = _node_tables(data_to, probs_clf_to, dev, True)
+    nodes_from = nodes_to[:4] if within else _node_tables(data_from, probs_clf_from, dev, False)
+    if isinstance(e_sim, (tuple, list)):
+        return ops.edge_validity(edge_index_added, nodes_from, nodes_to, within, thres_conf_quantile, thres_feat_sim,
+                                 e_sim_mat=e_sim[0].to(dev).float(), idx_mat=e_sim[1].to(dev))
+    return ops.edge_validity(edge_index_added, nodes_from, nodes_to, within, thres_conf_quantile, thres_feat_sim, e_sim=e_sim)
+
+
+def _fused_filter(edge_index_added, e_sim, data_from, data_to, probs_from, probs_to, within, q, thres_feat_sim, verbose, return_counts):
+    flags, counts, sim = fused_edge_flags(edge_index_added, e_sim, data_from, data_to, probs_from, probs_to, within, q, thres_feat_sim)
+    del sim
+    _filter_report(verbose, "removed after rules 1..5 (cumulative):", counts, "of", flags.numel())
+    out = edge_index_added[:, flags == 0]
+    return (out, counts) if return_counts else out
+
+
 def check_added_edges_cross_domain_validity(edge_index_added, e_sim, data_src, data_tar, probs_clf_src, probs_clf_tar,
-                                            thres_conf_quantile=0.1, thres_feat_sim=0.0, verbose=False):
+                                            thres_conf_quantile=0.1, thres_feat_sim=0.0, verbose=False, fused=False,
+                                            return_counts=False):
     """main_bridged_graph.py:225-264.  `e_sim`: one similarity per edge.  Pass `align_e_sim_to_edges(...)` for the
     intended semantics, or the reference's own `e_sim_mat.view(-1)` to reproduce its index-misaligned behaviour
-    bit for bit (same length, different order)."""
+    bit for bit (same length, different order).
+    fused=True (GPU tensors only) runs the one-launch HIP pass (`ops.edge_validity`) instead of the torch ops below: no [E, F]
+    gathers, no 2^24 limit on the quantile; `e_sim` may then also be the pair (e_sim_mat, idx_mat) of top-k tables, which replaces
+    `align_e_sim_to_edges`.  Rule 5 compares an fp32 cosine summed in another order: an edge whose cosine lies within
+    2 F 2^-24 + 8 2^-24 of `thres_feat_sim` may be decided differently.
+    return_counts=True -> (edges, [removed after rule 1, .. after rule 5]), the cumulative counts the reference prints (:241-255)."""
+    if fused:
+        return _fused_filter(edge_index_added, e_sim, data_src, data_tar, probs_clf_src, probs_clf_tar, False, thres_conf_quantile,
+                             thres_feat_sim, verbose, return_counts)
     dev = edge_index_added.device
     e0, e1 = edge_index_added[0], edge_index_added[1]
     ys, yt = data_src.y.to(dev), data_tar.y.to(dev)
     pred_s, pred_t = probs_clf_src.argmax(dim=1), probs_clf_tar.argmax(dim=1)
     e_sim = e_sim.reshape(-1).to(dev)
     rm = torch.zeros(edge_index_added.shape[1], dtype=torch.bool, device=dev)
+    counts = []
     thres = e_sim.quantile(q=thres_conf_quantile)                                  # :238
     rm |= e_sim < thres                                                            # :239
     _filter_report(verbose, "1. low SimNet confidence:", int(rm.sum()))
+    _count(counts, rm, return_counts)
     rm |= pred_s[e0] != ys[e0]                                                     # :243
+    _count(counts, rm, return_counts)
     rm |= (pred_t[e1] != yt[e1]) & data_tar.train_mask.to(dev)[e1]                 # :244
+    _count(counts, rm, return_counts)
     rm |= pred_s[e0] != pred_t[e1]                                                 # :248
+    _count(counts, rm, return_counts)
     cos = F.cosine_similarity(data_src.x.to(dev)[e0], data_tar.x.to(dev)[e1])      # :252
     rm |= cos < thres_feat_sim                                                     # :253
+    _count(counts, rm, return_counts)
     _filter_report(verbose, "[Done] removed", int(rm.sum()), "of", rm.numel())
-    return edge_index_added[:, ~rm]                                                # :257
+    out = edge_index_added[:, ~rm]                                                 # :257
+    return (out, counts) if return_counts else out
+
+
+def _count(counts, rm, wanted):
+    if wanted:
+        counts.append(int(rm.sum()))
 
 
 def check_added_edges_within_domain_validity(edge_index_added, e_sim, data_in, probs_clf, thres_conf_quantile=0.1,
-                                             thres_feat_sim=0.0, verbose=False):
-    """main_bridged_graph.py:123-161 (same remark about `e_sim` alignment)."""
+                                             thres_feat_sim=0.0, verbose=False, fused=False, return_counts=False):
+    """main_bridged_graph.py:123-161 (same remarks about `e_sim` alignment, `fused` and `return_counts`)."""
+    if fused:
+        return _fused_filter(edge_index_added, e_sim, data_in, data_in, probs_clf, probs_clf, True, thres_conf_quantile,
+                             thres_feat_sim, verbose, return_counts)
     dev = edge_index_added.device
     e0, e1 = edge_index_added[0], edge_index_added[1]
     y = data_in.y.to(dev)
     pred = probs_clf.argmax(dim=1)
     e_sim = e_sim.reshape(-1).to(dev)
     rm = torch.zeros(edge_index_added.shape[1], dtype=torch.bool, device=dev)
+    counts = []
     rm |= e_sim < e_sim.quantile(q=thres_conf_quantile)                            # :135-136
+    _count(counts, rm, return_counts)
     tm = data_in.train_mask.to(dev)[e1]
     rm |= (pred[e0] != y[e0]) & tm                                                 # :140
+    _count(counts, rm, return_counts)
     rm |= (pred[e1] != y[e1]) & tm                                                 # :141
+    _count(counts, rm, return_counts)
     rm |= pred[e0] != pred[e1]                                                     # :145
+    _count(counts, rm, return_counts)
     cos = F.cosine_similarity(data_in.x.to(dev)[e0], data_in.x.to(dev)[e1])        # :149
     rm |= cos < thres_feat_sim                                                     # :150
+    _count(counts, rm, return_counts)
     _filter_report(verbose, "[Done] removed", int(rm.sum()), "of", rm.numel())
-    return edge_index_added[:, ~rm]                                                # :154
+    out = edge_index_added[:, ~rm]                                                 # :154
+    return (out, counts) if return_counts else out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -528,26 +590,28 @@ def eval_homophily(data, second_order=False, verbose=False):
 
 def gen_bridged_graph(data_src, data_tar, model, k_cross=20, k_within=6, check_cross=False, check_within=False,
                       thres_conf_quantile=0.1, thres_feat_sim=0.8, mapper_idx_src=None, mapper_idx_tar=None,
-                      save_path=None, reference_filter_quirk=False, verbose=False):
+                      save_path=None, reference_filter_quirk=False, verbose=False, fused=False):
     """main_bridged_graph.py:267-321 after the model is loaded: top-k cross edges (+ filter), top-k within edges per
     domain (+ filter; the reference hard-codes quantile 0.1 / feature threshold 0.8 there, :302-306), merge, reorder,
-    save.  `reference_filter_quirk=True` feeds the filters the top-k-ordered similarity vector like the reference."""
+    save.  `reference_filter_quirk=True` feeds the filters the top-k-ordered similarity vector like the reference.
+    `fused=True` runs the filters as the HIP pass and hands them the [Nq, k] tables instead of `align_e_sim_to_edges`."""
+    def sim_of(ei, sim_mat, idx_mat):
+        if reference_filter_quirk:
+            return sim_mat.reshape(-1)
+        return (sim_mat, idx_mat) if fused else align_e_sim_to_edges(ei, sim_mat, idx_mat)
     z_src, z_tar = model.encode_source(data_src), model.encode_target(data_tar)
     ec, esim, eidx, pcs, pct = add_topk_sim_cross_domain_edges(data_src, data_tar, model, k=k_cross, z_src=z_src, z_tar=z_tar,
                                                                verbose=verbose)
     if check_cross:
-        es = esim.reshape(-1) if reference_filter_quirk else align_e_sim_to_edges(ec, esim, eidx)
-        ec = check_added_edges_cross_domain_validity(ec, es, data_src, data_tar, pcs, pct, thres_conf_quantile,
-                                                     thres_feat_sim, verbose)
+        ec = check_added_edges_cross_domain_validity(ec, sim_of(ec, esim, eidx), data_src, data_tar, pcs, pct, thres_conf_quantile,
+                                                     thres_feat_sim, verbose, fused=fused)
     e_s = e_t = None
     if k_within > 0:
         e_s, sim_s, idx_s = add_topk_sim_within_domain_edges(data_src, model, k=k_within, domain="source", z=z_src, verbose=verbose)
         e_t, sim_t, idx_t = add_topk_sim_within_domain_edges(data_tar, model, k=k_within, domain="target", z=z_tar, verbose=verbose)
         if check_within:
-            a = sim_s.reshape(-1) if reference_filter_quirk else align_e_sim_to_edges(e_s, sim_s, idx_s)
-            b = sim_t.reshape(-1) if reference_filter_quirk else align_e_sim_to_edges(e_t, sim_t, idx_t)
-            e_s = check_added_edges_within_domain_validity(e_s, a, data_src, pcs, 0.1, 0.8, verbose)
-            e_t = check_added_edges_within_domain_validity(e_t, b, data_tar, pct, 0.1, 0.8, verbose)
+            e_s = check_added_edges_within_domain_validity(e_s, sim_of(e_s, sim_s, idx_s), data_src, pcs, 0.1, 0.8, verbose, fused=fused)
+            e_t = check_added_edges_within_domain_validity(e_t, sim_of(e_t, sim_t, idx_t), data_tar, pct, 0.1, 0.8, verbose, fused=fused)
     merged = merge_graphs(data_src, data_tar, ec, e_s, e_t)
     if mapper_idx_src is not None:
         merged = reorder(merged, data_src, mapper_idx_src, mapper_idx_tar)

@@ -1243,3 +1243,80 @@ def step2_auc(score, y, sel):
     rc = L.lib().bgnn_step2_auc_count_f32(L.ptr(score), L.ptr(as_u8(pos)), N, L.ptr(keys), L.ptr(n_neg), L.ptr(out), L.stream())
     L.check(rc, "bgnn_step2_auc_count_f32")
     return out[0].double() / (2.0 * out[1].double() * n_neg[0].double())
+
+
+# ---- step 1's edge-validity filters (csrc/bgnn_edge_filter.hip) --------------------------------------------------------------------
+def quantile_f32(values, q):
+    """`torch.quantile(values, q)` (linear interpolation) of a 1-D fp32 tensor as a 0-dim fp32 tensor, by radix selection instead of
+    a sort: no 2^24 element limit (1 <= n <= 2^31 - 1), no host synchronisation, bitwise reproducible.  -0 and +0 are one value
+    (returned as +0).  NaN input is out of contract (torch returns NaN; this returns the order statistic of the bit patterns)."""
+    v = values.reshape(-1)
+    if v.dtype != torch.float32:
+        raise TypeError(f"quantile_f32 needs fp32 values (got {v.dtype})")
+    v = v.contiguous()
+    lib = L.lib()
+    out = torch.empty((), dtype=torch.float32, device=v.device)
+    wsb = lib.bgnn_quantile_workspace_bytes(v.shape[0])
+    ws = torch.empty(wsb // 8, dtype=torch.int64, device=v.device)
+    rc = lib.bgnn_quantile_f32(L.ptr(v), v.shape[0], float(q), L.ptr(out), L.ptr(ws), wsb, L.stream())
+    L.check(rc, "bgnn_quantile_f32")
+    return out
+
+
+def row_inv_norms(x, eps=1e-8):
+    """1 / max(||x_i||_2, eps) per row of a contiguous [N, F] fp32 table (the divisor of F.cosine_similarity), any F."""
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    rc = L.lib().bgnn_row_inv_norms_f32(L.ptr(x), x.shape[0], x.shape[1], float(eps), L.ptr(out), L.stream())
+    L.check(rc, "bgnn_row_inv_norms_f32")
+    return out
+
+
+def edge_validity(edge_index, nodes_from, nodes_to, within, thres_conf_quantile, thres_feat_sim, e_sim=None, idx_mat=None,
+                  e_sim_mat=None):
+    """The five removal rules of main_bridged_graph.py:123-161 (within=True) / :225-264 (within=False) over an edge list [2, E]
+    (int64; row 0 indexes `nodes_from`, row 1 `nodes_to`) without [E, F] or [E, k] temporaries.
+      nodes_from = (x [N, F] fp32, inv_norm [N] fp32, pred [N] int32, y [N] int32), nodes_to = the same plus train_mask [N] uint8;
+      similarity of an edge: `e_sim` [E] fp32 as given (the reference's top-k-ordered vector), or looked up in the top-k tables
+      `idx_mat` / `e_sim_mat` [n_to, k] the list was made from (a miss raises).
+    -> (flags [E] uint8: bit r-1 = removed by rule r (1 = similarity below its `thres_conf_quantile` quantile, 2 / 3 = a wrong
+    prediction at `from` / `to`, 4 = predictions differ, 5 = raw-feature cosine < thres_feat_sim), counts: the five cumulative
+    removal counts as Python ints (ONE device read), sim [E] fp32).  The list may be in any order; one sorted by row 0 (a coalesced
+    list) is gathered faster because neighbouring edges share a feature row."""
+    lib = L.lib()
+    ei = edge_index.contiguous()
+    if ei.dtype != torch.int64 or ei.dim() != 2 or ei.shape[0] != 2:
+        raise TypeError("edge_index must be int64 [2, E]")
+    E, dev = int(ei.shape[1]), ei.device
+    xa, inva, preda, ya = nodes_from
+    xb, invb, predb, yb, trainb = nodes_to
+    F = int(xa.shape[1])
+    if int(xb.shape[1]) != F:
+        raise ValueError(f"feature widths differ ({F} vs {int(xb.shape[1])})")
+    flags = torch.empty(E, dtype=torch.uint8, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    aligned = idx_mat is not None
+    if aligned:
+        idx_mat, e_sim_mat = idx_mat.contiguous(), e_sim_mat.contiguous()
+        if idx_mat.dtype != torch.int64 or e_sim_mat.dtype != torch.float32 or idx_mat.shape != e_sim_mat.shape or idx_mat.shape[0] != xb.shape[0]:
+            raise ValueError("idx_mat (int64) / e_sim_mat (fp32) must both be [n_to, k]")
+        sim = torch.empty(E, dtype=torch.float32, device=dev)
+    else:
+        sim = e_sim.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        if sim.shape[0] != E:
+            raise ValueError(f"e_sim has {sim.shape[0]} entries for {E} edges")
+    rc = lib.bgnn_edge_validity_f32(L.ptr(ei), E, L.ptr(xa), xa.shape[0], L.ptr(inva), L.ptr(preda), L.ptr(ya), L.ptr(xb), xb.shape[0],
+                                    L.ptr(invb), L.ptr(predb), L.ptr(yb), L.ptr(trainb), F, 1 if within else 0, float(thres_feat_sim),
+                                    L.ptr(idx_mat) if aligned else None, L.ptr(e_sim_mat) if aligned else None,
+                                    int(idx_mat.shape[1]) if aligned else 0, L.ptr(sim) if aligned else None, L.ptr(flags),
+                                    L.ptr(counts), L.stream())
+    L.check(rc, "bgnn_edge_validity_f32")
+    if E > 0:
+        thres = quantile_f32(sim, thres_conf_quantile)
+        rc = lib.bgnn_edge_rule1_counts_f32(L.ptr(sim), L.ptr(thres), E, L.ptr(flags), L.ptr(counts), L.stream())
+        L.check(rc, "bgnn_edge_rule1_counts_f32")
+    c = counts.tolist()
+    if c[6]:
+        raise RuntimeError(f"edge_validity: {c[6]} edges name a node outside the tables")
+    if c[5]:
+        raise RuntimeError(f"edge_validity: {c[5]} edges do not come from these top-k tables")
+    return flags, c[:5], sim

@@ -636,6 +636,36 @@ int bgnn_adam_step_f32(const void* records, int32_t n_tensors, const int32_t* ch
                        const double* lr_table, int64_t lr_len, double beta1, double beta2, double eps, double weight_decay,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Edge-validity filters of step 1    main_bridged_graph.py:123-161 (within a domain), :225-264 (across domains)
+ * quantile:   replaces `e_sim.quantile(q)` (:135, :238): torch.quantile's linear interpolation (the order statistics floor / ceil of
+ *             q (n - 1), then its lerp) by radix selection over the order-preserving uint32 image of the values, four histogram
+ *             passes, no sort.  1 <= n <= 2^31 - 1 (torch stops at 2^24); the position is formed in fp32 as torch forms it while
+ *             n - 1 <= 2^24 and in fp64 beyond.  -0 and +0 are one value, returned as +0.  NaN input is out of contract.  out:
+ *             one device float; no host synchronisation; two calls are bitwise equal.  ws: 8-byte aligned.
+ * inv_norms:  out[i] = 1 / max(|x_i|_2, eps) for a contiguous [N, F] table, any F (what F.cosine_similarity divides a row by,
+ *             :149, :252).
+ * validity:   replaces :140-150 / :243-253 and the [E, F] gathers of :149 / :252.  edge_index [2, E] int64 (row 0 = `from`, an index
+ *             into the *_from tables; row 1 = `to`, an index into the *_to tables; any order, a list sorted by row 0 is gathered
+ *             faster); per node: feature row, inverse norm, argmax class, label (-1 = none), and for `to` nodes the train mask.
+ *             within = 0: the cross-domain rules (:243-253), within = 1: the single-domain rules (:140-150; pass the same tables
+ *             twice).  flags [E]: bit 1 = wrong prediction at `from`, bit 2 = wrong prediction at `to`, bit 3 = predictions
+ *             differ, bit 4 = dot . inv_from . inv_to < thres_feat_sim (fp32).  idx_mat / e_sim_mat [n_to, k] (optional): the top-k
+ *             tables the list was made from; sim_out[e] = e_sim_mat[to, position of `from` in idx_mat[to]].  counts [8] int64 is
+ *             cleared; counts[5] = edges not found in idx_mat, counts[6] = edges with an index outside the tables (flagged, never
+ *             dereferenced).
+ * rule1:      replaces :136 / :239 and the prints of :138-152 / :241-255: flags[e] |= 1 where sim[e] < *thres (device scalar);
+ *             counts[r] += edges with any of bits 0..r set, r = 0..4.                                                           */
+size_t bgnn_quantile_workspace_bytes(int64_t n);
+int bgnn_quantile_f32(const float* values, int64_t n, double q, float* out, void* ws, size_t ws_bytes, void* stream);
+int bgnn_row_inv_norms_f32(const float* x, int64_t N, int32_t F, float eps, float* out, void* stream);
+int bgnn_edge_validity_f32(const int64_t* edge_index, int64_t E, const float* x_from, int64_t n_from, const float* inv_from,
+                           const int32_t* pred_from, const int32_t* y_from, const float* x_to, int64_t n_to, const float* inv_to,
+                           const int32_t* pred_to, const int32_t* y_to, const uint8_t* train_to, int32_t F, int within,
+                           float thres_feat_sim, const int64_t* idx_mat_opt, const float* e_sim_mat_opt, int32_t k,
+                           float* sim_out_opt, uint8_t* flags, long long* counts, void* stream);
+int bgnn_edge_rule1_counts_f32(const float* sim, const float* thres, int64_t E, uint8_t* flags, long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
