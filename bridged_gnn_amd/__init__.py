@@ -8,3 +8,11 @@ there is no CPU fallback: ops raise if the library or a GPU tensor is missing.
 from .data import Data, load_bridged_graph, save_bridged_graph  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the GCN baseline's classes, imported on first use (they pull in the HIP library's binding)
+    if name in ("GCNNet", "GCNConv"):
+        from . import gcn
+        return getattr(gcn, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

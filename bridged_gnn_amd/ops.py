@@ -9,7 +9,7 @@ from . import _lib as L
 
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
-           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "wide_heads_supported",
+           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "gcn_aggregate", "gcn_aggregate_bwd", "wide_heads_supported",
            "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd", "pair_csr", "pair_mlp_stats", "pair_mlp_loss",
            "pair_mlp_segsum", "pair_mlp_eval", "pair_mlp_count", "PAIR_MLP_WIDTH", "pair_cos_loss", "pair_cos_segsum", "pair_cos_count",
            "PAIR_COS_WIDTH"]
@@ -896,6 +896,69 @@ def sage_mean_aggregate_bwd(y, grad_y, rowptr, t_rowptr, t_col, n_src, D, epilog
         L.ptr_rows(grad_root), grad_root.stride(0), L.ptr(ws), ws.numel(), L.stream())
     L.check(rc, "bgnn_sage_mean_aggregate_bwd_f32")
     return grad_tbl, grad_root
+
+
+# rows with at least GCN_HUB_THRESHOLD edges are cut into segments of GCN_HUB_SEGMENT edges (bgnn_gcn_aggregate_f32): a row below
+# the threshold is at most 32 rounds of 8 gathers for its lane group
+GCN_HUB_THRESHOLD = 256
+GCN_HUB_SEGMENT = 128
+
+
+def _gcn_hub_args(hubs, D, dev):
+    """hubs: None or (threshold, hub_rows, hub_seg_ptr, seg_bounds) -> the hub arguments of the GCN entry points + the workspace"""
+    if hubs is None:
+        return (0, None, 0, None, None, 0, None, 0), None
+    thr, rows, seg_ptr, bounds = hubs
+    n_seg = int(bounds.shape[0]) // 2
+    wsb = int(L.lib().bgnn_gcn_aggregate_workspace_bytes(n_seg, int(D)))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    return (int(thr), L.ptr(rows), int(rows.shape[0]), L.ptr(seg_ptr), L.ptr(bounds), n_seg, L.ptr(ws), ws.numel()), ws
+
+
+def gcn_aggregate(tbl, rowptr, col, dinv, n_rows, D, bias=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, out=None,
+                  hubs=None):
+    """GCN normalised aggregation (models/backbones.py:246-300, bgnn.h: bgnn_gcn_aggregate_f32) -> out [n_rows, pad4(D)] (use
+    out[:, :D]): out[i] = epi(dinv[i] * sum_{t in row i} dinv[col[t]] * tbl[col[t]] + bias) over a CSR that holds one self loop per
+    row (`build_dst_csr(rewrite_self_loops=True)`) or its `transposed()` view; dinv float32 [>= max(n_rows, tbl rows)].
+    tbl / out: 2-D row-strided views with unit column stride; bias: float32 [>= D], 16-byte aligned, or None.  epilogue: None,
+    "relu" (then dropout at p_drop, the (seed, element index) hash of `sage_mean_aggregate`) or "log_softmax" (D <= 128).
+    hubs: None (every row is walked by one lane group) or (threshold, hub_rows, hub_seg_ptr, seg_bounds) from
+    `DstCSR.hub_tables(threshold, segment)` of the SAME view: those rows are summed segment by segment across the grid."""
+    n_rows, D = int(n_rows), int(D)
+    if out is None:
+        out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < D):
+        raise ValueError("bias must be float32 [>= D]")
+    if dinv.dtype != torch.float32 or dinv.dim() != 1:
+        raise ValueError("dinv must be float32 [N]")
+    hub_args, ws = _gcn_hub_args(hubs, D, tbl.device)
+    rc = L.lib().bgnn_gcn_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(bias), L.ptr(rowptr), L.ptr(col), L.ptr(dinv), int(dinv.shape[0]),
+        n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        L.ptr(seed_dev) if seed_dev is not None else None, *hub_args, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gcn_aggregate_f32")
+    return out
+
+
+def gcn_aggregate_bwd(y, grad_y, t_rowptr, t_col, dinv, n_src, D, epilogue=None, p_drop=0.0, want_bias=True, grad_tbl=None,
+                      hubs=None):
+    """Backward of `gcn_aggregate(tbl, rowptr, col, dinv, n_rows, D, bias, epilogue, p_drop)` -> (grad_tbl [n_src, pad4(D)],
+    grad_bias [D] | None).  y: the forward's output (unused without an epilogue, may be None); (t_rowptr, t_col): the view of the
+    same edges with the roles swapped, `hubs` that view's hub tables.  g (the gradient at the epilogue's input) comes from one row
+    pass, grad_bias = its fixed-order column sums (`column_sums`), grad_tbl[j] = dinv[j] * sum_{i : j -> i} dinv[i] * g[i] from the
+    forward walk over the swapped view.  No atomics: bit-identical from run to run."""
+    n_rows, n_src, D = int(grad_y.shape[0]), int(n_src), int(D)
+    dev = grad_y.device
+    if grad_tbl is None:
+        grad_tbl = torch.empty(n_src, pad4(D), dtype=torch.float32, device=dev)
+    g = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=dev)
+    hub_args, ws = _gcn_hub_args(hubs, D, dev)
+    rc = L.lib().bgnn_gcn_aggregate_bwd_f32(
+        L.ptr_rows(y), y.stride(0) if y is not None else 0, L.ptr_rows(grad_y), grad_y.stride(0), n_rows, L.ptr(t_rowptr),
+        L.ptr(t_col), L.ptr(dinv), int(dinv.shape[0]), n_src, D, SAGE_EPILOGUES[epilogue], float(p_drop), *hub_args,
+        L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.stream())
+    L.check(rc, "bgnn_gcn_aggregate_bwd_f32")
+    return grad_tbl, (column_sums(g)[:D] if want_bias else None)
 
 
 def rows_segment_add(src, seg_ptr, idx, row, dst, D=None, accumulate=True):

@@ -601,14 +601,16 @@ def test_noDTC(data, model, gnn=None, metric='f1', f1_average='macro'):
 def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gnn='GCN', seed=None, num_layer=2, hidden=64,
                     lr=1e-3, wd=5e-3, use_scheduler=True, step=1, step_size=100, gamma=0.1, metric='f1', f1_average='macro',
                     dropout=0.5, verbose=True, ckpt_dir='../ckpt', history=None, graphed=False):
-    """main_graph_knowledge_transfer.py:302-396 for `gnn='GraphSAGE'` (what `main` passes under --no_dtc): `sage.GraphSAGE`,
-    Adam(lr, wd), optional StepLR, best epoch by the lowest `loss_train` (:374); `save=True` writes
+    """main_graph_knowledge_transfer.py:302-396 for `gnn='GraphSAGE'` (what `main` passes under --no_dtc: `sage.GraphSAGE`) and
+    `gnn='GCN'` (the function's own default: `gcn.GCNNet`), Adam(lr, wd), optional StepLR, best epoch by the lowest `loss_train` (:374); `save=True` writes
     {ckpt_dir}/model_{gnn}_{args.dataset_name}_share_best.ckpt.  Returns None like the reference; `history` (a dict) receives
     'loss_train', 'eval_res', 'best_epoch', 'best_acc', 'final_acc'.  `graphed=True`: as in `train_gnn`."""
-    if gnn != 'GraphSAGE':
-        if gnn in ('MLP', 'GCN', 'GAT', 'GATv2', 'KTGNN'):
-            raise NotImplementedError(f"train_gnn_noDTC(gnn={gnn!r}): only the GraphSAGE backbone (the one `main` uses) is implemented")
+    if gnn not in ('GraphSAGE', 'GCN'):
+        if gnn in ('MLP', 'GAT', 'GATv2', 'KTGNN'):
+            raise NotImplementedError(f"train_gnn_noDTC(gnn={gnn!r}): the baselines implemented are GraphSAGE (the one `main` uses) "
+                                      "and GCN; MLP, GAT, GATv2 and KTGNN without DTC are not")
         raise NotImplementedError('Not Implemented Model:{}'.format(gnn))
+    from .gcn import GCNNet
     from .sage import GraphSAGE
     dev = _device_of(args)
     with torch.cuda.device(dev):
@@ -628,7 +630,10 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
             data_split_seed = 0
             model_init_seed = train_id - 1 if seed is None else seed
             set_random_seed(model_init_seed)
-            model = GraphSAGE(dataset, num_layer, hidden, root_weight=True, dropout=dropout).to(dev)
+            if gnn == 'GCN':
+                model = GCNNet(dataset, num_layer, hidden=hidden, dropout=dropout).to(dev)
+            else:
+                model = GraphSAGE(dataset, num_layer, hidden, root_weight=True, dropout=dropout).to(dev)
             _prime(model, data, lambda lp: ops.step2_nll(lp, plan.y, plan.train_u8))
             _say(verbose, data)
             _say(verbose, model)
@@ -700,11 +705,13 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
 _FLAGS = {
     "gpu": (int, 0, None, "index of the GPU to run on"),
     "dataset_name": (str, "twitter_unrelational", None, "name used in log lines and checkpoint files"),
-    "model_name": (str, "KTGNN", ("MLP", "GCN", "GAT", "GATv2", "GraphSAGE", "KTGNN"), "backbone (only KTGNN trains; see train_gnn)"),
+    "model_name": (str, "KTGNN", ("MLP", "GCN", "GAT", "GATv2", "GraphSAGE", "KTGNN"), "backbone (only KTGNN trains here; the baselines run under --no_dtc --baseline)"),
     "eval_metric": (str, "f1", ("f1", "auc"), "score reported per epoch"),
     "save": (None, False, None, "write the best epoch's parameters"),
     "to_undirected": (None, False, None, "add every edge's reverse before training"),
-    "no_dtc": (None, False, None, "train GraphSAGE on the bridged graph instead of KTGNN"),
+    "no_dtc": (None, False, None, "train a plain backbone (see --baseline) on the bridged graph instead of KTGNN"),
+    "baseline": (str, "GraphSAGE", ("GraphSAGE", "GCN"), "the backbone --no_dtc trains (this package's own flag: the reference always "
+                 "trains GraphSAGE there and ignores --model_name)"),
     "graphed": (None, False, None, "run every epoch as one replay of a captured HIP graph (the same run, launch cost paid once)"),
     "num_layer": (int, 2, None, None),
     "num_epoch": (int, 300, None, None),
@@ -742,7 +749,7 @@ def main(args=None, verbose=True):
         if args.to_undirected:
             data.to_undirected_()
         if args.no_dtc:
-            return train_gnn_noDTC(args, dataset, data, save=False, repeat=1, num_epoch=args.num_epoch, gnn='GraphSAGE', seed=0,
+            return train_gnn_noDTC(args, dataset, data, save=False, repeat=1, num_epoch=args.num_epoch, gnn=getattr(args, "baseline", "GraphSAGE"), seed=0,
                                    num_layer=args.num_layer, hidden=args.hidden_dim, lr=1e-3, wd=5e-3, use_scheduler=False, step=1,
                                    step_size=step_size, gamma=gamma, metric=args.eval_metric, f1_average='macro', verbose=verbose,
                                    graphed=getattr(args, "graphed", False))

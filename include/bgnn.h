@@ -32,7 +32,8 @@ extern "C" {
  * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32, and for the
  * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size, and for the cosine
  * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
- * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size. */
+ * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size, and for the GCN baseline's
+ * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -454,6 +455,44 @@ int bgnn_sage_mean_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_t
 int bgnn_rows_segment_add_f32(const float* src, int64_t lds, int64_t n_src, const int32_t* seg_ptr, const int32_t* idx,
                               const int32_t* row, int64_t n_seg, int32_t D, int accumulate, float* dst, int64_t ldd, int64_t n_dst,
                               void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GCN normalised aggregation (the `gnn='GCN'` baseline of main_graph_knowledge_transfer.py:302):
+ *     models/backbones.py:246-300 -- PyG GCNConv: gcn_norm(add_self_loops=True, improved=False) with unit edge weights,
+ *     propagate(aggr='add'), + bias; F.relu + F.dropout(p=0.5) between convs (:274-275) and F.log_softmax (:277).
+ * The caller transforms first (tbl = x W^T, width D = the conv's output width) and hands a by-destination CSR that already
+ * holds exactly one self loop per row (bgnn_build_dst_csr with rewrite_self_loops: add_remaining_self_loops leaves one loop of
+ * weight 1 per node however many the input had; duplicate non-loop edges count with their multiplicity, in the sum and in deg):
+ *   dinv[i] = 1 / sqrt(rowptr[i+1] - rowptr[i])
+ *   out[i]  = epi( dinv[i] * sum_{t in [rowptr[i], rowptr[i+1])} dinv[col[t]] * tbl[col[t]] + bias )
+ * dinv [n_dinv >= max(n_rows, n_tbl)] is built once per graph by the caller and gathered per edge.  bias_opt: one row of D
+ * floats (16-B aligned) or NULL.  Epilogues, strides, padding, alignment and the dropout hash are those of
+ * bgnn_sage_mean_aggregate_f32 (0 none; 1 ReLU then dropout over element index row * D + column with seed / seed_dev_opt;
+ * 2 row log_softmax at D <= 128).  D > 128 runs as 128-column slices (epilogue 2 then returns BGNN_E_SHAPE).
+ * Hub rows: with n_hubs > 0 the rows listed in hub_rows (exactly the rows of at least hub_threshold edges) are cut into n_seg
+ * segments -- hub_seg_ptr [n_hubs+1] indexes a hub's segments, seg_bounds [2 n_seg] holds each segment's (begin, end) offsets
+ * into col (`DstCSR.hub_tables`).  One lane group sums a segment into a partial row of ws
+ * (bgnn_gcn_aggregate_workspace_bytes(n_seg, D)), then one group per hub adds its partial rows in segment order and applies
+ * scale, bias and epilogue: three launches instead of one, and no row is walked by a single group.  n_hubs == 0: one launch.
+ * bgnn_gcn_aggregate_bwd_f32: the atomic-free backward.  A row pass writes g [n_rows, ldg] from the forward's output y and
+ * grad_y (g = grad_y; (y > 0 ? grad_y / (1 - p_drop) : 0); grad_y - exp(y) * rowsum(grad_y)); the caller takes grad_bias as the
+ * column sums of g.  By symmetry of the normalisation grad_tbl[j] = dinv[j] * sum_{i : j -> i} dinv[i] * g[i]: the forward
+ * walk without bias or epilogue over the by-source view (t_rowptr [n_src+1], t_col = destinations, self loops included; the
+ * hub tables are those of that view).  Deterministic bits. */
+size_t bgnn_gcn_aggregate_workspace_bytes(int64_t n_seg, int32_t D);
+int bgnn_gcn_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias_opt, const int32_t* rowptr,
+                           const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D,
+                           int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                           int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                           const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                           void* ws_opt, size_t ws_bytes, float* out, int64_t ldo, void* stream);
+int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows,
+                               const int32_t* t_rowptr, const int32_t* t_col, const float* dinv, int64_t n_dinv,
+                               int64_t n_src, int32_t D, int epilogue, float p_drop,
+                               int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                               const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                               void* ws_opt, size_t ws_bytes, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
