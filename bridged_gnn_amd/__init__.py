@@ -15,4 +15,7 @@ def __getattr__(name):
     if name in ("GCNNet", "GCNConv"):
         from . import gcn
         return getattr(gcn, name)
+    if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
+        from . import dist_gcn
+        return getattr(dist_gcn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -107,6 +107,8 @@ SIGNATURES = {
     "bgnn_gcn_aggregate_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_gcn_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P,
                                        _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _I64, _P]),
+    "bgnn_gcn_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P,
+                                            _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _I64, _P]),
     "bgnn_gcn_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I32, _INT, _F32,
                                            _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _I64, _P, _I64, _P]),
     "bgnn_step2_loss_workspace_bytes": (_SZ, [_I64, _I32]),

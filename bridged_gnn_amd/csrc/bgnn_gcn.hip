@@ -19,6 +19,10 @@
 // (an explicit (begin, end) pair of edge offsets) into a partial row of the workspace, FINISH mode adds a hub's partial rows
 // in segment order, scales by dinv_i, adds the bias and applies the epilogue.  One group per segment: a hub is spread over
 // the whole grid, its bits do not depend on which block took which segment.
+//
+// Rows of a larger graph (bgnn_gcn_aggregate_rows_f32, a rank's rows of a node partition): ROW_ID kernels draw the dropout mask
+// of output row io for row_id[io], its GLOBAL row, in the row kernel and in a hub's FINISH group alike; the id is loaded once per
+// row after the gather loop.  Without ids (or without dropout) the kernels launched are the ones without the template flag.
 #include "bgnn_common.h"
 
 namespace {
@@ -40,6 +44,7 @@ struct GcnParams {
   float* out; int64_t ldo;
   uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_dev;
   int32_t d_full; int32_t c0;
+  const int64_t* row_id;                           // ROW_ID: dropout row of output row io (element index row_id[io] * d_full + col)
 };
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -51,7 +56,7 @@ __device__ __forceinline__ uint32_t drop_bits(uint64_t e, uint64_t seed) {
   return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
 }
 
-template <int LF, int EP, int U, int EPI, int MODE>
+template <int LF, int EP, int U, int EPI, int MODE, bool ROW_ID = false>
 __global__ __launch_bounds__(256) void gcn_agg_kernel(GcnParams p) {
   constexpr int GL = LF * EP;            // lanes per output row
   constexpr int GPW = 64 / GL;           // rows per wave
@@ -137,7 +142,9 @@ __global__ __launch_bounds__(256) void gcn_agg_kernel(GcnParams p) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] = fmaxf(o[c], 0.f);
       if (p.thr != 0u) {
-        const uint64_t e = (uint64_t)(ovalid ? io : 0) * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
+        // the row the mask is drawn for: one 8-byte load per group after the gather loop (a hub's finish group reads its hub's)
+        const int64_t ih = ovalid ? (ROW_ID ? p.row_id[io] : io) : 0;
+        const uint64_t e = (uint64_t)ih * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
         if ((p.d_full & 3) == 0) {                              // the four columns share one word pair (as bgnn_norm.hip)
           uint32_t w0, w1;
           drop_words(e >> 2, seed, w0, w1);
@@ -227,14 +234,14 @@ __global__ __launch_bounds__(256) void gcn_bwd_rows_kernel(RowParams p) {
   }
 }
 
-template <int LF, int EP, int U, int EPI, int MODE>
+template <int LF, int EP, int U, int EPI, int MODE, bool ROW_ID>
 int launch_agg(const GcnParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
   static const int cap = [] {
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gcn_agg_kernel<LF, EP, U, EPI, MODE>, 256, 0) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gcn_agg_kernel<LF, EP, U, EPI, MODE, ROW_ID>, 256, 0) != hipSuccess || per_cu < 1)
       return 2048;
     if (per_cu > 8) per_cu = 8;
     return per_cu * prop.multiProcessorCount / 8 * 8;
@@ -242,24 +249,26 @@ int launch_agg(const GcnParams& p, hipStream_t st) {
   const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
   int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;   // multiple of 8 (XCD split)
   if (grid < 8) grid = 8;
-  hipLaunchKernelGGL((gcn_agg_kernel<LF, EP, U, EPI, MODE>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((gcn_agg_kernel<LF, EP, U, EPI, MODE, ROW_ID>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
 
-template <int EPI, int MODE>
+template <int EPI, int MODE, bool ROW_ID = false>
 int dispatch_agg(const GcnParams& p, hipStream_t st) {
   const int nv = (p.D + 3) / 4;   // float4 slots of the slice
-  if (nv <= 1) return launch_agg<1, 8, 4, EPI, MODE>(p, st);
-  if (nv <= 2) return launch_agg<2, 4, 4, EPI, MODE>(p, st);
-  if (nv <= 4) return launch_agg<4, 2, 4, EPI, MODE>(p, st);
-  if (nv <= 8) return launch_agg<8, 1, 8, EPI, MODE>(p, st);
-  if (nv <= 16) return launch_agg<16, 1, 8, EPI, MODE>(p, st);
-  return launch_agg<32, 1, 8, EPI, MODE>(p, st);
+  if (nv <= 1) return launch_agg<1, 8, 4, EPI, MODE, ROW_ID>(p, st);
+  if (nv <= 2) return launch_agg<2, 4, 4, EPI, MODE, ROW_ID>(p, st);
+  if (nv <= 4) return launch_agg<4, 2, 4, EPI, MODE, ROW_ID>(p, st);
+  if (nv <= 8) return launch_agg<8, 1, 8, EPI, MODE, ROW_ID>(p, st);
+  if (nv <= 16) return launch_agg<16, 1, 8, EPI, MODE, ROW_ID>(p, st);
+  return launch_agg<32, 1, 8, EPI, MODE, ROW_ID>(p, st);
 }
 
 template <int MODE>
 int dispatch_epi(int epilogue, const GcnParams& p, hipStream_t st) {
+  // the row-id variant exists only where a mask is drawn; every other call runs the kernels it always ran
+  if (epilogue == EPI_RELU && p.row_id != nullptr && p.thr != 0u) return dispatch_agg<EPI_RELU, MODE, true>(p, st);
   return epilogue == EPI_RELU ? dispatch_agg<EPI_RELU, MODE>(p, st)
        : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX, MODE>(p, st) : dispatch_agg<EPI_NONE, MODE>(p, st);
 }
@@ -293,7 +302,8 @@ int64_t part_ld(int32_t D) { return D < SLICE ? ((int64_t)D + 3) / 4 * 4 : SLICE
 int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias, const int32_t* rowptr, const int32_t* col,
              const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D, int epilogue, float p_drop, uint64_t seed,
              const uint64_t* seed_dev, int32_t hub_threshold, const int32_t* hub_rows, int64_t n_hubs, const int32_t* hub_seg_ptr,
-             const int32_t* seg_bounds, int64_t n_seg, void* ws, size_t ws_bytes, float* out, int64_t ldo, hipStream_t st) {
+             const int32_t* seg_bounds, int64_t n_seg, void* ws, size_t ws_bytes, float* out, int64_t ldo, hipStream_t st,
+             const int64_t* row_id = nullptr) {
   if (!tbl || !rowptr || !col || !dinv || !out) return BGNN_E_NULL;
   if (n_rows < 0 || n_tbl < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
   if (n_dinv < n_rows || n_dinv < n_tbl) return BGNN_E_SHAPE;
@@ -322,6 +332,7 @@ int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias, co
     p.out = out + c0; p.ldo = ldo;
     drop_consts(p_drop, p.thr, p.keep_scale);
     p.seed = seed; p.seed_dev = seed_dev; p.d_full = D; p.c0 = c0;
+    p.row_id = row_id;                       // [n_rows]: the row kernel reads row_id[i], a hub's finish group row_id[hub_rows[h]]
     int rc = dispatch_epi<MODE_ROWS>(epilogue, p, st);
     if (rc != 0) return rc;
     if (hubs) {
@@ -356,6 +367,18 @@ extern "C" int bgnn_gcn_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_t
   return agg_impl(tbl, ldt, n_tbl, bias_opt, rowptr, col, dinv, n_dinv, n_rows, D, epilogue, p_drop, seed, seed_dev_opt,
                   hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, out, ldo,
                   (hipStream_t)stream);
+}
+
+extern "C" int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias_opt, const int32_t* rowptr,
+                                           const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D,
+                                           int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                           int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                                           const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                                           void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo,
+                                           void* stream) {
+  return agg_impl(tbl, ldt, n_tbl, bias_opt, rowptr, col, dinv, n_dinv, n_rows, D, epilogue, p_drop, seed, seed_dev_opt,
+                  hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, out, ldo,
+                  (hipStream_t)stream, row_id_opt);
 }
 
 extern "C" int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows,

@@ -37,9 +37,9 @@ class SagePartition:
         seg_ptr, seg_idx, seg_row     segment CSR of the send list for the gradient return: segment s collects the send
                                       entries seg_idx[seg_ptr[s]:seg_ptr[s+1]] (ascending) of the owned row seg_row[s]"""
 
-    def __init__(self, edge_index, num_nodes, rank, world, owner=None):
+    def __init__(self, edge_index, num_nodes, rank, world, owner=None, rewrite_self_loops=False):
         N = int(num_nodes)
-        plan = PartitionPlan(edge_index, np.ones(N, dtype=bool), rank, world, owner=owner, rewrite_self_loops=False)
+        plan = PartitionPlan(edge_index, np.ones(N, dtype=bool), rank, world, owner=owner, rewrite_self_loops=rewrite_self_loops)
         assert plan.n_halo_by_table[1] == 0 and (plan.halo_ext_perm == np.arange(plan.n_halo)).all()
         self.plan, self.rank, self.world, self.N = plan, rank, world, N
         self.owned_global = plan.owned_global.astype(np.int64)
@@ -70,7 +70,7 @@ class _Layer:
         self.rowptr = t(part.rowptr)
         self.rowptr_local = self.rowptr[:part.n_local + 1]
         self.col = t(part.col) if part.num_edges else torch.zeros(1, dtype=torch.int32, device=device)
-        csr = ops.DstCSR(self.rowptr, self.col, None, part.num_edges, part.n_ext)
+        self.csr = csr = ops.DstCSR(self.rowptr, self.col, None, part.num_edges, part.n_ext)
         self.t_rowptr, _, self.t_dst = csr.transposed()
         if self.t_dst.numel() == 0:
             self.t_dst = torch.zeros(1, dtype=torch.int32, device=device)
@@ -154,7 +154,50 @@ class _PartSageLayerFn(torch.autograd.Function):
         return gx, gw_l, gb_l, gw_r, None, None, None, None, None
 
 
-class PartitionedGraphSAGE:
+class _RankModel:
+    """what the partitioned baselines share: the resident input halo, the loss share and the gradient all-reduce.  A subclass sets
+    model, part, tables (send_rows), comm and `_x_ext = None`."""
+
+    def _input_ext(self, x_local):
+        """[x own rows ; x halo rows] for the current version of the input features: the halo is fetched on first use and again
+        whenever x_local is another tensor object or was written in place"""
+        key = (x_local._version, tuple(x_local.shape), x_local.data_ptr())
+        if self._x_ext is None or self._x_ext[0] is not x_local or self._x_ext[1] != key:
+            xf = x_local.detach().float().contiguous()
+            if self.part.n_halo or self.comm.live:
+                send = xf.index_select(0, self.tables.send_rows)
+                halo = self.comm.all_to_all(send, self.part.send_splits, self.part.recv_splits)
+                ext = torch.cat((xf, halo)).contiguous()
+            else:
+                ext = xf
+            self._x_ext = (x_local, key, ext)
+        return self._x_ext[2]
+
+    def invalidate_input_cache(self):
+        """forget the resident input halo (after a write to x that does not advance its version)"""
+        self._x_ext = None
+
+    def nll_loss(self, out, y_local, train_mask_local):
+        """this rank's share of F.nll_loss(logp[train_mask], y[train_mask]): the owned training rows' terms over the GLOBAL count"""
+        tm = train_mask_local.bool()
+        cnt = self.comm.all_reduce(tm.sum().reshape(1).double()).float().clamp_min(1)
+        yi = y_local.clamp_min(0)[:, None]
+        return -(out.gather(1, yi).squeeze(1) * tm.float()).sum() / cnt[0]
+
+    def sync_grads(self):
+        """sum the parameter gradients over the ranks: ONE all-reduce of one flat bucket"""
+        ps = [p for p in self.model.parameters() if p.grad is not None]
+        if not ps or not self.comm.live:
+            return
+        flat = self.comm.all_reduce(torch.cat([p.grad.reshape(-1) for p in ps]))
+        o = 0
+        for p in ps:
+            n = p.grad.numel()
+            p.grad.copy_(flat[o:o + n].view_as(p.grad))
+            o += n
+
+
+class PartitionedGraphSAGE(_RankModel):
     """`sage.GraphSAGE` on rank `rank`'s rows of a destination-node partition (see the module docstring).
 
         ps = PartitionedGraphSAGE(model, edge_index, num_nodes, rank, world, device)
@@ -180,25 +223,6 @@ class PartitionedGraphSAGE:
                 raise NotImplementedError("PartitionedGraphSAGE: normalize=True is not supported")
         if model.convs[-1].out_channels > 128:
             raise NotImplementedError("PartitionedGraphSAGE: the fused log_softmax needs <= 128 classes")
-
-    def _input_ext(self, x_local):
-        """[x own rows ; x halo rows] for the current version of the input features: the halo is fetched on first use and again
-        whenever x_local is another tensor object or was written in place"""
-        key = (x_local._version, tuple(x_local.shape), x_local.data_ptr())
-        if self._x_ext is None or self._x_ext[0] is not x_local or self._x_ext[1] != key:
-            xf = x_local.detach().float().contiguous()
-            if self.part.n_halo or self.comm.live:
-                send = xf.index_select(0, self.tables.send_rows)
-                halo = self.comm.all_to_all(send, self.part.send_splits, self.part.recv_splits)
-                ext = torch.cat((xf, halo)).contiguous()
-            else:
-                ext = xf
-            self._x_ext = (x_local, key, ext)
-        return self._x_ext[2]
-
-    def invalidate_input_cache(self):
-        """forget the resident input halo (after a write to x that does not advance its version)"""
-        self._x_ext = None
 
     def forward(self, x_local):
         """x_local [n_local, F] (the rows of owned_global) -> log-probabilities [n_local, C] of the owned rows.  Training mode:
@@ -231,22 +255,3 @@ class PartitionedGraphSAGE:
 
     def get_logits(self, *args, **kwargs):
         raise NotImplementedError("PartitionedGraphSAGE.get_logits: out-neighbour averaging needs a source partition")
-
-    def nll_loss(self, out, y_local, train_mask_local):
-        """this rank's share of F.nll_loss(logp[train_mask], y[train_mask]): the owned training rows' terms over the GLOBAL count"""
-        tm = train_mask_local.bool()
-        cnt = self.comm.all_reduce(tm.sum().reshape(1).double()).float().clamp_min(1)
-        yi = y_local.clamp_min(0)[:, None]
-        return -(out.gather(1, yi).squeeze(1) * tm.float()).sum() / cnt[0]
-
-    def sync_grads(self):
-        """sum the parameter gradients over the ranks: ONE all-reduce of one flat bucket"""
-        ps = [p for p in self.model.parameters() if p.grad is not None]
-        if not ps or not self.comm.live:
-            return
-        flat = self.comm.all_reduce(torch.cat([p.grad.reshape(-1) for p in ps]))
-        o = 0
-        for p in ps:
-            n = p.grad.numel()
-            p.grad.copy_(flat[o:o + n].view_as(p.grad))
-            o += n

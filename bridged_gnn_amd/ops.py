@@ -916,14 +916,16 @@ def _gcn_hub_args(hubs, D, dev):
 
 
 def gcn_aggregate(tbl, rowptr, col, dinv, n_rows, D, bias=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, out=None,
-                  hubs=None):
+                  hubs=None, row_ids=None):
     """GCN normalised aggregation (models/backbones.py:246-300, bgnn.h: bgnn_gcn_aggregate_f32) -> out [n_rows, pad4(D)] (use
     out[:, :D]): out[i] = epi(dinv[i] * sum_{t in row i} dinv[col[t]] * tbl[col[t]] + bias) over a CSR that holds one self loop per
     row (`build_dst_csr(rewrite_self_loops=True)`) or its `transposed()` view; dinv float32 [>= max(n_rows, tbl rows)].
     tbl / out: 2-D row-strided views with unit column stride; bias: float32 [>= D], 16-byte aligned, or None.  epilogue: None,
     "relu" (then dropout at p_drop, the (seed, element index) hash of `sage_mean_aggregate`) or "log_softmax" (D <= 128).
     hubs: None (every row is walked by one lane group) or (threshold, hub_rows, hub_seg_ptr, seg_bounds) from
-    `DstCSR.hub_tables(threshold, segment)` of the SAME view: those rows are summed segment by segment across the grid."""
+    `DstCSR.hub_tables(threshold, segment)` of the SAME view: those rows are summed segment by segment across the grid.
+    row_ids: int64 [n_rows], the GLOBAL row id of every output row (a rank's rows of a partition): the dropout element index is
+    then row_ids[i] * D + column, the masks of the whole-graph call (bgnn_gcn_aggregate_rows_f32); None = row i itself."""
     n_rows, D = int(n_rows), int(D)
     if out is None:
         out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
@@ -932,11 +934,16 @@ def gcn_aggregate(tbl, rowptr, col, dinv, n_rows, D, bias=None, epilogue=None, p
     if dinv.dtype != torch.float32 or dinv.dim() != 1:
         raise ValueError("dinv must be float32 [N]")
     hub_args, ws = _gcn_hub_args(hubs, D, tbl.device)
-    rc = L.lib().bgnn_gcn_aggregate_f32(
-        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(bias), L.ptr(rowptr), L.ptr(col), L.ptr(dinv), int(dinv.shape[0]),
-        n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
-        L.ptr(seed_dev) if seed_dev is not None else None, *hub_args, L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_gcn_aggregate_f32")
+    args = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(bias), L.ptr(rowptr), L.ptr(col), L.ptr(dinv),
+            int(dinv.shape[0]), n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            L.ptr(seed_dev) if seed_dev is not None else None, *hub_args)
+    if row_ids is None:
+        rc = L.lib().bgnn_gcn_aggregate_f32(*args, L.ptr_rows(out), out.stride(0), L.stream())
+        L.check(rc, "bgnn_gcn_aggregate_f32")
+        return out
+    assert row_ids.dtype == torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n_rows and row_ids.is_contiguous()
+    rc = L.lib().bgnn_gcn_aggregate_rows_f32(*args, L.ptr(row_ids), L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gcn_aggregate_rows_f32")
     return out
 
 

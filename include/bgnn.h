@@ -33,7 +33,8 @@ extern "C" {
  * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size, and for the cosine
  * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
  * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size, and for the GCN baseline's
- * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size. */
+ * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for partitioned GCN's
+ * bgnn_gcn_aggregate_rows_f32. */
 #define BGNN_VERSION 113
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -493,6 +494,19 @@ int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y,
                                const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
                                void* ws_opt, size_t ws_bytes, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
                                void* stream);
+/* bgnn_gcn_aggregate_rows_f32: bgnn_gcn_aggregate_f32 for a block of rows of a larger graph (a rank's rows of a destination-node
+ * partition; tbl and dinv then cover the rank's own rows followed by its halo rows).  row_id_opt [n_rows] (int64) gives every
+ * output row its GLOBAL row id; the dropout element index is then row_id[i] * D + column, so a rank draws exactly the masks of the
+ * whole-graph call -- in the one-launch row kernel, in the finish pass of a hub row (row_id[hub_rows[h]]) and in every 128-column
+ * slice at D > 128.  With row_id_opt NULL (or no dropout) this is bgnn_gcn_aggregate_f32, bit for bit and kernel for kernel.
+ * Everything else as there.  The backward needs no counterpart: bgnn_gcn_aggregate_bwd_f32 recovers the mask from y > 0 and takes
+ * n_rows (rows of g) and n_src (rows of grad_tbl) separately. */
+int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias_opt, const int32_t* rowptr,
+                                const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D,
+                                int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                                const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                                void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
