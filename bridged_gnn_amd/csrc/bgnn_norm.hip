@@ -4,6 +4,9 @@
 //   backward: reduce (sum g', sum g'.xhat)              ->  apply (dx)
 // Nothing but x is kept for the backward: the ReLU state is re-derived from x and the dropout mask from the
 // counter-based hash of (seed, element index).  HBM-bound: 4 B/element read per reduction, 8-12 B/element per apply.
+// The same four phases are callable one by one (bgnn_bn_colstats_f32 and the three *_rows entries) for a node partition: a rank
+// reduces its rows, the partial sums are all-reduced between the launches, and the apply passes take the totals over ALL ranks'
+// rows, the global row count and the GLOBAL number of every local row, so that a rank's mask is its rows of the whole-graph mask.
 #include "bgnn_common.h"
 
 namespace {
@@ -23,6 +26,9 @@ struct NormParams {
   float momentum; float* running_mean; float* running_var;   // updated by block 0 when non-null
   const float* gy; int64_t ldg; double* gsum;                 // backward: [2 * D]: sum g' | sum g'.xhat
   float* gx; int64_t ldgx;
+  // the *_rows entries (kernels instantiated with SPLIT): `stats` / `gsum` read as plain [2 * D] totals over n_total rows of all ranks;
+  // local row r is row (row_ids ? row_ids[r] : row_base + r) of the whole activation for the dropout counter
+  int64_t n_total; const int64_t* row_ids; int64_t row_base;
 };
 
 // threads of a block: LPR = D/4 lanes per row (one float4 each), NT / LPR rows per pass
@@ -72,6 +78,25 @@ __device__ __forceinline__ void block_totals(const double* acc, int D, double* t
   __syncthreads();
 }
 
+// what differs between the fused entries and the split-phase (*_rows) ones: where the totals come from, the row count they are
+// divided by, and the row the dropout counter is built from
+template <bool SPLIT>
+__device__ __forceinline__ void load_totals(const double* acc, int D, double* tot /*LDS [2*D]*/) {
+  if constexpr (SPLIT) {
+    for (int t = threadIdx.x; t < 2 * D; t += NT) tot[t] = acc[t];
+    __syncthreads();
+  } else {
+    block_totals(acc, D, tot);
+  }
+}
+template <bool SPLIT>
+__device__ __forceinline__ int64_t stat_rows(const NormParams& p) { return SPLIT ? p.n_total : p.N; }
+template <bool SPLIT>
+__device__ __forceinline__ uint64_t counter_row(const NormParams& p, int64_t r) {
+  if constexpr (SPLIT) return (uint64_t)(p.row_ids != nullptr ? p.row_ids[r] : p.row_base + r);
+  return (uint64_t)r;
+}
+
 __global__ __launch_bounds__(NT) void colstats_kernel(NormParams p) {
   const Lay l = lay_of(p.D);
   double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -87,12 +112,12 @@ __global__ __launch_bounds__(NT) void colstats_kernel(NormParams p) {
 }
 
 // batch mean / biased variance of this lane's 4 columns (fp64 from the sums), as fp32 mean and 1/sqrt(var + eps)
-__device__ __forceinline__ void col_consts(const NormParams& p, const double* st /*totals [2*D]*/, int cg, float mean[4], float rstd[4], float ga[4], float be[4]) {
+__device__ __forceinline__ void col_consts(const NormParams& p, int64_t n, const double* st /*totals [2*D]*/, int cg, float mean[4], float rstd[4], float ga[4], float be[4]) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int c = 4 * cg + e;
-    const double m = st[c] / (double)p.N;
-    double var = st[p.D + c] / (double)p.N - m * m;
+    const double m = st[c] / (double)n;
+    double var = st[p.D + c] / (double)n - m * m;
     var = var > 0.0 ? var : 0.0;
     mean[e] = (float)m;
     rstd[e] = (float)(1.0 / sqrt(var + (double)p.eps));
@@ -101,29 +126,31 @@ __device__ __forceinline__ void col_consts(const NormParams& p, const double* st
   }
 }
 
+template <bool SPLIT>
 __global__ __launch_bounds__(NT) void bn_apply_kernel(NormParams p) {
   if (p.seed_dev != nullptr) p.seed += *p.seed_dev;
   const Lay l = lay_of(p.D);
+  const int64_t n = stat_rows<SPLIT>(p);
   __shared__ double st[2 * MAXD];
-  block_totals(p.stats, p.D, st);
+  load_totals<SPLIT>(p.stats, p.D, st);
   if (blockIdx.x == 0 && p.running_mean != nullptr) {      // torch.nn.BatchNorm1d: unbiased variance into the running buffer
     for (int c = threadIdx.x; c < p.D; c += NT) {
-      const double m = st[c] / (double)p.N;
-      double var = st[p.D + c] / (double)p.N - m * m;
+      const double m = st[c] / (double)n;
+      double var = st[p.D + c] / (double)n - m * m;
       var = var > 0.0 ? var : 0.0;
-      const double unb = p.N > 1 ? var * (double)p.N / (double)(p.N - 1) : var;
+      const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
       p.running_mean[c] = (1.f - p.momentum) * p.running_mean[c] + p.momentum * (float)m;
       p.running_var[c] = (1.f - p.momentum) * p.running_var[c] + p.momentum * (float)unb;
     }
   }
   if (!l.on) return;
   float mean[4], rstd[4], ga[4], be[4];
-  col_consts(p, st, l.cg, mean, rstd, ga, be);
+  col_consts(p, n, st, l.cg, mean, rstd, ga, be);
   for (int64_t r = (int64_t)blockIdx.x * l.rpp + l.rof; r < p.N; r += (int64_t)gridDim.x * l.rpp) {
     const float4 a = *reinterpret_cast<const float4*>(p.x + r * p.ldx + 4 * l.cg);
     float o[4] = {a.x, a.y, a.z, a.w};
     uint32_t w0 = 0xFFFFFFFFu, w1 = 0xFFFFFFFFu;
-    if (p.thr != 0u) drop_words((uint64_t)r * (uint64_t)l.lpr + (uint64_t)l.cg, p.seed, w0, w1);
+    if (p.thr != 0u) drop_words(counter_row<SPLIT>(p, r) * (uint64_t)l.lpr + (uint64_t)l.cg, p.seed, w0, w1);
     const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -136,13 +163,14 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(NormParams p) {
 }
 
 // g' = dL/d(bn output) = gy * keep_scale where kept and the ReLU is open, else 0
+template <bool SPLIT>
 __device__ __forceinline__ void grad_prime(const NormParams& p, const Lay& l, int64_t r, const float mean[4], const float rstd[4],
                                            const float ga[4], const float be[4], float xh[4], float gp[4]) {
   const float4 a = *reinterpret_cast<const float4*>(p.x + r * p.ldx + 4 * l.cg);
   const float4 g = *reinterpret_cast<const float4*>(p.gy + r * p.ldg + 4 * l.cg);
   const float xa[4] = {a.x, a.y, a.z, a.w}, gv[4] = {g.x, g.y, g.z, g.w};
   uint32_t w0 = 0xFFFFFFFFu, w1 = 0xFFFFFFFFu;
-  if (p.thr != 0u) drop_words((uint64_t)r * (uint64_t)l.lpr + (uint64_t)l.cg, p.seed, w0, w1);
+  if (p.thr != 0u) drop_words(counter_row<SPLIT>(p, r) * (uint64_t)l.lpr + (uint64_t)l.cg, p.seed, w0, w1);
   const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -152,18 +180,19 @@ __device__ __forceinline__ void grad_prime(const NormParams& p, const Lay& l, in
   }
 }
 
+template <bool SPLIT>
 __global__ __launch_bounds__(NT) void bn_bwd_reduce_kernel(NormParams p) {
   if (p.seed_dev != nullptr) p.seed += *p.seed_dev;
   const Lay l = lay_of(p.D);
   __shared__ double st[2 * MAXD];
-  block_totals(p.stats, p.D, st);
+  load_totals<SPLIT>(p.stats, p.D, st);
   double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (l.on) {
     float mean[4], rstd[4], ga[4], be[4];
-    col_consts(p, st, l.cg, mean, rstd, ga, be);
+    col_consts(p, stat_rows<SPLIT>(p), st, l.cg, mean, rstd, ga, be);
     for (int64_t r = (int64_t)blockIdx.x * l.rpp + l.rof; r < p.N; r += (int64_t)gridDim.x * l.rpp) {
       float xh[4], gp[4];
-      grad_prime(p, l, r, mean, rstd, ga, be, xh, gp);
+      grad_prime<SPLIT>(p, l, r, mean, rstd, ga, be, xh, gp);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         v[e] += (double)gp[e];
@@ -174,23 +203,25 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_kernel(NormParams p) {
   block_sum8_to_global(v, l, p.D, p.gsum);
 }
 
+template <bool SPLIT>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(NormParams p) {
   if (p.seed_dev != nullptr) p.seed += *p.seed_dev;
   const Lay l = lay_of(p.D);
+  const int64_t n = stat_rows<SPLIT>(p);
   __shared__ double st[2 * MAXD], gs[2 * MAXD];
-  block_totals(p.stats, p.D, st);
-  block_totals(p.gsum, p.D, gs);
+  load_totals<SPLIT>(p.stats, p.D, st);
+  load_totals<SPLIT>(p.gsum, p.D, gs);
   if (!l.on) return;
   float mean[4], rstd[4], ga[4], be[4], c1[4], c2[4];
-  col_consts(p, st, l.cg, mean, rstd, ga, be);
+  col_consts(p, n, st, l.cg, mean, rstd, ga, be);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    c1[e] = (float)(gs[4 * l.cg + e] / (double)p.N);
-    c2[e] = (float)(gs[p.D + 4 * l.cg + e] / (double)p.N);
+    c1[e] = (float)(gs[4 * l.cg + e] / (double)n);
+    c2[e] = (float)(gs[p.D + 4 * l.cg + e] / (double)n);
   }
   for (int64_t r = (int64_t)blockIdx.x * l.rpp + l.rof; r < p.N; r += (int64_t)gridDim.x * l.rpp) {
     float xh[4], gp[4], o[4];
-    grad_prime(p, l, r, mean, rstd, ga, be, xh, gp);
+    grad_prime<SPLIT>(p, l, r, mean, rstd, ga, be, xh, gp);
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = ga[e] * rstd[e] * (gp[e] - c1[e] - xh[e] * c2[e]);
     *reinterpret_cast<float4*>(p.gx + r * p.ldgx + 4 * l.cg) = make_float4(o[0], o[1], o[2], o[3]);
@@ -229,7 +260,7 @@ extern "C" int bgnn_bn_relu_dropout_f32(const float* x, int64_t N, int32_t D, in
   const int grid = grid_for(N, D);
   hipLaunchKernelGGL(colstats_kernel, dim3(grid), dim3(NT), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(NT), 0, st, p);
+  hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(grid), dim3(NT), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
@@ -249,9 +280,101 @@ extern "C" int bgnn_bn_relu_dropout_bwd_f32(const float* x, const float* grad_y,
   p.relu = relu; p.seed = seed; p.seed_dev = seed_dev_opt; p.gy = grad_y; p.ldg = ldg; p.gsum = gsum; p.gx = grad_x; p.ldgx = ldgx;
   drop_consts(p_drop, p.thr, p.keep_scale);
   const int grid = grid_for(N, D);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(grid), dim3(NT), 0, st, p);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(grid), dim3(NT), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(NT), 0, st, p);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(NT), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the same four phases, separately callable (a collective sits between a reduction and its apply pass) ------------------------
+namespace {
+
+// x / y / grad rows may be NULL only when there are no rows
+bool rows_null(const void* p, int64_t n_rows) { return p == nullptr && n_rows > 0; }
+
+int split_params(NormParams& p, const float* x, int64_t n_rows, int32_t D, int64_t ldx, const double* totals, int64_t n_total,
+                 const float* gamma_opt, const float* beta_opt, float eps, int relu, float p_drop, uint64_t seed,
+                 const uint64_t* seed_dev_opt, const int64_t* row_ids_opt, int64_t row_base) {
+  if (rows_null(x, n_rows) || !totals) return BGNN_E_NULL;
+  if (!shape_ok(n_rows, D, ldx) || n_total < 1 || n_total < n_rows || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
+  if (row_ids_opt == nullptr && row_base < 0) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(x)) return BGNN_E_ALIGN;
+  p.x = x; p.N = n_rows; p.D = D; p.ldx = ldx; p.stats = totals; p.n_total = n_total; p.gamma = gamma_opt; p.beta = beta_opt; p.eps = eps;
+  p.relu = relu; p.seed = seed; p.seed_dev = seed_dev_opt; p.row_ids = row_ids_opt; p.row_base = row_base;
+  drop_consts(p_drop, p.thr, p.keep_scale);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int bgnn_bn_colstats_f32(const float* x, int64_t n_rows, int32_t D, int64_t ldx, double* acc, void* stream) {
+  if (rows_null(x, n_rows) || !acc) return BGNN_E_NULL;
+  if (!shape_ok(n_rows, D, ldx)) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(x)) return BGNN_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (bgnn_zero_async(acc, sizeof(double) * acc_doubles(D), st) != hipSuccess) return (int)hipErrorInvalidValue;
+  if (n_rows == 0) return 0;
+  NormParams p{};
+  p.x = x; p.N = n_rows; p.D = D; p.ldx = ldx; p.stats = acc;
+  hipLaunchKernelGGL(colstats_kernel, dim3(grid_for(n_rows, D)), dim3(NT), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int bgnn_bn_apply_rows_f32(const float* x, int64_t n_rows, int32_t D, int64_t ldx, const double* totals, int64_t n_total,
+                                      const float* gamma_opt, const float* beta_opt, float eps, int relu, float p_drop, uint64_t seed,
+                                      const uint64_t* seed_dev_opt, const int64_t* row_ids_opt, int64_t row_base,
+                                      float momentum, float* running_mean_opt, float* running_var_opt,
+                                      float* y, int64_t ldy, void* stream) {
+  if (rows_null(y, n_rows)) return BGNN_E_NULL;
+  if ((running_mean_opt == nullptr) != (running_var_opt == nullptr)) return BGNN_E_NULL;
+  NormParams p{};
+  const int rc = split_params(p, x, n_rows, D, ldx, totals, n_total, gamma_opt, beta_opt, eps, relu, p_drop, seed, seed_dev_opt, row_ids_opt, row_base);
+  if (rc != 0) return rc;
+  if (!shape_ok(n_rows, D, ldy)) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(y)) return BGNN_E_ALIGN;
+  if (n_rows == 0 && running_mean_opt == nullptr) return 0;
+  p.y = y; p.ldy = ldy; p.momentum = momentum; p.running_mean = running_mean_opt; p.running_var = running_var_opt;
+  // a rank without rows still runs block 0: its copy of the running buffers moves with everybody else's
+  hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(grid_for(n_rows, D)), dim3(NT), 0, (hipStream_t)stream, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int bgnn_bn_bwd_reduce_rows_f32(const float* x, const float* grad_y, int64_t n_rows, int32_t D, int64_t ldx, int64_t ldg,
+                                           const double* totals, int64_t n_total, const float* gamma_opt, const float* beta_opt,
+                                           float eps, int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                           const int64_t* row_ids_opt, int64_t row_base, double* gacc, void* stream) {
+  if (rows_null(grad_y, n_rows) || !gacc) return BGNN_E_NULL;
+  NormParams p{};
+  const int rc = split_params(p, x, n_rows, D, ldx, totals, n_total, gamma_opt, beta_opt, eps, relu, p_drop, seed, seed_dev_opt, row_ids_opt, row_base);
+  if (rc != 0) return rc;
+  if (!shape_ok(n_rows, D, ldg)) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(grad_y)) return BGNN_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (bgnn_zero_async(gacc, sizeof(double) * acc_doubles(D), st) != hipSuccess) return (int)hipErrorInvalidValue;
+  if (n_rows == 0) return 0;
+  p.gy = grad_y; p.ldg = ldg; p.gsum = gacc;
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(grid_for(n_rows, D)), dim3(NT), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int bgnn_bn_bwd_apply_rows_f32(const float* x, const float* grad_y, int64_t n_rows, int32_t D, int64_t ldx, int64_t ldg,
+                                          const double* totals, const double* gtotals, int64_t n_total, const float* gamma_opt,
+                                          const float* beta_opt, float eps, int relu, float p_drop, uint64_t seed,
+                                          const uint64_t* seed_dev_opt, const int64_t* row_ids_opt, int64_t row_base,
+                                          float* grad_x, int64_t ldgx, void* stream) {
+  if (rows_null(grad_y, n_rows) || rows_null(grad_x, n_rows) || !gtotals) return BGNN_E_NULL;
+  NormParams p{};
+  const int rc = split_params(p, x, n_rows, D, ldx, totals, n_total, gamma_opt, beta_opt, eps, relu, p_drop, seed, seed_dev_opt, row_ids_opt, row_base);
+  if (rc != 0) return rc;
+  if (!shape_ok(n_rows, D, ldg) || !shape_ok(n_rows, D, ldgx)) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(grad_y) || !bgnn_aligned16(grad_x)) return BGNN_E_ALIGN;
+  if (n_rows == 0) return 0;
+  p.gy = grad_y; p.ldg = ldg; p.gsum = const_cast<double*>(gtotals); p.gx = grad_x; p.ldgx = ldgx;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(grid_for(n_rows, D)), dim3(NT), 0, (hipStream_t)stream, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }

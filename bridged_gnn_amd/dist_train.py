@@ -13,7 +13,8 @@ square by giving the halo rows no in-edges.  What crosses ranks, forward and bac
   * the per-domain sums behind delta (KTGNN.py:275) are all-reduced; the gradient through the domain means is a global quantity:
     every transform hands its local adjoint of delta to a hook that all-reduces it and applies +1/n_S | -1/n_T on the owned rows;
   * train-mode BatchNorm uses the statistics of ALL N nodes (KTGNN.py:420-430): sum / sum-of-squares all-reduced forward, the two
-    backward reductions all-reduced too (`_SyncBnReluDrop`);
+    backward reductions all-reduced too (`_SyncBnReluDrop`: the single-GPU HIP layer in four phases, its dropout mask the rank's rows
+    of the single-GPU mask);
   * parameter gradients are summed over ranks in ONE bucketed all-reduce (`sync_grads`).
 Losses are sums over owned rows with GLOBAL normalisers (`reference_loss`), so the per-rank losses add up to the reference's loss.
 """
@@ -23,7 +24,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .dist import PartitionPlan
-from .ktgnn import _AggregateFn, _pad_cols4
+from .ktgnn import _AggregateFn, _pad_cols4, dropout_seed
 
 
 class _Comm:
@@ -74,7 +75,56 @@ class _HaloRows(torch.autograd.Function):
 
 
 class _SyncBnReluDrop(torch.autograd.Function):
-    """BatchNorm1d(train) -> ReLU -> dropout over the rows of ALL ranks (KTGNN.py:420-430; clf_transformer's BN + ReLU, :407-411)"""
+    """BatchNorm1d(train) -> ReLU -> dropout over the rows of ALL ranks (KTGNN.py:420-430; clf_transformer's BN + ReLU, :407-411):
+    the single-GPU layer (`ktgnn._BnReluDropFn`) with a collective between each reduction and its apply pass --
+      forward : ops.bn_colstats -> all-reduce of 2 D doubles -> ops.bn_apply_rows
+      backward: ops.bn_bwd_reduce_rows -> all-reduce of 2 D doubles -> ops.bn_bwd_apply_rows
+    Only x and the all-reduced totals are kept.  The dropout mask is the single-GPU kernel's hash of (seed, GLOBAL row, column group):
+    the seed is drawn as `_BnReluDropFn` draws it (`ktgnn.dropout_seed`: host generator, nothing for p = 0), so ranks seeded alike
+    drop exactly the rows of the whole-graph mask they own."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, relu, p_drop, comm, n_global, row_ids):
+        seed, seed_dev = dropout_seed(p_drop)
+        track = bn.track_running_stats and bn.running_mean is not None
+        mom = 0.0
+        if track:
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+            mom = bn.momentum
+        ga = weight.detach() if weight is not None else None
+        be = bias.detach() if bias is not None else None
+        totals = comm.all_reduce(ops.bn_colstats(x))
+        y = ops.bn_apply_rows(x, totals, n_global, ga, be, bn.eps, relu, p_drop, seed, row_ids=row_ids, momentum=mom,
+                              running_mean=bn.running_mean if track else None, running_var=bn.running_var if track else None,
+                              seed_dev=seed_dev)
+        if track:                                                # written through raw pointers: see `_BnReluDropFn.forward`
+            torch.autograd.graph.increment_version((bn.running_mean, bn.running_var))
+            bn._bgnn_affine = None
+        ctx.save_for_backward(x, weight, bias, totals, row_ids)
+        ctx.cfg = (bn.eps, relu, p_drop, seed, comm, n_global)
+        ctx.seed_dev = seed_dev
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, bias, totals, row_ids = ctx.saved_tensors
+        eps, relu, p_drop, seed, comm, n = ctx.cfg
+        gy = gy if (gy.stride(1) == 1 and gy.stride(0) % 4 == 0 and gy.data_ptr() % 16 == 0) else gy.contiguous()
+        ga = weight.detach() if weight is not None else None
+        be = bias.detach() if bias is not None else None
+        kw = dict(row_ids=row_ids, seed_dev=ctx.seed_dev)
+        part = ops.bn_bwd_reduce_rows(x, gy, totals, n, ga, be, eps, relu, p_drop, seed, **kw)
+        gtot = comm.all_reduce(part.clone() if comm.live else part)          # `part` stays this rank's share: dL/dbeta | dL/dgamma
+        gx = ops.bn_bwd_apply_rows(x, gy, totals, gtot, n, ga, be, eps, relu, p_drop, seed, **kw) if ctx.needs_input_grad[0] else None
+        D = x.shape[1]
+        gs = part.float()
+        return (gx, gs[D:] if weight is not None else None, gs[:D] if bias is not None else None, None, None, None, None, None, None)
+
+
+class _SyncBnReluDropTorch(torch.autograd.Function):
+    """the same layer in torch ops, for shapes outside the kernels' envelope (`ops.bn_relu_dropout_supported`); its dropout mask
+    comes from the device generator, as the single-GPU model's does there"""
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn, relu, p_drop, comm, n_global):
@@ -160,7 +210,9 @@ class PartitionedTrainer:
         return self.coef * self.comm.all_reduce(ddl.contiguous())[None, :]
 
     def _bn(self, x, bn, relu, p_drop):
-        return _SyncBnReluDrop.apply(x, bn.weight, bn.bias, bn, relu, float(p_drop), self.comm, self.n_global)
+        if (ops.bn_relu_dropout_supported(x) and self.n_global > 1 and (bn.momentum is not None or not bn.track_running_stats)):
+            return _SyncBnReluDrop.apply(x, bn.weight, bn.bias, bn, relu, float(p_drop), self.comm, self.n_global, self.owned_global)
+        return _SyncBnReluDropTorch.apply(x, bn.weight, bn.bias, bn, relu, float(p_drop), self.comm, self.n_global)
 
     def _input_ext(self, x_local):
         if self._x_ext is None or self._x_ext[0] is not x_local or self._x_ext[1] != x_local._version:
@@ -210,17 +262,29 @@ class PartitionedTrainer:
     def reference_loss(self, out, y_local, train_mask_local):
         """this rank's share of the reference's loss (main_graph_knowledge_transfer.py:44-54): the three masked NLL terms and the
         KL term as sums over the OWNED rows divided by the GLOBAL counts -- the shares of all ranks add up to the reference's value"""
+        return self.reference_loss_terms(out, y_local, train_mask_local)[0]
+
+    def reference_loss_terms(self, out, y_local, train_mask_local, Lambda=1.0):
+        """-> (`reference_loss` with the KL term weighted by `Lambda`, this rank's share of the loss pass's fp64 [8] vector in
+        `ops.STEP2_TERMS` layout: total, the three NLL means, the KL term without Lambda, the two row counts).  Summed over the
+        ranks (ONE all-reduce) the shares are the terms `ops.step2_loss` returns on the whole graph."""
         lb, lt, lth = out
         tm = train_mask_local.bool()
         tmt = tm & ~self.mask_local
-        cnt = self.comm.all_reduce(torch.stack((tm.sum(), tmt.sum())).double()).float().clamp_min(1)
+        own = torch.stack((tm.sum(), tmt.sum())).double()
+        cnt = self.comm.all_reduce(own.clone()).float().clamp_min(1)
         yi = y_local.clamp_min(0)[:, None]
 
         def nll(logp, w):
             return -(logp.gather(1, yi).squeeze(1) * w).sum()
         w_b, w_t = tm.float() / cnt[0], tmt.float() / cnt[1]
         kl = (lt.exp() * (lt - lth)).sum() / self.n_global                       # F.kl_div(lth, lt, log_target=True, 'batchmean')
-        return (2 * nll(lb, w_b) + nll(lt, w_t) + nll(lth, w_t)) / 4 + kl
+        n_s, n_t, n_h = nll(lb, w_b), nll(lt, w_t), nll(lth, w_t)
+        loss = (2 * n_s + n_t + n_h) / 4 + (kl if Lambda == 1.0 else Lambda * kl)
+        with torch.no_grad():
+            terms = torch.stack((loss, n_s, n_t, n_h, kl)).double()
+            terms = torch.cat((terms, own, own.new_zeros(1)))
+        return loss, terms
 
     def sync_grads(self):
         """sum the parameter gradients over the ranks: ONE all-reduce of one flat bucket"""

@@ -440,6 +440,64 @@ def bn_relu_dropout_bwd(x, grad_y, stats, gamma, beta, eps, relu, p_drop, seed, 
     return gx, gsum.view(-1, 2 * D).sum(0)
 
 
+# ---- the same layer in four phases for a node partition (include/bgnn.h: the *_rows entries): a rank reduces its rows, the caller
+#      all-reduces the [2 * D] doubles, the apply passes take the totals over all ranks, the global row count and the global row
+#      numbers (`row_ids` int64 [n_rows], or `row_base` + local row) that fix the dropout counter
+def _bn_rows_args(x, totals, n_total, gamma, beta, eps, relu, p_drop, seed, seed_dev, row_ids, row_base):
+    D = x.shape[1]
+    if totals.dtype != torch.float64 or totals.numel() != 2 * D:
+        raise RuntimeError(f"totals must be {2 * D} doubles (sum x | sum x^2 over all ranks' rows)")
+    if row_ids is not None and (row_ids.dtype != torch.int64 or row_ids.numel() != x.shape[0]):
+        raise RuntimeError("row_ids must hold one int64 global row number per local row")
+    return (L.ptr(totals), int(n_total), L.ptr(gamma) if gamma is not None else None, L.ptr(beta) if beta is not None else None,
+            float(eps), int(bool(relu)), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(seed_dev) if seed_dev is not None else None,
+            L.ptr(row_ids) if row_ids is not None else None, int(row_base))
+
+
+def bn_colstats(x):
+    """-> fp64 [2 * D]: the column sums of x | x^2 over this rank's rows (zeros for no rows)"""
+    N, D = x.shape
+    acc = torch.empty(L.lib().bgnn_bn_acc_doubles(D), dtype=torch.float64, device=x.device)
+    L.check(L.lib().bgnn_bn_colstats_f32(L.ptr_rows(x), N, D, x.stride(0), L.ptr(acc), L.stream()), "bgnn_bn_colstats_f32")
+    return acc.view(-1, 2 * D).sum(0)
+
+
+def bn_apply_rows(x, totals, n_total, gamma, beta, eps, relu, p_drop, seed, row_ids=None, row_base=0, momentum=0.0, running_mean=None,
+                  running_var=None, seed_dev=None):
+    """-> y [n_rows, D]: BatchNorm1d(train) -> ReLU -> dropout of this rank's rows from the totals over `n_total` rows of all ranks"""
+    N, D = x.shape
+    y = torch.empty(N, D, dtype=torch.float32, device=x.device)
+    a = _bn_rows_args(x, totals, n_total, gamma, beta, eps, relu, p_drop, seed, seed_dev, row_ids, row_base)
+    rc = L.lib().bgnn_bn_apply_rows_f32(L.ptr_rows(x), N, D, x.stride(0), *a, float(momentum),
+                                        L.ptr(running_mean) if running_mean is not None else None,
+                                        L.ptr(running_var) if running_var is not None else None, L.ptr(y), D, L.stream())
+    L.check(rc, "bgnn_bn_apply_rows_f32")
+    return y
+
+
+def bn_bwd_reduce_rows(x, grad_y, totals, n_total, gamma, beta, eps, relu, p_drop, seed, row_ids=None, row_base=0, seed_dev=None):
+    """-> fp64 [2 * D]: this rank's share of sum g' (= dL/dbeta) | sum g'.xhat (= dL/dgamma)"""
+    N, D = x.shape
+    gacc = torch.empty(L.lib().bgnn_bn_acc_doubles(D), dtype=torch.float64, device=x.device)
+    a = _bn_rows_args(x, totals, n_total, gamma, beta, eps, relu, p_drop, seed, seed_dev, row_ids, row_base)
+    rc = L.lib().bgnn_bn_bwd_reduce_rows_f32(L.ptr_rows(x), L.ptr_rows(grad_y), N, D, x.stride(0), grad_y.stride(0), *a, L.ptr(gacc), L.stream())
+    L.check(rc, "bgnn_bn_bwd_reduce_rows_f32")
+    return gacc.view(-1, 2 * D).sum(0)
+
+
+def bn_bwd_apply_rows(x, grad_y, totals, gtotals, n_total, gamma, beta, eps, relu, p_drop, seed, row_ids=None, row_base=0, seed_dev=None):
+    """-> dL/dx [n_rows, D] from the all-reduced pair of `bn_bwd_reduce_rows`"""
+    N, D = x.shape
+    if gtotals.dtype != torch.float64 or gtotals.numel() != 2 * D:
+        raise RuntimeError(f"gtotals must be {2 * D} doubles (sum g' | sum g'.xhat over all ranks' rows)")
+    gx = torch.empty(N, D, dtype=torch.float32, device=x.device)
+    a = _bn_rows_args(x, totals, n_total, gamma, beta, eps, relu, p_drop, seed, seed_dev, row_ids, row_base)
+    rc = L.lib().bgnn_bn_bwd_apply_rows_f32(L.ptr_rows(x), L.ptr_rows(grad_y), N, D, x.stride(0), grad_y.stride(0), a[0], L.ptr(gtotals), *a[1:],
+                                            L.ptr(gx), D, L.stream())
+    L.check(rc, "bgnn_bn_bwd_apply_rows_f32")
+    return gx
+
+
 def rowdot(X, V):
     """X [N,d] (unit column stride, 16-B aligned rows) times up to four vectors V [nv,d] -> [N,nv] in one pass over X."""
     N, d = X.shape

@@ -161,6 +161,34 @@ int bgnn_bn_relu_dropout_bwd_f32(const float* x, const float* grad_y, int64_t N,
                                  const double* stats, const float* gamma_opt, const float* beta_opt, float eps,
                                  int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* grad_x, int64_t ldgx,
                                  double* gsum, void* stream);
+/* The same BatchNorm1d -> ReLU -> dropout (models/KTGNN.py:420-430, :364-367) in four separately callable phases, for a node
+ *   partition whose ranks put a collective between a reduction and its apply pass.  Same envelope and error codes as above;
+ *   n_rows == 0 is valid (row pointers may then be NULL); nothing uses a memset node.
+ * bgnn_bn_colstats_f32: this rank's fp64 column sums of x | x^2 into `acc` (bgnn_bn_acc_doubles(D) doubles = R x [2*D] partials,
+ *   cleared here by a kernel; their sum over R is the rank's share; n_rows == 0 leaves zeros).
+ * The *_rows entries take `totals` (plain [2*D] doubles: sum x | sum x^2 over the rows of ALL ranks) and `n_total`, the row count
+ *   those sums run over (>= n_rows, >= 1): mean, variance and the unbiased factor of the running buffers use n_total.  The dropout
+ *   counter of local row r is global_row * (D/4) + column group with global_row = row_ids_opt[r] (device int64 [n_rows]) or, when
+ *   row_ids_opt is NULL, row_base + r -- the counter of bgnn_bn_relu_dropout_f32 on the whole activation, same `seed` /
+ *   `seed_dev_opt` convention, so a rank's mask is its rows of the whole-graph mask.
+ * bgnn_bn_apply_rows_f32: y rows; running_mean / running_var (both or neither) are updated on every call, also with n_rows == 0.
+ * bgnn_bn_bwd_reduce_rows_f32: this rank's partial sum g' | sum g'.xhat into `gacc` (bgnn_bn_acc_doubles(D) doubles, as `acc`).
+ * bgnn_bn_bwd_apply_rows_f32: dL/dx rows from `gtotals` (plain [2*D] doubles: that pair summed over all ranks) and n_total. */
+int bgnn_bn_colstats_f32(const float* x, int64_t n_rows, int32_t D, int64_t ldx, double* acc, void* stream);
+int bgnn_bn_apply_rows_f32(const float* x, int64_t n_rows, int32_t D, int64_t ldx, const double* totals, int64_t n_total,
+                           const float* gamma_opt, const float* beta_opt, float eps, int relu, float p_drop, uint64_t seed,
+                           const uint64_t* seed_dev_opt, const int64_t* row_ids_opt, int64_t row_base,
+                           float momentum, float* running_mean_opt, float* running_var_opt,
+                           float* y, int64_t ldy, void* stream);
+int bgnn_bn_bwd_reduce_rows_f32(const float* x, const float* grad_y, int64_t n_rows, int32_t D, int64_t ldx, int64_t ldg,
+                                const double* totals, int64_t n_total, const float* gamma_opt, const float* beta_opt,
+                                float eps, int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                const int64_t* row_ids_opt, int64_t row_base, double* gacc, void* stream);
+int bgnn_bn_bwd_apply_rows_f32(const float* x, const float* grad_y, int64_t n_rows, int32_t D, int64_t ldx, int64_t ldg,
+                               const double* totals, const double* gtotals, int64_t n_total, const float* gamma_opt,
+                               const float* beta_opt, float eps, int relu, float p_drop, uint64_t seed,
+                               const uint64_t* seed_dev_opt, const int64_t* row_ids_opt, int64_t row_base,
+                               float* grad_x, int64_t ldgx, void* stream);
 /* bgnn_transform_bwd_prep_f32: row-local part of the transform's hand-derived backward (KTGNN.py:275-284 under autograd) in
  *   one stream over x and the two incoming gradient tables: gate values (tanh of x.gx[g] + gconst[g]), the gates'
  *   adjoints G.(W delta) (wd [2][2D]: row 0 = -(W_t delta) in columns 0..D-1, row 1 = W_s delta in columns D..2D-1), and
