@@ -65,6 +65,10 @@ SIGNATURES = {
     "bgnn_adaptedconv_aggregate_bwd_pull_hub_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _F32,
                                                             _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32,
                                                             _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
+    "bgnn_aggregate_bwd_pull_wide_workspace_bytes": (C.c_size_t, [_I64, _I64, _I64, _I64, _I64]),
+    "bgnn_adaptedconv_aggregate_bwd_pull_wide_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _F32,
+                                                             _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32,
+                                                             _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
     "bgnn_aggregate_heads_bwd_workspace_bytes": (C.c_size_t, [_I64, _I64, _I32]),
     "bgnn_adaptedconv_aggregate_heads_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32,
                                                          _P, _P, _P, _INT, _P, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -146,7 +150,7 @@ def source_hash():
 
 # keep in step with HASHED in csrc/Makefile
 _HASHED_SOURCES = ("bgnn_api.hip", "bgnn_csr.hip", "bgnn_transform.hip", "bgnn_transform_stream.hip", "bgnn_transform_cls.hip", "bgnn_aggregate.hip", "bgnn_aggregate_bwd.hip",
-                   "bgnn_aggregate_bwd_fast.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_gcn.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_pair_mlp.hip", "bgnn_pair_cos.hip", "bgnn_step2.hip", "bgnn_optim.hip", "bgnn_edge_filter.hip", "bgnn_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
+                   "bgnn_aggregate_bwd_fast.hip", "bgnn_aggregate_bwd_wide.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_gcn.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_pair_mlp.hip", "bgnn_pair_cos.hip", "bgnn_step2.hip", "bgnn_optim.hip", "bgnn_edge_filter.hip", "bgnn_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
 
 
 def _sidecar_hash():

@@ -824,6 +824,19 @@ int launch_pull(const PullParams& p, hipStream_t st, const PullHubs* hubs = null
 
 }  // namespace
 
+int bgnn_bwd::pull_merge_dst_launch(const PullParams& p, const int32_t* hub_rows, const int32_t* seg_ptr, int64_t n_hubs, hipStream_t st) {
+  PullMergeParams m{hub_rows, seg_ptr, n_hubs, p.ldh, p.d_vpart, nullptr, p.mask, p.dstside, nullptr, nullptr};
+  hipLaunchKernelGGL(pull_merge_dst_kernel, dim3((unsigned)((n_hubs * (p.ldh / 4) + 255) / 256)), dim3(256), 0, st, m);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+int bgnn_bwd::pull_merge_src_launch(const PullParams& p, const int32_t* hub_rows, const int32_t* seg_ptr, int64_t n_hubs, hipStream_t st) {
+  PullMergeParams m{hub_rows, seg_ptr, n_hubs, p.ldh, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t};
+  hipLaunchKernelGGL(pull_merge_src_kernel, dim3((unsigned)((n_hubs * (p.ldh / 4) + 255) / 256)), dim3(256), 0, st, m);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int bgnn_adaptedconv_aggregate_bwd_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
                                                   const float* a_t2s, const float* a_s2t,
                                                   const int32_t* rowptr, const int32_t* col, const uint8_t* mask,

@@ -35,5 +35,9 @@ struct PullParams {
 bool pull_fast_plan(PullParams& p);
 // pass A (by destination) + pass B (by source) on `st`; p.queue zeroed by the caller
 int pull_fast_launch(const PullParams& p, hipStream_t st);
+// merges of the hub segments' partial rows (pull_merge_dst_kernel / pull_merge_src_kernel, bgnn_aggregate_bwd.hip; generic in ldh),
+// for the D > 128 pair (bgnn_aggregate_bwd_wide.hip): after pass A / after pass B, hub tables as in PullHubs
+int pull_merge_dst_launch(const PullParams& p, const int32_t* hub_rows, const int32_t* seg_ptr, int64_t n_hubs, hipStream_t st);
+int pull_merge_src_launch(const PullParams& p, const int32_t* hub_rows, const int32_t* seg_ptr, int64_t n_hubs, hipStream_t st);
 
 }  // namespace bgnn_bwd

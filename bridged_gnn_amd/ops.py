@@ -670,8 +670,8 @@ def adaptedconv_aggregate_bwd(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, out, 
     da_s2t = torch.zeros(D, dtype=torch.float32, device=dev)
     grad_out = grad_out.contiguous()
     if D <= 128 and grad_out.stride(0) % 4 == 0 and grad_out.data_ptr() % 16 == 0 and h_t2s.shape[0] == csr.num_nodes:
-        # atomic-free pull over the by-source CSR (float atomics retire at ~1.3 TB/s on MI355X); the atomic form remains for
-        # D > 128 and for row ranges
+        # atomic-free pull over the by-source CSR (float atomics retire at ~1.3 TB/s on MI355X); 128 < D <= 256 takes the wide
+        # pair further down, the atomic form remains for row ranges
         t_rowptr, t_eid, t_dst = csr.transposed()
         dh_t2s, dh_s2t = torch.empty_like(h_t2s), torch.empty_like(h_s2t)
         narrow = D <= 4 and h_t2s.stride(0) == 4 and out.stride(0) == 4 and grad_out.stride(0) == 4
@@ -702,6 +702,31 @@ def adaptedconv_aggregate_bwd(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, out, 
             L.ptr(out), out.stride(0), L.ptr(alpha), L.ptr(grad_out), grad_out.stride(0),
             L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), L.ptr(ws), wsb, L.stream())
         L.check(rc, "bgnn_adaptedconv_aggregate_bwd_pull_f32")
+        return dh_t2s, dh_s2t, da_t2s, da_s2t
+    if (128 < D <= 256 and grad_out.stride(0) % 4 == 0 and grad_out.data_ptr() % 16 == 0 and h_t2s.shape[0] == csr.num_nodes
+            and h_t2s.stride(0) % 4 == 0 and out.stride(0) % 4 == 0
+            and h_t2s.data_ptr() % 16 == 0 and h_s2t.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0):
+        # the same pull form, a whole wave per row (bgnn_aggregate_bwd_wide.hip): no float atomics, da summed in a fixed order --
+        # all four gradients bitwise reproducible.  Row ranges and misaligned operands keep the atomic form below.
+        t_rowptr, t_eid, t_dst = csr.transposed()
+        dh_t2s, dh_s2t = torch.empty_like(h_t2s), torch.empty_like(h_s2t)
+        dh_, sh_ = (csr.hub_tables(), csr.transposed_hub_tables()) if os.environ.get("BGNN_HUB_ROWS", "1") != "0" else (None, None)
+        none4 = (None, None, None, None)
+        d_rows, d_ptr, d_bounds, d_node = dh_ if dh_ is not None else none4
+        s_rows, s_ptr, s_bounds, s_node = sh_ if sh_ is not None else none4
+        nd = 0 if dh_ is None else int(d_node.numel())
+        ns = 0 if sh_ is None else int(s_node.numel())
+        wsb = lib.bgnn_aggregate_bwd_pull_wide_workspace_bytes(csr.num_nodes, csr.num_edges, h_t2s.stride(0), nd, ns)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        rc = lib.bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(
+            L.ptr(h_t2s), L.ptr(h_s2t), h_t2s.stride(0), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
+            L.ptr(mask_u8), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), csr.num_nodes, csr.num_edges, D, float(negative_slope),
+            L.ptr(out), out.stride(0), L.ptr(alpha), L.ptr(grad_out), grad_out.stride(0),
+            L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), HUB_THRESHOLD,
+            L.ptr(d_rows), 0 if dh_ is None else int(d_rows.numel()), L.ptr(d_ptr), L.ptr(d_bounds), L.ptr(d_node), nd,
+            L.ptr(s_rows), 0 if sh_ is None else int(s_rows.numel()), L.ptr(s_ptr), L.ptr(s_bounds), L.ptr(s_node), ns,
+            L.ptr(ws), wsb, L.stream())
+        L.check(rc, "bgnn_adaptedconv_aggregate_bwd_pull_wide_f32")
         return dh_t2s, dh_s2t, da_t2s, da_s2t
     dh_t2s, dh_s2t = torch.zeros_like(h_t2s), torch.zeros_like(h_s2t)
     rc = lib.bgnn_adaptedconv_aggregate_bwd_f32(

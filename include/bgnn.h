@@ -383,6 +383,29 @@ int bgnn_adaptedconv_aggregate_bwd_pull_hub_f32(const float* h_t2s, const float*
                                                 const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
                                                 void* ws, size_t ws_bytes, void* stream);
 
+/* The pull-form backward for 128 < D <= 256 (a whole wave per row; the two entries above keep refusing D > 128).  Argument list
+ * and hub tables of bgnn_adaptedconv_aggregate_bwd_pull_hub_f32; d_n_hubs = s_n_hubs = 0 (tables may then be NULL): no hub rows.
+ * Every dH row is written exactly once (pad columns D <= c < ldh: 0) and da_t2s / da_s2t are WRITTEN, not accumulated: pass A
+ * leaves partial da rows that are summed in a fixed order, so all four outputs of a call are bitwise reproducible.  Pad columns
+ * of the tables must hold finite values.  BGNN_E_SHAPE: D <= 128, D > 256, or ldh / ldo / ldg below D or not a multiple of 4.
+ * ws: bgnn_aggregate_bwd_pull_wide_workspace_bytes(N, E', ldh, d_n_segments, s_n_segments) (64-byte record per edge, the
+ * dstside table, the da partial rows, the hub segments' partial rows). */
+size_t bgnn_aggregate_bwd_pull_wide_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int64_t d_segments, int64_t s_segments);
+int bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
+                                                 const float* a_t2s, const float* a_s2t,
+                                                 const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                                 const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
+                                                 int64_t N, int64_t E, int32_t D, float negative_slope,
+                                                 const float* out, int64_t ldo, const float* alpha,
+                                                 const float* grad_out, int64_t ldg,
+                                                 float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
+                                                 int32_t hub_threshold,
+                                                 const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
+                                                 const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
+                                                 const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
+                                                 const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
+                                                 void* ws, size_t ws_bytes, void* stream);
+
 /* Pull-form backward for `heads` (2 or 3) interleaved narrow convs evaluated together (KT-GNN's classifier stage under
  * autograd: clf_base(x), clf_target(x), clf_target(T(x)), KTGNN.py:432-435, share the graph): tables / out / grad_out / dH are
  * [N][heads][4], a_* and da_* [heads][D] (da accumulated: caller zero-fills), D <= 4.  `state_ms` [N][heads][2] is the finished
