@@ -58,24 +58,14 @@ SIGNATURES = {
                                                    _P, _I32, _P, _I64, _P, _P, _P, _I64, _P, _P, C.c_size_t, _P]),
     "bgnn_adaptedconv_aggregate_bwd_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _F32,
                                                    _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P]),
-    "bgnn_aggregate_bwd_pull_workspace_bytes": (C.c_size_t, [_I64, _I64, _I64]),
+    "bgnn_aggregate_bwd_pull_workspace_bytes": (C.c_size_t, [_I64, _I64, _I64, _I32, _I64, _I64]),
     "bgnn_adaptedconv_aggregate_bwd_pull_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _F32,
-                                                        _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "bgnn_aggregate_bwd_pull_hub_workspace_bytes": (C.c_size_t, [_I64, _I64, _I64, _I64, _I64]),
-    "bgnn_adaptedconv_aggregate_bwd_pull_hub_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _F32,
-                                                            _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32,
-                                                            _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
-    "bgnn_aggregate_bwd_pull_wide_workspace_bytes": (C.c_size_t, [_I64, _I64, _I64, _I64, _I64]),
-    "bgnn_adaptedconv_aggregate_bwd_pull_wide_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _F32,
-                                                             _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32,
-                                                             _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
-    "bgnn_aggregate_heads_bwd_workspace_bytes": (C.c_size_t, [_I64, _I64, _I32]),
-    "bgnn_adaptedconv_aggregate_heads_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32,
-                                                         _P, _P, _P, _INT, _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "bgnn_aggregate_heads_bwd_hub_workspace_bytes": (C.c_size_t, [_I64, _I64, _I32, _I64, _I64]),
-    "bgnn_adaptedconv_aggregate_heads_bwd_hub_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32,
-                                                             _P, _P, _P, _INT, _P, _P, _P, _P, _I32,
-                                                             _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
+                                                        _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32,
+                                                        _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
+    "bgnn_aggregate_heads_bwd_workspace_bytes": (C.c_size_t, [_I64, _I64, _I32, _I64, _I64]),
+    "bgnn_adaptedconv_aggregate_heads_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32,
+                                                         _P, _P, _P, _INT, _P, _P, _P, _P, _I32,
+                                                         _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, C.c_size_t, _P]),
     "bgnn_adaptedconv_aggregate_heads_wide_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P, _P, _P]),
     "bgnn_aggregate_heads_wide_bwd_workspace_bytes": (C.c_size_t, [_I64, _I32, _I64]),
     "bgnn_adaptedconv_aggregate_heads_wide_bwd_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F32,
@@ -162,7 +152,7 @@ def _sidecar_hash():
 
 
 # the ABI revision this binding was written for (include/bgnn.h: BGNN_VERSION); checked against the loaded library
-ABI_VERSION = 113
+ABI_VERSION = 114
 
 
 def _make():

@@ -485,12 +485,10 @@ __global__ __launch_bounds__(256) void agg_bwd_src_narrow_kernel(PullParams p) {
 
 static int launch_pull_narrow(const PullParams& p, hipStream_t st) {
   constexpr int EP = 8, RPB = 4 * (64 / EP);
-  const int64_t ntiles = (p.N + RPB - 1) / RPB;
-  int64_t grid = ntiles < 2048 ? (ntiles + 7) / 8 * 8 : 2048;
-  if (grid < 8) grid = 8;
-  hipLaunchKernelGGL((agg_bwd_dst_narrow_kernel<EP>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  const unsigned grid = bgnn_bwd::resident_grid((p.N + RPB - 1) / RPB, 2048);
+  hipLaunchKernelGGL((agg_bwd_dst_narrow_kernel<EP>), dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL((agg_bwd_src_narrow_kernel<EP>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((agg_bwd_src_narrow_kernel<EP>), dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
@@ -756,83 +754,79 @@ __global__ __launch_bounds__(256) void pull_merge_src_kernel(PullMergeParams p) 
   *reinterpret_cast<float4*>(p.dh_t2s + j * p.ldh + f0) = a;
   *reinterpret_cast<float4*>(p.dh_s2t + j * p.ldh + f0) = c;
 }
-struct PullHubs {        // host side of the hub tables (device pointers)
-  const int32_t* d_rows; const int32_t* d_seg_ptr; int64_t d_nh;
-  const int32_t* s_rows; const int32_t* s_seg_ptr; int64_t s_nh;
-};
+using bgnn_bwd::PullHubs;
+using bgnn_bwd::PullLayout;
 
 template <int HEADS>
-int launch_heads_bwd(const HeadsBwdParams& p, hipStream_t st, const PullHubs* hubs = nullptr) {
+int launch_heads_bwd(const HeadsBwdParams& p, const PullHubs& hubs, hipStream_t st) {
   // (EP, U) = (2, 4) from a sweep on C4, both passes together: lane per head 2/4 0.69, 1/4 0.70, 1/2 0.73, 2/2 0.74, 4/4 0.74,
   // 4/2 0.80 ms (one lane for all heads: 1.33 ms); tools/heads_bwd_time.py times this pair of launches
   constexpr int EPV = 2, UV = 4, RPB = 4 * (64 / (EPV * HEADS));
   const int64_t nmax = p.N + (p.d_nv > p.s_nv ? p.d_nv : p.s_nv);
-  const int64_t ntiles = (nmax + RPB - 1) / RPB;
-  int64_t grid = ntiles < 2048 ? (ntiles + 7) / 8 * 8 : 2048;
-  if (grid < 8) grid = 8;
-  hipLaunchKernelGGL((agg_heads_bwd_dst_kernel<HEADS, EPV, UV>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  const unsigned grid = bgnn_bwd::resident_grid((nmax + RPB - 1) / RPB, 2048);
+  hipLaunchKernelGGL((agg_heads_bwd_dst_kernel<HEADS, EPV, UV>), dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  const int64_t ld = HEADS * 4;
-  if (hubs && hubs->d_nh > 0) {            // the hub destinations' dstside rows, before pass B reads them
-    PullMergeParams m{hubs->d_rows, hubs->d_seg_ptr, hubs->d_nh, ld, p.d_vpart, nullptr, p.mask, p.dstside, nullptr, nullptr};
-    hipLaunchKernelGGL(pull_merge_dst_kernel, dim3((unsigned)((hubs->d_nh * (ld / 4) + 255) / 256)), dim3(256), 0, st, m);
-    BGNN_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL((agg_heads_bwd_src_kernel<HEADS, EPV, UV>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  // the hub destinations' dstside rows, before pass B reads them
+  if (const int rc = bgnn_bwd::pull_merge_dst_launch(hubs, HEADS * 4, p.d_vpart, p.mask, p.dstside, st)) return rc;
+  hipLaunchKernelGGL((agg_heads_bwd_src_kernel<HEADS, EPV, UV>), dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  if (hubs && hubs->s_nh > 0) {
-    PullMergeParams m{hubs->s_rows, hubs->s_seg_ptr, hubs->s_nh, ld, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t};
-    hipLaunchKernelGGL(pull_merge_src_kernel, dim3((unsigned)((hubs->s_nh * (ld / 4) + 255) / 256)), dim3(256), 0, st, m);
-    BGNN_LAUNCH_CHECK();
-  }
-  return 0;
+  return bgnn_bwd::pull_merge_src_launch(hubs, HEADS * 4, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t, st);
 }
 
 template <int LF>
-int launch_pull(const PullParams& p, hipStream_t st, const PullHubs* hubs = nullptr) {
+int launch_pull(const PullParams& p, const PullHubs& hubs, hipStream_t st) {
   constexpr int RPB = 4 * (64 / LF);
-  static const int cap = [] {
-    int a = 0, b = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, agg_bwd_dst_kernel<LF>, 256, 0) != hipSuccess || a < 1) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, agg_bwd_src_kernel<LF>, 256, 0) != hipSuccess || b < 1) return 2048;
-    int per_cu = a < b ? a : b;
-    if (per_cu > 8) per_cu = 8;
-    return per_cu * prop.multiProcessorCount / 8 * 8;
-  }();
+  static const int cap = bgnn_bwd::resident_cap(agg_bwd_dst_kernel<LF>, agg_bwd_src_kernel<LF>);
   const int64_t nmax = p.N + (p.d_nv > p.s_nv ? p.d_nv : p.s_nv);
-  const int64_t ntiles = (nmax + RPB - 1) / RPB;
-  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;
-  if (grid < 8) grid = 8;
-  hipLaunchKernelGGL((agg_bwd_dst_kernel<LF>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  const unsigned grid = bgnn_bwd::resident_grid((nmax + RPB - 1) / RPB, cap);
+  hipLaunchKernelGGL((agg_bwd_dst_kernel<LF>), dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  if (hubs && hubs->d_nh > 0) {            // the hub destinations' dstside rows, before pass B reads them
-    PullMergeParams m{hubs->d_rows, hubs->d_seg_ptr, hubs->d_nh, p.ldh, p.d_vpart, nullptr, p.mask, p.dstside, nullptr, nullptr};
-    hipLaunchKernelGGL(pull_merge_dst_kernel, dim3((unsigned)((hubs->d_nh * (p.ldh / 4) + 255) / 256)), dim3(256), 0, st, m);
-    BGNN_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL((agg_bwd_src_kernel<LF>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  // the hub destinations' dstside rows, before pass B reads them
+  if (const int rc = bgnn_bwd::pull_merge_dst_launch(hubs, p.ldh, p.d_vpart, p.mask, p.dstside, st)) return rc;
+  hipLaunchKernelGGL((agg_bwd_src_kernel<LF>), dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  if (hubs && hubs->s_nh > 0) {
-    PullMergeParams m{hubs->s_rows, hubs->s_seg_ptr, hubs->s_nh, p.ldh, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t};
-    hipLaunchKernelGGL(pull_merge_src_kernel, dim3((unsigned)((hubs->s_nh * (p.ldh / 4) + 255) / 256)), dim3(256), 0, st, m);
-    BGNN_LAUNCH_CHECK();
-  }
-  return 0;
+  return bgnn_bwd::pull_merge_src_launch(hubs, p.ldh, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t, st);
+}
+
+// workspace of the single-head entry: D <= 128: records (32 bytes per edge) | dstside | queue | hub segment rows
+PullLayout pull_layout(int64_t N, int64_t E, int64_t ldh, int32_t D, int64_t d_nv, int64_t s_nv) {
+  if (D > 128) return bgnn_bwd::pull_wide_plan(N, E, ldh, d_nv, s_nv);
+  const size_t n = (size_t)(N > 0 ? N : 0), e = (size_t)(E > 0 ? E : 0), l = (size_t)(ldh > 0 ? ldh : 0);
+  const size_t dv = (size_t)(d_nv > 0 ? d_nv : 0), sv = (size_t)(s_nv > 0 ? s_nv : 0);
+  PullLayout w{};
+  w.dstside = bgnn_align_up((size_t)32 * e, 256);
+  w.queue = w.dstside + bgnn_align_up(sizeof(float) * n * l, 256);
+  w.seg = w.queue + 256;
+  w.total = w.seg + bgnn_align_up(sizeof(float) * l * (dv + 2 * sv), 256);
+  return w;
+}
+
+// ... of the heads entry (nothing per edge is kept): node records (3 * heads float4 per node) | dstside | hub segment rows
+PullLayout heads_layout(int64_t N, int32_t heads, int64_t d_nv, int64_t s_nv) {
+  const size_t n = (size_t)(N > 0 ? N : 0), h = (size_t)(heads > 0 ? heads : 0);
+  const size_t dv = (size_t)(d_nv > 0 ? d_nv : 0), sv = (size_t)(s_nv > 0 ? s_nv : 0);
+  PullLayout w{};
+  w.dstside = bgnn_align_up(sizeof(float4) * n * 3 * h, 256);
+  w.seg = w.dstside + bgnn_align_up(sizeof(float) * n * h * 4, 256);
+  w.total = w.seg + bgnn_align_up(sizeof(float) * h * 4 * (dv + 2 * sv), 256) + 256;     // (never 0: the entry wants a workspace)
+  return w;
 }
 
 }  // namespace
 
-int bgnn_bwd::pull_merge_dst_launch(const PullParams& p, const int32_t* hub_rows, const int32_t* seg_ptr, int64_t n_hubs, hipStream_t st) {
-  PullMergeParams m{hub_rows, seg_ptr, n_hubs, p.ldh, p.d_vpart, nullptr, p.mask, p.dstside, nullptr, nullptr};
-  hipLaunchKernelGGL(pull_merge_dst_kernel, dim3((unsigned)((n_hubs * (p.ldh / 4) + 255) / 256)), dim3(256), 0, st, m);
+int bgnn_bwd::pull_merge_dst_launch(const PullHubs& hubs, int64_t ld, const float* d_vpart, const uint8_t* mask, float* dstside,
+                                    hipStream_t st) {
+  if (hubs.d_nh <= 0) return 0;
+  PullMergeParams m{hubs.d_rows, hubs.d_seg_ptr, hubs.d_nh, ld, d_vpart, nullptr, mask, dstside, nullptr, nullptr};
+  hipLaunchKernelGGL(pull_merge_dst_kernel, dim3((unsigned)((hubs.d_nh * (ld / 4) + 255) / 256)), dim3(256), 0, st, m);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
-int bgnn_bwd::pull_merge_src_launch(const PullParams& p, const int32_t* hub_rows, const int32_t* seg_ptr, int64_t n_hubs, hipStream_t st) {
-  PullMergeParams m{hub_rows, seg_ptr, n_hubs, p.ldh, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t};
-  hipLaunchKernelGGL(pull_merge_src_kernel, dim3((unsigned)((n_hubs * (p.ldh / 4) + 255) / 256)), dim3(256), 0, st, m);
+int bgnn_bwd::pull_merge_src_launch(const PullHubs& hubs, int64_t ld, const float* s_vpartS, const float* s_vpartT, const uint8_t* mask,
+                                    float* dstside, float* dh_t2s, float* dh_s2t, hipStream_t st) {
+  if (hubs.s_nh <= 0) return 0;
+  PullMergeParams m{hubs.s_rows, hubs.s_seg_ptr, hubs.s_nh, ld, s_vpartS, s_vpartT, mask, dstside, dh_t2s, dh_s2t};
+  hipLaunchKernelGGL(pull_merge_src_kernel, dim3((unsigned)((hubs.s_nh * (ld / 4) + 255) / 256)), dim3(256), 0, st, m);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
@@ -863,51 +857,9 @@ extern "C" int bgnn_adaptedconv_aggregate_bwd_f32(const float* h_t2s, const floa
   return launch_bwd<64, 2>(p, st);
 }
 
-extern "C" size_t bgnn_aggregate_bwd_pull_workspace_bytes(int64_t N, int64_t E, int64_t ldh) {
-  return (size_t)32 * (size_t)(E > 0 ? E : 0) + sizeof(float) * (size_t)(N > 0 ? N : 0) * (size_t)(ldh > 0 ? ldh : 0) + 1024;
-}
-
-static int pull_impl(const float* h_t2s, const float* h_s2t, int64_t ldh, const float* a_t2s, const float* a_s2t,
-                     const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                     const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                     int64_t N, int64_t E, int32_t D, float negative_slope, const float* out, int64_t ldo, const float* alpha,
-                     const float* grad_out, int64_t ldg, float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                     int32_t hub_threshold, const PullHubs* hubs, const int32_t* d_vbounds, const int32_t* d_vnode, int64_t d_nv,
-                     const int32_t* s_vbounds, const int32_t* s_vnode, int64_t s_nv, void* ws, size_t ws_bytes, void* stream) {
-  if (!h_t2s || !h_s2t || !a_t2s || !a_s2t || !rowptr || !col || !mask || !t_rowptr || !t_eid || !t_dst || !out || !alpha ||
-      !grad_out || !dh_t2s || !dh_s2t || !da_t2s || !da_s2t || !ws)
-    return BGNN_E_NULL;
-  const bool narrow = D >= 1 && D <= 4 && ldh == 4 && ldo == 4 && ldg == 4;
-  if (N < 0 || E < 0 || D < 1 || D > 128 || ldh < D || ldo < D || ldg < D || (ldh & 3) || (ldo & 3) || (ldg & 3)) return BGNN_E_SHAPE;
-  if (hubs && (narrow || hub_threshold < 2 || d_nv < 0 || s_nv < 0)) return BGNN_E_SHAPE;
-  if (!bgnn_aligned16(h_t2s) || !bgnn_aligned16(h_s2t) || !bgnn_aligned16(out) || !bgnn_aligned16(grad_out) ||
-      !bgnn_aligned16(dh_t2s) || !bgnn_aligned16(dh_s2t) || !bgnn_aligned16(ws))
-    return BGNN_E_ALIGN;
-  const size_t base_bytes = bgnn_aggregate_bwd_pull_workspace_bytes(N, E, ldh);
-  const size_t seg_bytes = hubs ? bgnn_align_up(sizeof(float) * (size_t)ldh * (size_t)(d_nv + 2 * s_nv), 256) + 256 : 0;
-  if (ws_bytes < base_bytes + seg_bytes) return BGNN_E_WORKSPACE;
-  if (N == 0) return 0;
-  uint4* rec = (uint4*)ws;
-  float* dstside = (float*)((char*)ws + bgnn_align_up((size_t)32 * (size_t)E, 256));
-  unsigned int* queue = (unsigned int*)((char*)dstside + bgnn_align_up(sizeof(float) * (size_t)N * (size_t)ldh, 256));
-  PullParams p{h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, N, D, negative_slope, out, ldo, alpha, grad_out, ldg,
-               t_rowptr, t_eid, t_dst, rec, queue, dstside, dh_t2s, dh_s2t, da_t2s, da_s2t};
-  if (hubs) {
-    float* seg = (float*)((char*)ws + bgnn_align_up(base_bytes, 256));
-    p.hub_threshold = hub_threshold;
-    p.d_vnode = d_vnode; p.d_vbounds = d_vbounds; p.d_nv = d_nv; p.d_vpart = seg;
-    p.s_vnode = s_vnode; p.s_vbounds = s_vbounds; p.s_nv = s_nv; p.s_vpartS = seg + (size_t)d_nv * ldh; p.s_vpartT = seg + (size_t)(d_nv + s_nv) * ldh;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (bgnn_zero_async(queue, 16 * sizeof(unsigned int), st) != hipSuccess) return (int)hipErrorInvalidValue;
-  if (narrow) return launch_pull_narrow(p, st);
-  const int nv = (D + 3) / 4;
-  p.E = E;
-  if (!hubs && nv > 16 && bgnn_bwd::pull_fast_plan(p)) return bgnn_bwd::pull_fast_launch(p, st);
-  if (nv <= 2) return launch_pull<2>(p, st, hubs);
-  if (nv <= 4) return launch_pull<4>(p, st, hubs);
-  if (nv <= 8) return launch_pull<8>(p, st, hubs);
-  return nv <= 16 ? launch_pull<16>(p, st, hubs) : launch_pull<32>(p, st, hubs);
+extern "C" size_t bgnn_aggregate_bwd_pull_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int32_t D, int64_t d_segments,
+                                                          int64_t s_segments) {
+  return pull_layout(N, E, ldh, D, d_segments, s_segments).total;
 }
 
 extern "C" int bgnn_adaptedconv_aggregate_bwd_pull_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
@@ -918,120 +870,84 @@ extern "C" int bgnn_adaptedconv_aggregate_bwd_pull_f32(const float* h_t2s, const
                                                        const float* out, int64_t ldo, const float* alpha,
                                                        const float* grad_out, int64_t ldg,
                                                        float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
+                                                       int32_t hub_threshold,
+                                                       const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
+                                                       const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
+                                                       const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
+                                                       const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
                                                        void* ws, size_t ws_bytes, void* stream) {
-  return pull_impl(h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, t_rowptr, t_eid, t_dst, N, E, D, negative_slope, out, ldo,
-                   alpha, grad_out, ldg, dh_t2s, dh_s2t, da_t2s, da_s2t, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0,
-                   ws, ws_bytes, stream);
-}
-
-extern "C" size_t bgnn_aggregate_bwd_pull_hub_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int64_t d_segments, int64_t s_segments) {
-  const size_t nseg = (size_t)(d_segments > 0 ? d_segments : 0) + 2 * (size_t)(s_segments > 0 ? s_segments : 0);
-  return bgnn_align_up(bgnn_aggregate_bwd_pull_workspace_bytes(N, E, ldh), 256) +
-         bgnn_align_up(sizeof(float) * (size_t)(ldh > 0 ? ldh : 0) * nseg, 256) + 512;
-}
-
-extern "C" int bgnn_adaptedconv_aggregate_bwd_pull_hub_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
-                                                           const float* a_t2s, const float* a_s2t,
-                                                           const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                           const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                                           int64_t N, int64_t E, int32_t D, float negative_slope,
-                                                           const float* out, int64_t ldo, const float* alpha,
-                                                           const float* grad_out, int64_t ldg,
-                                                           float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                                                           int32_t hub_threshold,
-                                                           const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
-                                                           const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
-                                                           const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
-                                                           const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
-                                                           void* ws, size_t ws_bytes, void* stream) {
-  if (d_n_hubs < 0 || s_n_hubs < 0 || d_n_segments < d_n_hubs || s_n_segments < s_n_hubs) return BGNN_E_SHAPE;
-  if ((d_n_hubs > 0 && (!d_hub_rows || !d_hub_seg_ptr || !d_seg_bounds || !d_seg_node)) ||
-      (s_n_hubs > 0 && (!s_hub_rows || !s_hub_seg_ptr || !s_seg_bounds || !s_seg_node)))
-    return BGNN_E_NULL;
-  PullHubs hubs{d_hub_rows, d_hub_seg_ptr, d_n_hubs, s_hub_rows, s_hub_seg_ptr, s_n_hubs};
-  return pull_impl(h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, t_rowptr, t_eid, t_dst, N, E, D, negative_slope, out, ldo,
-                   alpha, grad_out, ldg, dh_t2s, dh_s2t, da_t2s, da_s2t, hub_threshold, &hubs,
-                   d_seg_bounds, d_seg_node, d_n_hubs > 0 ? d_n_segments : 0, s_seg_bounds, s_seg_node, s_n_hubs > 0 ? s_n_segments : 0,
-                   ws, ws_bytes, stream);
-}
-
-extern "C" size_t bgnn_aggregate_heads_bwd_workspace_bytes(int64_t N, int64_t E, int32_t heads) {
-  (void)E;                                       // nothing per edge is kept
-  const size_t n = (size_t)(N > 0 ? N : 0), h = (size_t)(heads > 0 ? heads : 0);
-  return bgnn_align_up(sizeof(float4) * n * 3 * h, 256) + bgnn_align_up(sizeof(float) * n * h * 4, 256) + 256;
-}
-
-static int heads_bwd_impl(const float* h_t2s, const float* h_s2t, const float* a_t2s, const float* a_s2t,
-                          const int32_t* rowptr, const int32_t* col, const uint8_t* mask, const int32_t* t_rowptr, const int32_t* t_dst,
-                          int64_t N, int64_t E, int32_t D, int32_t heads, float negative_slope, const float* out, const float* state_ms,
-                          const float* grad_out, int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                          int32_t hub_threshold, const PullHubs* hubs, const int32_t* d_vbounds, const int32_t* d_vnode, int64_t d_nv,
-                          const int32_t* s_vbounds, const int32_t* s_vnode, int64_t s_nv, void* ws, size_t ws_bytes, void* stream) {
-  if (!h_t2s || !h_s2t || !a_t2s || !a_s2t || !rowptr || !col || !mask || !t_rowptr || !t_dst || !out || !state_ms ||
+  if (!h_t2s || !h_s2t || !a_t2s || !a_s2t || !rowptr || !col || !mask || !t_rowptr || !t_eid || !t_dst || !out || !alpha ||
       !grad_out || !dh_t2s || !dh_s2t || !da_t2s || !da_s2t || !ws)
     return BGNN_E_NULL;
-  if (N < 0 || E < 0 || D < 1 || D > 4 || (heads != 2 && heads != 3)) return BGNN_E_SHAPE;
-  if (hubs && (hub_threshold < 2 || d_nv < 0 || s_nv < 0)) return BGNN_E_SHAPE;
+  if (N < 0 || E < 0 || D < 1 || D > 256 || ldh < D || ldo < D || ldg < D || (ldh & 3) || (ldo & 3) || (ldg & 3)) return BGNN_E_SHAPE;
+  PullHubs hubs{hub_threshold, d_hub_rows, d_n_hubs, d_hub_seg_ptr, d_seg_bounds, d_seg_node, d_n_segments,
+                s_hub_rows, s_n_hubs, s_hub_seg_ptr, s_seg_bounds, s_seg_node, s_n_segments};
+  if (const int rc = bgnn_bwd::pull_hubs_check(hubs)) return rc;
+  const bool narrow = D <= 4 && ldh == 4 && ldo == 4 && ldg == 4;
+  if (narrow && hubs.any()) return BGNN_E_SHAPE;     // the narrow kernels know no segments
   if (!bgnn_aligned16(h_t2s) || !bgnn_aligned16(h_s2t) || !bgnn_aligned16(out) || !bgnn_aligned16(grad_out) ||
       !bgnn_aligned16(dh_t2s) || !bgnn_aligned16(dh_s2t) || !bgnn_aligned16(ws))
     return BGNN_E_ALIGN;
-  const size_t base_bytes = bgnn_aggregate_heads_bwd_workspace_bytes(N, E, heads);
-  const size_t seg_bytes = hubs ? bgnn_align_up(sizeof(float) * (size_t)heads * 4 * (size_t)(d_nv + 2 * s_nv), 256) + 256 : 0;
-  if (ws_bytes < base_bytes + seg_bytes) return BGNN_E_WORKSPACE;
-  if (N == 0) return 0;
-  float4* node = (float4*)ws;
-  float* dstside = (float*)((char*)ws + bgnn_align_up(sizeof(float4) * (size_t)N * 3 * (size_t)heads, 256));
-  HeadsBwdParams p{h_t2s, h_s2t, a_t2s, a_s2t, rowptr, col, mask, N, D, negative_slope, out, state_ms, grad_out, log_softmax,
-                   t_rowptr, t_dst, node, dstside, dh_t2s, dh_s2t, da_t2s, da_s2t};
-  if (hubs) {
-    float* seg = (float*)((char*)ws + bgnn_align_up(base_bytes, 256));
-    const size_t ld = (size_t)heads * 4;
-    p.hub_threshold = hub_threshold;
-    p.d_vnode = d_vnode; p.d_vbounds = d_vbounds; p.d_nv = d_nv; p.d_vpart = seg;
-    p.s_vnode = s_vnode; p.s_vbounds = s_vbounds; p.s_nv = s_nv; p.s_vpartS = seg + (size_t)d_nv * ld; p.s_vpartT = seg + (size_t)(d_nv + s_nv) * ld;
-  }
+  const PullLayout w = pull_layout(N, E, ldh, D, hubs.d_nv, hubs.s_nv);
+  if (ws_bytes < w.total) return BGNN_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  return heads == 3 ? launch_heads_bwd<3>(p, st, hubs) : launch_heads_bwd<2>(p, st, hubs);
+  if (N == 0) {                                      // no rows: nothing to add for D <= 128; the D > 128 pair writes da (zeros)
+    if (D <= 128) return 0;
+    hipError_t e = bgnn_zero_async(da_t2s, sizeof(float) * (size_t)D, st);
+    if (e == hipSuccess) e = bgnn_zero_async(da_s2t, sizeof(float) * (size_t)D, st);
+    return (int)e;
+  }
+  char* base = (char*)ws;
+  PullParams p{h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, N, D, negative_slope, out, ldo, alpha, grad_out, ldg,
+               t_rowptr, t_eid, t_dst, (uint4*)(base + w.rec), (unsigned int*)(base + w.queue), (float*)(base + w.dstside),
+               dh_t2s, dh_s2t, da_t2s, da_s2t};
+  p.E = E;
+  bgnn_bwd::pull_set_hubs(p, hubs, (float*)(base + w.seg), ldh);
+  if (bgnn_zero_async(p.queue, 16 * sizeof(unsigned int), st) != hipSuccess) return (int)hipErrorInvalidValue;
+  if (narrow) return launch_pull_narrow(p, st);
+  const int nv = (D + 3) / 4;
+  if (nv > 32) return bgnn_bwd::pull_wide_launch(p, hubs, w, ws, st);
+  if (nv > 16 && bgnn_bwd::pull_fast_plan(p)) return bgnn_bwd::pull_fast_launch(p, st);     // (refuses hub rows itself)
+  if (nv <= 2) return launch_pull<2>(p, hubs, st);
+  if (nv <= 4) return launch_pull<4>(p, hubs, st);
+  if (nv <= 8) return launch_pull<8>(p, hubs, st);
+  return nv <= 16 ? launch_pull<16>(p, hubs, st) : launch_pull<32>(p, hubs, st);
+}
+
+extern "C" size_t bgnn_aggregate_heads_bwd_workspace_bytes(int64_t N, int64_t E, int32_t heads, int64_t d_segments, int64_t s_segments) {
+  (void)E;                                       // nothing per edge is kept
+  return heads_layout(N, heads, d_segments, s_segments).total;
 }
 
 extern "C" int bgnn_adaptedconv_aggregate_heads_bwd_f32(const float* h_t2s, const float* h_s2t, const float* a_t2s, const float* a_s2t,
                                                         const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                        const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
+                                                        const int32_t* t_rowptr, const int32_t* t_dst,
                                                         int64_t N, int64_t E, int32_t D, int32_t heads, float negative_slope,
                                                         const float* out, const float* state_ms, const float* grad_out,
-                                                        int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s,
-                                                        float* da_s2t, void* ws, size_t ws_bytes, void* stream) {
-  (void)t_eid;                                   // (kept in the signature: the by-source view is passed as one triple everywhere)
-  return heads_bwd_impl(h_t2s, h_s2t, a_t2s, a_s2t, rowptr, col, mask, t_rowptr, t_dst, N, E, D, heads, negative_slope, out, state_ms,
-                        grad_out, log_softmax, dh_t2s, dh_s2t, da_t2s, da_s2t, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0,
-                        ws, ws_bytes, stream);
-}
-
-extern "C" size_t bgnn_aggregate_heads_bwd_hub_workspace_bytes(int64_t N, int64_t E, int32_t heads, int64_t d_segments, int64_t s_segments) {
-  const size_t nseg = (size_t)(d_segments > 0 ? d_segments : 0) + 2 * (size_t)(s_segments > 0 ? s_segments : 0);
-  return bgnn_align_up(bgnn_aggregate_heads_bwd_workspace_bytes(N, E, heads), 256) +
-         bgnn_align_up(sizeof(float) * (size_t)(heads > 0 ? heads : 0) * 4 * nseg, 256) + 512;
-}
-
-extern "C" int bgnn_adaptedconv_aggregate_heads_bwd_hub_f32(const float* h_t2s, const float* h_s2t, const float* a_t2s, const float* a_s2t,
-                                                            const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                            const int32_t* t_rowptr, const int32_t* t_dst,
-                                                            int64_t N, int64_t E, int32_t D, int32_t heads, float negative_slope,
-                                                            const float* out, const float* state_ms, const float* grad_out,
-                                                            int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                                                            int32_t hub_threshold,
-                                                            const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
-                                                            const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
-                                                            const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
-                                                            const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
-                                                            void* ws, size_t ws_bytes, void* stream) {
-  if (d_n_hubs < 0 || s_n_hubs < 0 || d_n_segments < d_n_hubs || s_n_segments < s_n_hubs) return BGNN_E_SHAPE;
-  if ((d_n_hubs > 0 && (!d_hub_rows || !d_hub_seg_ptr || !d_seg_bounds || !d_seg_node)) ||
-      (s_n_hubs > 0 && (!s_hub_rows || !s_hub_seg_ptr || !s_seg_bounds || !s_seg_node)))
+                                                        int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
+                                                        int32_t hub_threshold,
+                                                        const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
+                                                        const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
+                                                        const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
+                                                        const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
+                                                        void* ws, size_t ws_bytes, void* stream) {
+  if (!h_t2s || !h_s2t || !a_t2s || !a_s2t || !rowptr || !col || !mask || !t_rowptr || !t_dst || !out || !state_ms ||
+      !grad_out || !dh_t2s || !dh_s2t || !da_t2s || !da_s2t || !ws)
     return BGNN_E_NULL;
-  PullHubs hubs{d_hub_rows, d_hub_seg_ptr, d_n_hubs, s_hub_rows, s_hub_seg_ptr, s_n_hubs};
-  return heads_bwd_impl(h_t2s, h_s2t, a_t2s, a_s2t, rowptr, col, mask, t_rowptr, t_dst, N, E, D, heads, negative_slope, out, state_ms,
-                        grad_out, log_softmax, dh_t2s, dh_s2t, da_t2s, da_s2t, hub_threshold, &hubs,
-                        d_seg_bounds, d_seg_node, d_n_hubs > 0 ? d_n_segments : 0, s_seg_bounds, s_seg_node, s_n_hubs > 0 ? s_n_segments : 0,
-                        ws, ws_bytes, stream);
+  if (N < 0 || E < 0 || D < 1 || D > 4 || (heads != 2 && heads != 3)) return BGNN_E_SHAPE;
+  PullHubs hubs{hub_threshold, d_hub_rows, d_n_hubs, d_hub_seg_ptr, d_seg_bounds, d_seg_node, d_n_segments,
+                s_hub_rows, s_n_hubs, s_hub_seg_ptr, s_seg_bounds, s_seg_node, s_n_segments};
+  if (const int rc = bgnn_bwd::pull_hubs_check(hubs)) return rc;
+  if (!bgnn_aligned16(h_t2s) || !bgnn_aligned16(h_s2t) || !bgnn_aligned16(out) || !bgnn_aligned16(grad_out) ||
+      !bgnn_aligned16(dh_t2s) || !bgnn_aligned16(dh_s2t) || !bgnn_aligned16(ws))
+    return BGNN_E_ALIGN;
+  const PullLayout w = heads_layout(N, heads, hubs.d_nv, hubs.s_nv);
+  if (ws_bytes < w.total) return BGNN_E_WORKSPACE;
+  if (N == 0) return 0;
+  char* base = (char*)ws;
+  HeadsBwdParams p{h_t2s, h_s2t, a_t2s, a_s2t, rowptr, col, mask, N, D, negative_slope, out, state_ms, grad_out, log_softmax,
+                   t_rowptr, t_dst, (float4*)(base + w.rec), (float*)(base + w.dstside), dh_t2s, dh_s2t, da_t2s, da_s2t};
+  bgnn_bwd::pull_set_hubs(p, hubs, (float*)(base + w.seg), (int64_t)heads * 4);
+  hipStream_t st = (hipStream_t)stream;
+  return heads == 3 ? launch_heads_bwd<3>(p, hubs, st) : launch_heads_bwd<2>(p, hubs, st);
 }

@@ -359,20 +359,6 @@ __global__ __launch_bounds__(256) void agg_bwd_src_fast_kernel(PullParams p) {
   }
 }
 
-int resident_cap() {
-  static const int cap = [] {
-    int a = 0, b = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, agg_bwd_dst_fast_kernel, 256, 0) != hipSuccess || a < 1) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, agg_bwd_src_fast_kernel, 256, 0) != hipSuccess || b < 1) return 2048;
-    int per_cu = a < b ? a : b;
-    if (per_cu > 8) per_cu = 8;
-    return per_cu * prop.multiProcessorCount / 8 * 8;
-  }();
-  return cap;
-}
-
 }  // namespace
 
 namespace bgnn_bwd {
@@ -402,12 +388,11 @@ bool pull_fast_plan(PullParams& p) {
 int pull_fast_launch(const PullParams& p, hipStream_t st) {
   constexpr int RPB = 8;
   const int64_t ntiles = (p.N + RPB - 1) / RPB;
-  const int64_t cap = resident_cap();
-  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;
-  if (grid < 8) grid = 8;
-  hipLaunchKernelGGL(agg_bwd_dst_fast_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
+  static const int cap = resident_cap(agg_bwd_dst_fast_kernel, agg_bwd_src_fast_kernel);
+  const unsigned grid = resident_grid(ntiles, cap);
+  hipLaunchKernelGGL(agg_bwd_dst_fast_kernel, dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(agg_bwd_src_fast_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(agg_bwd_src_fast_kernel, dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }

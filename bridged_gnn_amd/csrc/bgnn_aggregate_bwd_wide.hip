@@ -301,15 +301,15 @@ __global__ __launch_bounds__(256) void agg_bwd_src_wide_kernel(PullParams p) {
   }
 }
 
-// workspace: records | dstside | queue | da chunk rows | da slice rows | hub segment rows
-struct WideLayout {
-  size_t rec, dstside, queue, da_part, da_stage, seg, total;
-  int64_t nparts;
-};
-WideLayout wide_layout(int64_t N, int64_t E, int64_t ldh, int64_t d_nv, int64_t s_nv) {
+}  // namespace
+
+namespace bgnn_bwd {
+
+// workspace: records (64 bytes per edge) | dstside | queue | da chunk rows | da slice rows | hub segment rows
+PullLayout pull_wide_plan(int64_t N, int64_t E, int64_t ldh, int64_t d_nv, int64_t s_nv) {
   const size_t n = (size_t)(N > 0 ? N : 0), e = (size_t)(E > 0 ? E : 0), l = (size_t)(ldh > 0 ? ldh : 0);
   const size_t dv = (size_t)(d_nv > 0 ? d_nv : 0), sv = (size_t)(s_nv > 0 ? s_nv : 0);
-  WideLayout w;
+  PullLayout w;
   w.nparts = 8 * chunks_per_xcd((int64_t)((n + dv + RPB - 1) / RPB));
   w.rec = 0;
   w.dstside = w.rec + bgnn_align_up((size_t)64 * e, 256);
@@ -321,104 +321,34 @@ WideLayout wide_layout(int64_t N, int64_t E, int64_t ldh, int64_t d_nv, int64_t 
   return w;
 }
 
-}  // namespace
-
-extern "C" size_t bgnn_aggregate_bwd_pull_wide_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int64_t d_segments, int64_t s_segments) {
-  return wide_layout(N, E, ldh, d_segments, s_segments).total;
-}
-
-extern "C" int bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
-                                                            const float* a_t2s, const float* a_s2t,
-                                                            const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                            const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                                            int64_t N, int64_t E, int32_t D, float negative_slope,
-                                                            const float* out, int64_t ldo, const float* alpha,
-                                                            const float* grad_out, int64_t ldg,
-                                                            float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                                                            int32_t hub_threshold,
-                                                            const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
-                                                            const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
-                                                            const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
-                                                            const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
-                                                            void* ws, size_t ws_bytes, void* stream) {
-  if (!h_t2s || !h_s2t || !a_t2s || !a_s2t || !rowptr || !col || !mask || !t_rowptr || !t_eid || !t_dst || !out || !alpha ||
-      !grad_out || !dh_t2s || !dh_s2t || !da_t2s || !da_s2t || !ws)
-    return BGNN_E_NULL;
-  if (N < 0 || E < 0 || D <= 128 || D > 256 || ldh < D || ldo < D || ldg < D || (ldh & 3) || (ldo & 3) || (ldg & 3)) return BGNN_E_SHAPE;
-  if (d_n_hubs < 0 || s_n_hubs < 0 || (d_n_hubs > 0 && d_n_segments < d_n_hubs) || (s_n_hubs > 0 && s_n_segments < s_n_hubs)) return BGNN_E_SHAPE;
-  const bool hubs = d_n_hubs > 0 || s_n_hubs > 0;
-  if (hubs && hub_threshold < 2) return BGNN_E_SHAPE;
-  if ((d_n_hubs > 0 && (!d_hub_rows || !d_hub_seg_ptr || !d_seg_bounds || !d_seg_node)) ||
-      (s_n_hubs > 0 && (!s_hub_rows || !s_hub_seg_ptr || !s_seg_bounds || !s_seg_node)))
-    return BGNN_E_NULL;
-  if (!bgnn_aligned16(h_t2s) || !bgnn_aligned16(h_s2t) || !bgnn_aligned16(out) || !bgnn_aligned16(grad_out) ||
-      !bgnn_aligned16(dh_t2s) || !bgnn_aligned16(dh_s2t) || !bgnn_aligned16(ws))
-    return BGNN_E_ALIGN;
-  const int64_t d_nv = d_n_hubs > 0 ? d_n_segments : 0, s_nv = s_n_hubs > 0 ? s_n_segments : 0;
-  const WideLayout w = wide_layout(N, E, ldh, d_nv, s_nv);
-  if (ws_bytes < w.total) return BGNN_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (N == 0) {                                      // no rows: da is still written (zeros)
-    hipError_t e = bgnn_zero_async(da_t2s, sizeof(float) * (size_t)D, st);
-    if (e == hipSuccess) e = bgnn_zero_async(da_s2t, sizeof(float) * (size_t)D, st);
-    return (int)e;
-  }
-  char* base = (char*)ws;
-  PullParams p{h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, N, D, negative_slope, out, ldo, alpha, grad_out, ldg,
-               t_rowptr, t_eid, t_dst, (uint4*)(base + w.rec), (unsigned int*)(base + w.queue), (float*)(base + w.dstside),
-               dh_t2s, dh_s2t, da_t2s, da_s2t};
-  p.E = E;
-  if (hubs) {
-    float* seg = (float*)(base + w.seg);
-    p.hub_threshold = hub_threshold;
-    p.d_vnode = d_seg_node; p.d_vbounds = d_seg_bounds; p.d_nv = d_nv; p.d_vpart = seg;
-    p.s_vnode = s_seg_node; p.s_vbounds = s_seg_bounds; p.s_nv = s_nv;
-    p.s_vpartS = seg + (size_t)d_nv * ldh; p.s_vpartT = seg + (size_t)(d_nv + s_nv) * ldh;
-  }
-  float* da_part = (float*)(base + w.da_part);
-  float* da_stage = (float*)(base + w.da_stage);
-  if (bgnn_zero_async(p.queue, 16 * sizeof(unsigned int), st) != hipSuccess) return (int)hipErrorInvalidValue;
-
-  static const int cap = [] {
-    int a = 0, b = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, agg_bwd_dst_wide_kernel, 256, 0) != hipSuccess || a < 1) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, agg_bwd_src_wide_kernel, 256, 0) != hipSuccess || b < 1) return 2048;
-    int per_cu = a < b ? a : b;
-    if (per_cu > 8) per_cu = 8;
-    return per_cu * prop.multiProcessorCount / 8 * 8;
-  }();
-  const int64_t nmax = N + (d_nv > s_nv ? d_nv : s_nv);
-  const int64_t ntiles = (nmax + RPB - 1) / RPB;
-  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;
-  if (grid < 8) grid = 8;
-  hipLaunchKernelGGL(agg_bwd_dst_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, p, da_part);
+int pull_wide_launch(const PullParams& p, const PullHubs& hubs, const PullLayout& w, void* ws, hipStream_t st) {
+  float* da_part = (float*)((char*)ws + w.da_part);
+  float* da_stage = (float*)((char*)ws + w.da_stage);
+  static const int cap = resident_cap(agg_bwd_dst_wide_kernel, agg_bwd_src_wide_kernel);
+  const int64_t nmax = p.N + (p.d_nv > p.s_nv ? p.d_nv : p.s_nv);
+  const unsigned grid = resident_grid((nmax + RPB - 1) / RPB, cap);
+  hipLaunchKernelGGL(agg_bwd_dst_wide_kernel, dim3(grid), dim3(256), 0, st, p, da_part);
   BGNN_LAUNCH_CHECK();
-  if (d_n_hubs > 0) {                      // the hub destinations' dstside rows, before pass B reads them
-    const int rc = bgnn_bwd::pull_merge_dst_launch(p, d_hub_rows, d_hub_seg_ptr, d_n_hubs, st);
-    if (rc != 0) return rc;
-  }
+  // the hub destinations' dstside rows, before pass B reads them
+  if (const int rc = pull_merge_dst_launch(hubs, p.ldh, p.d_vpart, p.mask, p.dstside, st)) return rc;
   // da: the chunk rows in a fixed order (two stages above DA_DIRECT rows)
-  const int W = (int)(2 * ldh);
+  const int W = (int)(2 * p.ldh);
   const unsigned cb = (unsigned)((W + 63) / 64);
   const float* src = da_part;
   int64_t rows = w.nparts;
   if (rows > DA_DIRECT) {
     const int64_t per = (rows + DA_SLICES - 1) / DA_SLICES, slices = (rows + per - 1) / per;
     hipLaunchKernelGGL(pull_wide_da_kernel, dim3(cb, (unsigned)slices), dim3(256), 0, st, src, rows, per, W, da_stage,
-                       (float*)nullptr, (float*)nullptr, (int)ldh, (int)D);
+                       (float*)nullptr, (float*)nullptr, (int)p.ldh, (int)p.D);
     BGNN_LAUNCH_CHECK();
     src = da_stage; rows = slices;
   }
-  hipLaunchKernelGGL(pull_wide_da_kernel, dim3(cb, 1), dim3(256), 0, st, src, rows, rows, W, (float*)nullptr, da_t2s, da_s2t,
-                     (int)ldh, (int)D);
+  hipLaunchKernelGGL(pull_wide_da_kernel, dim3(cb, 1), dim3(256), 0, st, src, rows, rows, W, (float*)nullptr, p.da_t2s, p.da_s2t,
+                     (int)p.ldh, (int)p.D);
   BGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(agg_bwd_src_wide_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(agg_bwd_src_wide_kernel, dim3(grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
-  if (s_n_hubs > 0) {
-    const int rc = bgnn_bwd::pull_merge_src_launch(p, s_hub_rows, s_hub_seg_ptr, s_n_hubs, st);
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return pull_merge_src_launch(hubs, p.ldh, p.s_vpartS, p.s_vpartT, p.mask, p.dstside, p.dh_t2s, p.dh_s2t, st);
 }
+
+}  // namespace bgnn_bwd

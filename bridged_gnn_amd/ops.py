@@ -661,6 +661,19 @@ def adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, negative_
     return (out, alpha) if want_alpha else out
 
 
+def _bwd_hub_args(csr, use=True):
+    """-> (args, nd, ns): the hub-table argument group of the two pull-form backward entries (bgnn.h) for `csr` -- threshold, then
+    per side (d_*: destinations, s_*: sources) rows, count, seg_ptr, seg_bounds, seg_node, segment count -- and the two segment
+    counts for the workspace query.  A side without hub rows, `use=False` or BGNN_HUB_ROWS=0: its zero-hubs group."""
+    use = use and os.environ.get("BGNN_HUB_ROWS", "1") != "0"
+    args, nseg = [HUB_THRESHOLD], []
+    for tables in ((csr.hub_tables(), csr.transposed_hub_tables()) if use else (None, None)):
+        rows, seg_ptr, bounds, node = tables if tables is not None else (None, None, None, None)
+        nseg.append(0 if tables is None else int(node.numel()))
+        args += [L.ptr(rows), 0 if tables is None else int(rows.numel()), L.ptr(seg_ptr), L.ptr(bounds), L.ptr(node), nseg[-1]]
+    return args, nseg[0], nseg[1]
+
+
 def adaptedconv_aggregate_bwd(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, out, alpha, grad_out, negative_slope=0.1):
     """-> (dh_t2s, dh_s2t, da_t2s, da_s2t): gradients of the fused aggregation w.r.t. both tables and
     both attention vectors (reference: autograd through models/KTGNN.py:292-305)."""
@@ -669,70 +682,33 @@ def adaptedconv_aggregate_bwd(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, out, 
     da_t2s = torch.zeros(D, dtype=torch.float32, device=dev)
     da_s2t = torch.zeros(D, dtype=torch.float32, device=dev)
     grad_out = grad_out.contiguous()
-    if D <= 128 and grad_out.stride(0) % 4 == 0 and grad_out.data_ptr() % 16 == 0 and h_t2s.shape[0] == csr.num_nodes:
-        # atomic-free pull over the by-source CSR (float atomics retire at ~1.3 TB/s on MI355X); 128 < D <= 256 takes the wide
-        # pair further down, the atomic form remains for row ranges
+    ldh, ldo, ldg = h_t2s.stride(0), out.stride(0), grad_out.stride(0)
+    # atomic-free pull over the by-source CSR (float atomics retire at ~1.3 TB/s on MI355X; for D > 128 da is summed in a fixed
+    # order too, so all four gradients are bitwise reproducible): whole-graph calls with an aligned grad_out.  Row ranges keep the
+    # atomic form below, and so do misaligned tables / out at D > 128 (at D <= 128 the entry refuses them).
+    pull = D <= 256 and ldg % 4 == 0 and grad_out.data_ptr() % 16 == 0 and h_t2s.shape[0] == csr.num_nodes
+    if pull and D > 128:
+        pull = (ldh % 4 == 0 and ldo % 4 == 0 and h_t2s.data_ptr() % 16 == 0 and h_s2t.data_ptr() % 16 == 0
+                and out.data_ptr() % 16 == 0)
+    if pull:
         t_rowptr, t_eid, t_dst = csr.transposed()
         dh_t2s, dh_s2t = torch.empty_like(h_t2s), torch.empty_like(h_s2t)
-        narrow = D <= 4 and h_t2s.stride(0) == 4 and out.stride(0) == 4 and grad_out.stride(0) == 4
-        dh_, sh_ = (csr.hub_tables(), csr.transposed_hub_tables()) if (not narrow and os.environ.get("BGNN_HUB_ROWS", "1") != "0") else (None, None)
-        if dh_ is not None or sh_ is not None:      # graphs with hub rows: segments + merge (bgnn.h)
-            none4 = (None, None, None, None)
-            d_rows, d_ptr, d_bounds, d_node = dh_ if dh_ is not None else none4
-            s_rows, s_ptr, s_bounds, s_node = sh_ if sh_ is not None else none4
-            nd = 0 if dh_ is None else int(d_node.numel())
-            ns = 0 if sh_ is None else int(s_node.numel())
-            wsb = lib.bgnn_aggregate_bwd_pull_hub_workspace_bytes(csr.num_nodes, csr.num_edges, h_t2s.stride(0), nd, ns)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            rc = lib.bgnn_adaptedconv_aggregate_bwd_pull_hub_f32(
-                L.ptr(h_t2s), L.ptr(h_s2t), h_t2s.stride(0), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
-                L.ptr(mask_u8), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), csr.num_nodes, csr.num_edges, D, float(negative_slope),
-                L.ptr(out), out.stride(0), L.ptr(alpha), L.ptr(grad_out), grad_out.stride(0),
-                L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), HUB_THRESHOLD,
-                L.ptr(d_rows), 0 if dh_ is None else int(d_rows.numel()), L.ptr(d_ptr), L.ptr(d_bounds), L.ptr(d_node), nd,
-                L.ptr(s_rows), 0 if sh_ is None else int(s_rows.numel()), L.ptr(s_ptr), L.ptr(s_bounds), L.ptr(s_node), ns,
-                L.ptr(ws), wsb, L.stream())
-            L.check(rc, "bgnn_adaptedconv_aggregate_bwd_pull_hub_f32")
-            return dh_t2s, dh_s2t, da_t2s, da_s2t
-        wsb = lib.bgnn_aggregate_bwd_pull_workspace_bytes(csr.num_nodes, csr.num_edges, h_t2s.stride(0))
+        narrow = D <= 4 and ldh == 4 and ldo == 4 and ldg == 4              # (the narrow kernels know no hub segments)
+        hub_args, nd, ns = _bwd_hub_args(csr, use=not narrow)
+        wsb = lib.bgnn_aggregate_bwd_pull_workspace_bytes(csr.num_nodes, csr.num_edges, ldh, D, nd, ns)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         rc = lib.bgnn_adaptedconv_aggregate_bwd_pull_f32(
-            L.ptr(h_t2s), L.ptr(h_s2t), h_t2s.stride(0), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
+            L.ptr(h_t2s), L.ptr(h_s2t), ldh, L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
             L.ptr(mask_u8), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), csr.num_nodes, csr.num_edges, D, float(negative_slope),
-            L.ptr(out), out.stride(0), L.ptr(alpha), L.ptr(grad_out), grad_out.stride(0),
-            L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), L.ptr(ws), wsb, L.stream())
+            L.ptr(out), ldo, L.ptr(alpha), L.ptr(grad_out), ldg,
+            L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), *hub_args, L.ptr(ws), wsb, L.stream())
         L.check(rc, "bgnn_adaptedconv_aggregate_bwd_pull_f32")
-        return dh_t2s, dh_s2t, da_t2s, da_s2t
-    if (128 < D <= 256 and grad_out.stride(0) % 4 == 0 and grad_out.data_ptr() % 16 == 0 and h_t2s.shape[0] == csr.num_nodes
-            and h_t2s.stride(0) % 4 == 0 and out.stride(0) % 4 == 0
-            and h_t2s.data_ptr() % 16 == 0 and h_s2t.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0):
-        # the same pull form, a whole wave per row (bgnn_aggregate_bwd_wide.hip): no float atomics, da summed in a fixed order --
-        # all four gradients bitwise reproducible.  Row ranges and misaligned operands keep the atomic form below.
-        t_rowptr, t_eid, t_dst = csr.transposed()
-        dh_t2s, dh_s2t = torch.empty_like(h_t2s), torch.empty_like(h_s2t)
-        dh_, sh_ = (csr.hub_tables(), csr.transposed_hub_tables()) if os.environ.get("BGNN_HUB_ROWS", "1") != "0" else (None, None)
-        none4 = (None, None, None, None)
-        d_rows, d_ptr, d_bounds, d_node = dh_ if dh_ is not None else none4
-        s_rows, s_ptr, s_bounds, s_node = sh_ if sh_ is not None else none4
-        nd = 0 if dh_ is None else int(d_node.numel())
-        ns = 0 if sh_ is None else int(s_node.numel())
-        wsb = lib.bgnn_aggregate_bwd_pull_wide_workspace_bytes(csr.num_nodes, csr.num_edges, h_t2s.stride(0), nd, ns)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        rc = lib.bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(
-            L.ptr(h_t2s), L.ptr(h_s2t), h_t2s.stride(0), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
-            L.ptr(mask_u8), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), csr.num_nodes, csr.num_edges, D, float(negative_slope),
-            L.ptr(out), out.stride(0), L.ptr(alpha), L.ptr(grad_out), grad_out.stride(0),
-            L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), HUB_THRESHOLD,
-            L.ptr(d_rows), 0 if dh_ is None else int(d_rows.numel()), L.ptr(d_ptr), L.ptr(d_bounds), L.ptr(d_node), nd,
-            L.ptr(s_rows), 0 if sh_ is None else int(s_rows.numel()), L.ptr(s_ptr), L.ptr(s_bounds), L.ptr(s_node), ns,
-            L.ptr(ws), wsb, L.stream())
-        L.check(rc, "bgnn_adaptedconv_aggregate_bwd_pull_wide_f32")
         return dh_t2s, dh_s2t, da_t2s, da_s2t
     dh_t2s, dh_s2t = torch.zeros_like(h_t2s), torch.zeros_like(h_s2t)
     rc = lib.bgnn_adaptedconv_aggregate_bwd_f32(
-        L.ptr(h_t2s), L.ptr(h_s2t), h_t2s.stride(0), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
-        L.ptr(mask_u8), 0, csr.num_nodes, D, float(negative_slope), L.ptr(out), out.stride(0), L.ptr(alpha),
-        L.ptr(grad_out), grad_out.stride(0), L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), L.stream())
+        L.ptr(h_t2s), L.ptr(h_s2t), ldh, L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
+        L.ptr(mask_u8), 0, csr.num_nodes, D, float(negative_slope), L.ptr(out), ldo, L.ptr(alpha),
+        L.ptr(grad_out), ldg, L.ptr(dh_t2s), L.ptr(dh_s2t), L.ptr(da_t2s), L.ptr(da_s2t), L.stream())
     L.check(rc, "bgnn_adaptedconv_aggregate_bwd_f32")
     return dh_t2s, dh_s2t, da_t2s, da_s2t
 
@@ -748,33 +724,15 @@ def adaptedconv_aggregate_heads_bwd(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, hea
     da_t2s = torch.zeros(heads, D, dtype=torch.float32, device=dev)
     da_s2t = torch.zeros(heads, D, dtype=torch.float32, device=dev)
     dh_t2s, dh_s2t = torch.empty_like(t2s), torch.empty_like(s2t)
-    t_rowptr, t_eid, t_dst = csr.transposed()
-    dh_, sh_ = (csr.hub_tables(), csr.transposed_hub_tables()) if os.environ.get("BGNN_HUB_ROWS", "1") != "0" else (None, None)
-    if dh_ is not None or sh_ is not None:          # graphs with hub rows: segments + merges (bgnn.h)
-        none4 = (None, None, None, None)
-        d_rows, d_ptr, d_bounds, d_node = dh_ if dh_ is not None else none4
-        s_rows, s_ptr, s_bounds, s_node = sh_ if sh_ is not None else none4
-        nd = 0 if dh_ is None else int(d_node.numel())
-        ns = 0 if sh_ is None else int(s_node.numel())
-        wsb = lib.bgnn_aggregate_heads_bwd_hub_workspace_bytes(N, csr.num_edges, heads, nd, ns)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        rc = lib.bgnn_adaptedconv_aggregate_heads_bwd_hub_f32(
-            L.ptr(t2s), L.ptr(s2t), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col), L.ptr(mask_u8),
-            L.ptr(t_rowptr), L.ptr(t_dst), N, csr.num_edges, D, heads, float(negative_slope),
-            L.ptr(out), L.ptr(state_ms), L.ptr(grad_out), int(bool(log_softmax)), L.ptr(dh_t2s), L.ptr(dh_s2t),
-            L.ptr(da_t2s), L.ptr(da_s2t), HUB_THRESHOLD,
-            L.ptr(d_rows), 0 if dh_ is None else int(d_rows.numel()), L.ptr(d_ptr), L.ptr(d_bounds), L.ptr(d_node), nd,
-            L.ptr(s_rows), 0 if sh_ is None else int(s_rows.numel()), L.ptr(s_ptr), L.ptr(s_bounds), L.ptr(s_node), ns,
-            L.ptr(ws), wsb, L.stream())
-        L.check(rc, "bgnn_adaptedconv_aggregate_heads_bwd_hub_f32")
-        return dh_t2s, dh_s2t, da_t2s, da_s2t
-    wsb = lib.bgnn_aggregate_heads_bwd_workspace_bytes(N, csr.num_edges, heads)
+    t_rowptr, _, t_dst = csr.transposed()
+    hub_args, nd, ns = _bwd_hub_args(csr)               # graphs with hub rows: segments + merges (bgnn.h)
+    wsb = lib.bgnn_aggregate_heads_bwd_workspace_bytes(N, csr.num_edges, heads, nd, ns)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     rc = lib.bgnn_adaptedconv_aggregate_heads_bwd_f32(
         L.ptr(t2s), L.ptr(s2t), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col), L.ptr(mask_u8),
-        L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), N, csr.num_edges, D, heads, float(negative_slope),
+        L.ptr(t_rowptr), L.ptr(t_dst), N, csr.num_edges, D, heads, float(negative_slope),
         L.ptr(out), L.ptr(state_ms), L.ptr(grad_out), int(bool(log_softmax)), L.ptr(dh_t2s), L.ptr(dh_s2t),
-        L.ptr(da_t2s), L.ptr(da_s2t), L.ptr(ws), wsb, L.stream())
+        L.ptr(da_t2s), L.ptr(da_s2t), *hub_args, L.ptr(ws), wsb, L.stream())
     L.check(rc, "bgnn_adaptedconv_aggregate_heads_bwd_f32")
     return dh_t2s, dh_s2t, da_t2s, da_s2t
 

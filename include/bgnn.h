@@ -34,8 +34,11 @@ extern "C" {
  * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
  * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size, and for the GCN baseline's
  * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for partitioned GCN's
- * bgnn_gcn_aggregate_rows_f32. */
-#define BGNN_VERSION 113
+ * bgnn_gcn_aggregate_rows_f32.
+ * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
+ * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
+ * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone. */
+#define BGNN_VERSION 114
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
 #define BGNN_E_WORKSPACE (-3)   /* ws_bytes smaller than *_workspace_bytes()    */
@@ -346,11 +349,24 @@ int bgnn_adaptedconv_aggregate_bwd_f32(const float* h_t2s, const float* h_s2t, i
                                        float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
                                        void* stream);
 
-/* Atomic-free ("pull") form of the same backward for D <= 128: the source-side sums are gathered over a by-source
- * view of the edges (t_rowptr [N+1]; t_eid [E'] = position of the edge in the by-destination order; t_dst [E'] = its
- * destination) instead of scattered with float atomics; every dH row is written exactly once (no zero-fill needed,
- * deterministic).  All N rows are visited; ws: bgnn_aggregate_bwd_pull_workspace_bytes(N, E', ldh). */
-size_t bgnn_aggregate_bwd_pull_workspace_bytes(int64_t N, int64_t E, int64_t ldh);
+/* Atomic-free ("pull") form of the same backward, 1 <= D <= 256 (ABI 114: one entry for every width, with or without hub rows): the
+ * source-side sums are gathered over a by-source view of the edges (t_rowptr [N+1]; t_eid [E'] = position of the edge in the
+ * by-destination order; t_dst [E'] = its destination) instead of scattered with float atomics; every dH row is written exactly once
+ * (no zero-fill needed, deterministic; pad columns D <= c < ldh are written 0 for D > 128).  All N rows are visited.  ldh / ldo / ldg
+ * are multiples of 4 and at least D, else BGNN_E_SHAPE.
+ * Hub rows: pass A walks destinations, pass B sources: a destination with >= hub_threshold in-edges / a source with that many
+ * out-edges is skipped as a row and walked as segments -- d_* tables over `rowptr` / `col`, s_* tables over the by-source arrays,
+ * both in the layout of bgnn_adaptedconv_aggregate_hub_f32 (hub_rows, hub_seg_ptr, seg_bounds = (begin, end) pairs, seg_node) --
+ * that ride behind the real rows of the same launch and leave partial row sums, merged in a fixed order.  d_n_hubs = s_n_hubs = 0
+ * (tables may then be NULL, hub_threshold is not looked at): no hub rows.  The narrow form (D <= 4 with ldh = ldo = ldg = 4)
+ * knows no segments: BGNN_E_SHAPE with hub tables.
+ * da: for D <= 128 da_t2s / da_s2t are ACCUMULATED into with float atomics (caller zero-fills; N == 0 leaves them untouched); for
+ * D > 128 (a whole wave per row) they are WRITTEN whole, from partial rows summed in a fixed order, so all four outputs of a call
+ * are bitwise reproducible (N == 0 writes zeros).  For D > 128 pad columns of the tables must hold finite values.
+ * ws: bgnn_aggregate_bwd_pull_workspace_bytes(N, E', ldh, D, d_n_segments, s_n_segments) -- a record per edge (32 bytes, 64 for
+ * D > 128), the dstside table, for D > 128 the da partial rows, the hub segments' partial rows; the entry returns
+ * BGNN_E_WORKSPACE exactly when ws_bytes is below that figure. */
+size_t bgnn_aggregate_bwd_pull_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int32_t D, int64_t d_segments, int64_t s_segments);
 int bgnn_adaptedconv_aggregate_bwd_pull_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
                                             const float* a_t2s, const float* a_s2t,
                                             const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
@@ -359,52 +375,12 @@ int bgnn_adaptedconv_aggregate_bwd_pull_f32(const float* h_t2s, const float* h_s
                                             const float* out, int64_t ldo, const float* alpha,
                                             const float* grad_out, int64_t ldg,
                                             float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
+                                            int32_t hub_threshold,
+                                            const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
+                                            const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
+                                            const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
+                                            const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
                                             void* ws, size_t ws_bytes, void* stream);
-
-/* The same pull-form backward for graphs with hub rows (wide rows only: not the ldh = 4 narrow form).  Pass A walks destinations,
- * pass B sources: a destination with >= hub_threshold in-edges / a source with that many out-edges is skipped as a row and walked
- * as segments -- d_* tables over `rowptr` / `col`, s_* tables over the by-source arrays, both in the layout of
- * bgnn_adaptedconv_aggregate_hub_f32 (hub_rows, hub_seg_ptr, seg_bounds = (begin, end) pairs, seg_node) -- that ride behind the real
- * rows of the same launch and leave partial row sums, merged in a fixed order (deterministic like the plain form).
- * ws: bgnn_aggregate_bwd_pull_hub_workspace_bytes(N, E', ldh, d_n_segments, s_n_segments). */
-size_t bgnn_aggregate_bwd_pull_hub_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int64_t d_segments, int64_t s_segments);
-int bgnn_adaptedconv_aggregate_bwd_pull_hub_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
-                                                const float* a_t2s, const float* a_s2t,
-                                                const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                                int64_t N, int64_t E, int32_t D, float negative_slope,
-                                                const float* out, int64_t ldo, const float* alpha,
-                                                const float* grad_out, int64_t ldg,
-                                                float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                                                int32_t hub_threshold,
-                                                const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
-                                                const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
-                                                const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
-                                                const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
-                                                void* ws, size_t ws_bytes, void* stream);
-
-/* The pull-form backward for 128 < D <= 256 (a whole wave per row; the two entries above keep refusing D > 128).  Argument list
- * and hub tables of bgnn_adaptedconv_aggregate_bwd_pull_hub_f32; d_n_hubs = s_n_hubs = 0 (tables may then be NULL): no hub rows.
- * Every dH row is written exactly once (pad columns D <= c < ldh: 0) and da_t2s / da_s2t are WRITTEN, not accumulated: pass A
- * leaves partial da rows that are summed in a fixed order, so all four outputs of a call are bitwise reproducible.  Pad columns
- * of the tables must hold finite values.  BGNN_E_SHAPE: D <= 128, D > 256, or ldh / ldo / ldg below D or not a multiple of 4.
- * ws: bgnn_aggregate_bwd_pull_wide_workspace_bytes(N, E', ldh, d_n_segments, s_n_segments) (64-byte record per edge, the
- * dstside table, the da partial rows, the hub segments' partial rows). */
-size_t bgnn_aggregate_bwd_pull_wide_workspace_bytes(int64_t N, int64_t E, int64_t ldh, int64_t d_segments, int64_t s_segments);
-int bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
-                                                 const float* a_t2s, const float* a_s2t,
-                                                 const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                 const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                                 int64_t N, int64_t E, int32_t D, float negative_slope,
-                                                 const float* out, int64_t ldo, const float* alpha,
-                                                 const float* grad_out, int64_t ldg,
-                                                 float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                                                 int32_t hub_threshold,
-                                                 const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
-                                                 const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
-                                                 const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
-                                                 const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
-                                                 void* ws, size_t ws_bytes, void* stream);
 
 /* Pull-form backward for `heads` (2 or 3) interleaved narrow convs evaluated together (KT-GNN's classifier stage under
  * autograd: clf_base(x), clf_target(x), clf_target(T(x)), KTGNN.py:432-435, share the graph): tables / out / grad_out / dH are
@@ -412,29 +388,21 @@ int bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(const float* h_t2s, const float
  * rows' softmax state (max, sum) that bgnn_adaptedconv_aggregate_f32 leaves with part = 3; alpha is rebuilt from it, no per-edge
  * array is kept by the forward.  log_softmax != 0: `out` holds the fused log-probabilities (ep_relu = 2) and grad_out is
  * dL/dlogp -- the row-local adjoint is applied first.  Every dH row is written exactly once (deterministic).
- * ws: bgnn_aggregate_heads_bwd_workspace_bytes(N, E', heads). */
-size_t bgnn_aggregate_heads_bwd_workspace_bytes(int64_t N, int64_t E, int32_t heads);
+ * Hub tables and the zero-hubs rule as in bgnn_adaptedconv_aggregate_bwd_pull_f32 (partial rows of heads * 4 floats).
+ * ws: bgnn_aggregate_heads_bwd_workspace_bytes(N, E', heads, d_n_segments, s_n_segments), refused exactly below that figure. */
+size_t bgnn_aggregate_heads_bwd_workspace_bytes(int64_t N, int64_t E, int32_t heads, int64_t d_segments, int64_t s_segments);
 int bgnn_adaptedconv_aggregate_heads_bwd_f32(const float* h_t2s, const float* h_s2t, const float* a_t2s, const float* a_s2t,
                                              const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                             const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
+                                             const int32_t* t_rowptr, const int32_t* t_dst,
                                              int64_t N, int64_t E, int32_t D, int32_t heads, float negative_slope,
                                              const float* out, const float* state_ms, const float* grad_out,
-                                             int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s,
-                                             float* da_s2t, void* ws, size_t ws_bytes, void* stream);
-/* ... and for graphs with hub rows (tables as in bgnn_adaptedconv_aggregate_bwd_pull_hub_f32; partial rows of heads * 4 floats). */
-size_t bgnn_aggregate_heads_bwd_hub_workspace_bytes(int64_t N, int64_t E, int32_t heads, int64_t d_segments, int64_t s_segments);
-int bgnn_adaptedconv_aggregate_heads_bwd_hub_f32(const float* h_t2s, const float* h_s2t, const float* a_t2s, const float* a_s2t,
-                                                 const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
-                                                 const int32_t* t_rowptr, const int32_t* t_dst,
-                                                 int64_t N, int64_t E, int32_t D, int32_t heads, float negative_slope,
-                                                 const float* out, const float* state_ms, const float* grad_out,
-                                                 int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
-                                                 int32_t hub_threshold,
-                                                 const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
-                                                 const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
-                                                 const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
-                                                 const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
-                                                 void* ws, size_t ws_bytes, void* stream);
+                                             int log_softmax, float* dh_t2s, float* dh_s2t, float* da_t2s, float* da_s2t,
+                                             int32_t hub_threshold,
+                                             const int32_t* d_hub_rows, int64_t d_n_hubs, const int32_t* d_hub_seg_ptr,
+                                             const int32_t* d_seg_bounds, const int32_t* d_seg_node, int64_t d_n_segments,
+                                             const int32_t* s_hub_rows, int64_t s_n_hubs, const int32_t* s_hub_seg_ptr,
+                                             const int32_t* s_seg_bounds, const int32_t* s_seg_node, int64_t s_n_segments,
+                                             void* ws, size_t ws_bytes, void* stream);
 
 /* The classifier stage's three-head walk for WIDE classes (KT-GNN trained on office, 31 classes; ABI 113, additive): `heads`
  * (2 or 3) interleaved convs, 4 < D <= 32, tables / out [N][heads][ldh] with ldh = pad4(D), a_* [heads][D].  One CSR walk for all

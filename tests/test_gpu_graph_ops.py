@@ -126,11 +126,13 @@ def test_training_entry_points_reject_shapes_outside_their_envelope():
     # rowdot: more than four vectors, d > 256
     assert L.bgnn_rowdot_f32(p(x), 128, 64, 128, p(w), 128, 5, p(o), None) == -2
     assert L.bgnn_rowdot_f32(p(x), 128, 64, 260, p(w), 260, 1, p(o), None) == -2
-    # pull backward: D > 128 has no pull form (the record holds 4 x 32 sign bits per edge)
+    # pull backward: the one entry takes 1 <= D <= 256 (above 128 a wave per row, 8 x 32 sign bits per edge); D = 260 has no form.
+    # The refusal comes before any launch, so the 128-column buffers serve.
     i32 = torch.zeros(8, dtype=torch.int32, device=DEV)
     m = torch.zeros(8, dtype=torch.uint8, device=DEV)
-    rc = L.bgnn_adaptedconv_aggregate_bwd_pull_f32(p(x), p(x), 132, p(b), p(b), p(i32), p(i32), p(m), p(i32), p(i32), p(i32), 4, 0, 132, 0.1,
-                                                   p(x), 132, p(b), p(x), 132, p(o), p(o), p(b), p(b), p(ws), ws.numel(), None)
+    no_hubs = (0, None, 0, None, None, None, 0, None, 0, None, None, None, 0)
+    rc = L.bgnn_adaptedconv_aggregate_bwd_pull_f32(p(x), p(x), 260, p(b), p(b), p(i32), p(i32), p(m), p(i32), p(i32), p(i32), 4, 0, 260, 0.1,
+                                                   p(x), 260, p(b), p(x), 260, p(o), p(o), p(b), p(b), *no_hubs, p(ws), ws.numel(), None)
     assert rc == -2
 
 

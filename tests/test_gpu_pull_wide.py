@@ -1,6 +1,7 @@
-"""GPU: the atomic-free aggregation backward for 128 < D <= 256 (bgnn_adaptedconv_aggregate_bwd_pull_wide_f32,
-csrc/bgnn_aggregate_bwd_wide.hip): ABI envelope, fp64 autograd on the same tables, the atomic scatter form, hub rows against the
-plain walk, bitwise reproducibility and the route `ops.adaptedconv_aggregate_bwd` takes."""
+"""GPU: the atomic-free aggregation backward for 128 < D <= 256 (the wave-per-row route of bgnn_adaptedconv_aggregate_bwd_pull_f32,
+csrc/bgnn_aggregate_bwd_wide.hip): ABI envelope and the border to the D <= 128 routes, fp64 autograd on the same tables, the atomic
+scatter form, hub rows against the plain walk, bitwise reproducibility and the route `ops.adaptedconv_aggregate_bwd` takes; and
+for both pull entries, that the advertised workspace is the accepted one."""
 import functools
 
 import numpy as np
@@ -58,31 +59,39 @@ def _op(c):
     return ops.adaptedconv_aggregate_bwd(c["hS"], c["hT"], c["a1"], c["a2"], c["csr"], c["m8"], c["D"], c["out"], c["alpha"], c["g"], SLOPE)
 
 
-def _direct(c, D=None, ld=None, hubs=True, ws_bytes=None):
-    """bgnn_adaptedconv_aggregate_bwd_pull_wide_f32 called through ctypes -> (rc, (dh_t2s, dh_s2t, da_t2s, da_s2t))"""
+def _hub_args(csr, hubs=True):
+    """the hub-table argument group of the pull entries (bgnn.h) and the two segment counts"""
     from bridged_gnn_amd import _lib, ops
+    P = _lib.ptr
+    args, nseg = [ops.HUB_THRESHOLD], []
+    for tables in ((csr.hub_tables(), csr.transposed_hub_tables()) if hubs else (None, None)):
+        rows, seg_ptr, bounds, node = tables if tables is not None else (None, None, None, None)
+        nseg.append(0 if tables is None else int(node.numel()))
+        args += [P(rows), 0 if tables is None else int(rows.numel()), P(seg_ptr), P(bounds), P(node), nseg[-1]]
+    return args, nseg[0], nseg[1]
+
+
+def _direct(c, D=None, ld=None, hubs=True, ws_bytes=None, ws_short=0):
+    """bgnn_adaptedconv_aggregate_bwd_pull_f32 called through ctypes -> (rc, (dh_t2s, dh_s2t, da_t2s, da_s2t)); the workspace
+    size claimed is `ws_bytes`, by default the advertised one less `ws_short`.  Outputs are NaN-prefilled (every element must be
+    written), but da for D <= 128, which is accumulated into, is zeroed as its contract says."""
+    from bridged_gnn_amd import _lib
     L = _lib.lib()
     P = _lib.ptr
     csr, n = c["csr"], c["n"]
     D = c["D"] if D is None else D
     ld = c["ld"] if ld is None else ld
     t_rowptr, t_eid, t_dst = csr.transposed()
-    dh_, sh_ = (csr.hub_tables(), csr.transposed_hub_tables()) if hubs else (None, None)
-    none4 = (None, None, None, None)
-    d_rows, d_ptr, d_bounds, d_node = dh_ if dh_ is not None else none4
-    s_rows, s_ptr, s_bounds, s_node = sh_ if sh_ is not None else none4
-    nd = 0 if dh_ is None else int(d_node.numel())
-    ns = 0 if sh_ is None else int(s_node.numel())
-    wsb = L.bgnn_aggregate_bwd_pull_wide_workspace_bytes(n, csr.num_edges, ld, nd, ns)
+    hub_args, nd, ns = _hub_args(csr, hubs)
+    wsb = L.bgnn_aggregate_bwd_pull_workspace_bytes(n, csr.num_edges, ld, D, nd, ns)
     ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    d1, d2 = torch.full_like(c["hS"], float("nan")), torch.full_like(c["hT"], float("nan"))      # every element must be written
-    da1, da2 = torch.full((D,), float("nan"), device=DEV), torch.full((D,), float("nan"), device=DEV)
-    rc = L.bgnn_adaptedconv_aggregate_bwd_pull_wide_f32(
+    d1, d2 = torch.full_like(c["hS"], float("nan")), torch.full_like(c["hT"], float("nan"))
+    fill = float("nan") if D > 128 else 0.0
+    da1, da2 = torch.full((max(D, 1),), fill, device=DEV), torch.full((max(D, 1),), fill, device=DEV)
+    rc = L.bgnn_adaptedconv_aggregate_bwd_pull_f32(
         P(c["hS"]), P(c["hT"]), ld, P(c["a1"]), P(c["a2"]), P(csr.rowptr), P(csr.col), P(c["m8"]), P(t_rowptr), P(t_eid), P(t_dst),
-        n, csr.num_edges, D, SLOPE, P(c["out"]), ld, P(c["alpha"]), P(c["g"]), ld, P(d1), P(d2), P(da1), P(da2), ops.HUB_THRESHOLD,
-        P(d_rows), 0 if dh_ is None else int(d_rows.numel()), P(d_ptr), P(d_bounds), P(d_node), nd,
-        P(s_rows), 0 if sh_ is None else int(s_rows.numel()), P(s_ptr), P(s_bounds), P(s_node), ns,
-        P(ws), wsb if ws_bytes is None else ws_bytes, _lib.stream())
+        n, csr.num_edges, D, SLOPE, P(c["out"]), ld, P(c["alpha"]), P(c["g"]), ld, P(d1), P(d2), P(da1), P(da2), *hub_args,
+        P(ws), wsb - ws_short if ws_bytes is None else ws_bytes, _lib.stream())
     torch.cuda.synchronize()
     return rc, (d1, d2, da1, da2)
 
@@ -145,22 +154,85 @@ def _tiny_case(D):
     return _forward(_inputs(ei, np.array([True, False, True, False]), 4, D, seed=D))
 
 
+def _assert_whole_and_fp64(c, got):
+    D = c["D"]
+    for t in got:
+        assert bool(torch.isfinite(t).all())
+    for name, a, b in zip(("dh_t2s", "dh_s2t", "da_t2s", "da_s2t"), got, _fp64(c)):
+        assert _rel(a[..., :D].double().cpu(), b) < 2e-5, name
+
+
 def test_abi_envelope():
-    """0 inside the envelope (D = 132 on a 4-node graph, every output element written); BGNN_E_SHAPE at D = 128, D = 260 and
+    """0 inside the envelope (D = 132 on a 4-node graph, every output element written); BGNN_E_SHAPE at D = 0, D = 260 and
     ldh = 134; BGNN_E_WORKSPACE with a 16-byte workspace."""
     c = _tiny_case(132)
     rc, got = _direct(c)
     assert rc == 0
-    for t in got:
-        assert bool(torch.isfinite(t).all())
-    ref = _fp64(c)
-    for name, a, b in zip(("dh_t2s", "dh_s2t", "da_t2s", "da_s2t"), got, ref):
-        assert _rel(a[..., :132].double().cpu(), b) < 2e-5, name
+    _assert_whole_and_fp64(c, got)
     # the refusals come before any launch, so the same 132-column buffers serve (the claimed widths are never walked)
     assert _direct(c, ws_bytes=16)[0] == -3
-    assert _direct(c, D=128)[0] == -2
+    assert _direct(c, D=0)[0] == -2
     assert _direct(c, D=260, ld=260)[0] == -2
     assert _direct(c, ld=134)[0] == -2
+
+
+@pytest.mark.parametrize("D", [128, 129])
+def test_entry_at_the_border_of_the_wide_route(D):
+    """the one entry on either side of D = 128 (lane groups of 32 | a wave per row) on the 4-node graph: 0, every element of the
+    NaN-prefilled outputs written (da of D = 128, which is accumulated into, zeroed beforehand), fp64 at 2e-5"""
+    c = _tiny_case(D)
+    rc, got = _direct(c)
+    assert rc == 0
+    _assert_whole_and_fp64(c, got)
+
+
+def _untouched(got, D):
+    return all(bool(torch.isnan(t).all()) for t in got[:2]) and all(bool((torch.isnan(t) if D > 128 else t == 0).all()) for t in got[2:])
+
+
+@pytest.mark.parametrize("graph,D", [("tiny", 2), ("tiny", 16), ("tiny", 100), ("tiny", 160), ("hub", 100), ("hub", 160)])
+def test_advertised_workspace_is_the_accepted_workspace(graph, D):
+    """bgnn_aggregate_bwd_pull_workspace_bytes is exactly what the entry accepts: one byte less is BGNN_E_WORKSPACE with
+    nothing launched (the prefilled outputs stay as they were), the advertised size runs"""
+    c = _tiny_case(D) if graph == "tiny" else _hub_case(D)
+    rc, got = _direct(c, ws_short=1)
+    assert rc == -3 and _untouched(got, D)
+    rc, got = _direct(c)
+    assert rc == 0 and bool(torch.isfinite(got[0]).all())
+
+
+@pytest.mark.parametrize("graph", ["tiny", "hub"])
+def test_advertised_heads_workspace_is_the_accepted_workspace(graph):
+    """the same for bgnn_aggregate_heads_bwd_workspace_bytes / bgnn_adaptedconv_aggregate_heads_bwd_f32 at heads = 3, D = 2"""
+    from bridged_gnn_amd import _lib, ops
+    L, P, heads, D = _lib.lib(), _lib.ptr, 3, 2
+    base = _tiny_case(4) if graph == "tiny" else _hub_case(4)          # (the graph; the tables below are the heads' own)
+    csr, m8, n = base["csr"], base["m8"], base["n"]
+    g = torch.Generator(device=DEV).manual_seed(5)
+    t2s, s2t, gr = (torch.zeros(n, heads * 4, device=DEV) for _ in range(3))
+    for t in (t2s, s2t, gr):
+        for h in range(heads):
+            t[:, 4 * h:4 * h + D] = torch.randn(n, D, device=DEV, generator=g)
+    a1, a2 = torch.randn(heads, D, device=DEV, generator=g) * 0.3, torch.randn(heads, D, device=DEV, generator=g) * 0.3
+    ms = torch.zeros(n, heads, 2, device=DEV)
+    out = ops.adaptedconv_aggregate(t2s, s2t, a1, a2, csr, m8, D, SLOPE, heads=heads, log_softmax=True, state_ms=ms, part=3)
+    t_rowptr, _, t_dst = csr.transposed()
+    hub_args, nd, ns = _hub_args(csr)
+    assert (nd > 0 and ns > 0) == (graph == "hub")
+    wsb = L.bgnn_aggregate_heads_bwd_workspace_bytes(n, csr.num_edges, heads, nd, ns)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+    for claimed, want in ((wsb - 1, -3), (wsb, 0)):
+        d1, d2 = torch.full_like(t2s, float("nan")), torch.full_like(s2t, float("nan"))
+        da1, da2 = torch.zeros(heads, D, device=DEV), torch.zeros(heads, D, device=DEV)
+        rc = L.bgnn_adaptedconv_aggregate_heads_bwd_f32(
+            P(t2s), P(s2t), P(a1), P(a2), P(csr.rowptr), P(csr.col), P(m8), P(t_rowptr), P(t_dst), n, csr.num_edges, D, heads, SLOPE,
+            P(out), P(ms), P(gr), 1, P(d1), P(d2), P(da1), P(da2), *hub_args, P(ws), claimed, _lib.stream())
+        torch.cuda.synchronize()
+        assert rc == want
+        if want == 0:
+            assert bool(torch.isfinite(d1).all()) and bool(torch.isfinite(d2).all())
+        else:
+            assert bool(torch.isnan(d1).all()) and bool(torch.isnan(d2).all()) and not bool(da1.any()) and not bool(da2.any())
 
 
 @pytest.mark.parametrize("D", sorted(CASES))

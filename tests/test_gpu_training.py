@@ -330,7 +330,7 @@ def test_three_head_aggregation_backward_equals_three_single_heads(D, n, seed):
 @pytest.mark.parametrize("D,seed", [(128, 0), (64, 1), (36, 2), (16, 3)])
 def test_pull_backward_with_hub_segments_equals_the_plain_pull(D, seed, monkeypatch):
     """Graphs with hub rows (in-degree and out-degree >= ops.HUB_THRESHOLD): the segmented pull backward
-    (bgnn_adaptedconv_aggregate_bwd_pull_hub_f32) equals the plain one to fp32 rounding in every output, and is deterministic."""
+    (bgnn_adaptedconv_aggregate_bwd_pull_f32 with hub tables) equals the plain one to fp32 rounding in every output, and is deterministic."""
     from bridged_gnn_amd import ops, synth
     n = 3000
     ei, mask = synth.random_multigraph(n, 6 * n, frac_src=0.4, n_isolated=2, seed=seed)
@@ -363,7 +363,7 @@ def test_pull_backward_with_hub_segments_equals_the_plain_pull(D, seed, monkeypa
 @pytest.mark.parametrize("D,heads,seed", [(2, 3, 0), (4, 2, 1), (3, 3, 2)])
 def test_heads_backward_with_hub_segments_equals_the_plain_one(D, heads, seed, monkeypatch):
     """the interleaved-heads pull backward on a graph with in- and out-degree hubs: segments + fixed-order merges
-    (bgnn_adaptedconv_aggregate_heads_bwd_hub_f32) == the plain kernels (fp32 rounding), deterministic."""
+    (bgnn_adaptedconv_aggregate_heads_bwd_f32 with hub tables) == the plain kernels (fp32 rounding), deterministic."""
     from bridged_gnn_amd import ops, synth
     n = 3000
     ei, mask = synth.random_multigraph(n, 6 * n, frac_src=0.4, n_isolated=2, seed=seed)

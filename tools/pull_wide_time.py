@@ -1,5 +1,5 @@
 """Timing of the aggregation backward at 128 < D <= 256 on the C4-shaped graph (bench.py's generator: 1M nodes / ~21M edges):
-the atomic-free pair (bgnn_adaptedconv_aggregate_bwd_pull_wide_f32: pass A + merge + da sum + pass B + merge) against the
+the atomic-free pair (bgnn_adaptedconv_aggregate_bwd_pull_f32 at these widths: pass A + merge + da sum + pass B + merge) against the
 atomic scatter form (zero-fill of both dH tables + bgnn_adaptedconv_aggregate_bwd_f32, what `ops.adaptedconv_aggregate_bwd` did at
 these widths before), one device-event interval per call, the two forms alternating in one process.  Prints ONE JSON line:
   widths[D] -- median / min / p10 / p90 ms of both forms, `spread_ms` = the larger p10..p90 range of the two, `gain_ms` = scatter

@@ -18,12 +18,13 @@ g = t(rng.standard_normal((n, D)).astype(np.float32))
 lib = L.lib()
 E = csr.num_edges
 t_rowptr, t_eid, t_dst = csr.transposed()
-wsb = lib.bgnn_aggregate_bwd_pull_workspace_bytes(n, E, D)
+wsb = lib.bgnn_aggregate_bwd_pull_workspace_bytes(n, E, D, D, 0, 0)
 ws = torch.zeros(wsb, dtype=torch.uint8, device=DEV)
 dS, dT = torch.empty_like(hS), torch.empty_like(hT)
 da1, da2 = torch.zeros(D, device=DEV), torch.zeros(D, device=DEV)
 rc = lib.bgnn_adaptedconv_aggregate_bwd_pull_f32(L.ptr_rows(hS), L.ptr_rows(hT), D, L.ptr(a1), L.ptr(a2), L.ptr(csr.rowptr), L.ptr(csr.col), L.ptr(m8),
-        L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), n, E, D, 0.1, L.ptr(out), D, L.ptr(alpha), L.ptr(g), D, L.ptr(dS), L.ptr(dT), L.ptr(da1), L.ptr(da2), L.ptr(ws), wsb, L.stream())
+        L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), n, E, D, 0.1, L.ptr(out), D, L.ptr(alpha), L.ptr(g), D, L.ptr(dS), L.ptr(dT), L.ptr(da1), L.ptr(da2),
+        0, None, 0, None, None, None, 0, None, 0, None, None, None, 0, L.ptr(ws), wsb, L.stream())   # no hub rows
 print("rc", rc)
 torch.cuda.synchronize()
 rec = ws[:32 * E].view(torch.int32).view(E, 8).cpu()
