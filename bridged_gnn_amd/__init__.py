@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("GCNNet", "GCNConv"):
         from . import gcn
         return getattr(gcn, name)
+    if name in ("GAT", "GATConv"):                     # the GAT baseline's, likewise
+        from . import gat
+        return getattr(gat, name)
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)

@@ -9,7 +9,7 @@ from . import _lib as L
 
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
-           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "gcn_aggregate", "gcn_aggregate_bwd", "wide_heads_supported",
+           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "gcn_aggregate", "gcn_aggregate_bwd", "gat_scores", "gat_aggregate", "gat_aggregate_bwd", "wide_heads_supported",
            "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd", "pair_csr", "pair_mlp_stats", "pair_mlp_loss",
            "pair_mlp_segsum", "pair_mlp_eval", "pair_mlp_count", "PAIR_MLP_WIDTH", "pair_cos_loss", "pair_cos_segsum", "pair_cos_count",
            "PAIR_COS_WIDTH"]
@@ -1007,6 +1007,145 @@ def gcn_aggregate_bwd(y, grad_y, t_rowptr, t_col, dinv, n_src, D, epilogue=None,
         L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.stream())
     L.check(rc, "bgnn_gcn_aggregate_bwd_f32")
     return grad_tbl, (column_sums(g)[:D] if want_bias else None)
+
+
+GAT_EPILOGUES = {None: 0, "none": 0, "elu": 1, "log_softmax": 2}
+GAT_MAX_HEADS, GAT_MAX_C = 8, 128
+
+
+def _gat_check(tbl, H, C, what):
+    H, C = int(H), int(C)
+    if not tbl.is_cuda:
+        raise RuntimeError(f"bridged_gnn_amd ops need CUDA(HIP) tensors; there is no CPU path (got a {tbl.device} tensor)")
+    if not (1 <= H <= GAT_MAX_HEADS and 1 <= C <= GAT_MAX_C):
+        raise RuntimeError(f"{what}: unsupported shape: heads = {H}, channels per head = {C} (1 <= heads <= {GAT_MAX_HEADS}, "
+                           f"1 <= channels <= {GAT_MAX_C})")
+    if tbl.dtype != torch.float32 or tbl.dim() != 2 or tbl.shape[1] < pad4(H * C):
+        raise ValueError(f"{what}: the table must be float32 [N, >= pad4(H*C)]")
+    return H, C
+
+
+def _gat_need(t, what, shape, dtype=torch.float32):
+    """an operand of the GAT entry points: dtype, exact shape and contiguity, before its raw pointer goes to a kernel"""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} (got {t.dtype} {tuple(t.shape)})")
+
+
+def _gat_need_rows(t, what, rows, width):
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < width or t.stride(1) != 1:
+        raise ValueError(f"{what} must be float32 [{rows}, >= {width}] with unit column stride (got {t.dtype} {tuple(t.shape)})")
+
+
+def _gat_need_seed_word(w, what):
+    if w is not None and (w.dtype != torch.int64 or w.numel() != 1):
+        raise ValueError(f"{what} must be an int64 device tensor of one element")
+
+
+def _seed_args(seed, seed_dev):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, (L.ptr(seed_dev) if seed_dev is not None else None)
+
+
+def gat_scores(tbl, att_src, att_dst, H, C):
+    """s_src[n,h] = <tbl[n,h,:], att_src[h,:]>, s_dst likewise (models/backbones.py:404-438 -> GATConv's alpha_src / alpha_dst;
+    bgnn.h: bgnn_gat_scores_f32) -> two float32 [N, H] in one read of tbl [N, >= pad4(H*C)].  att_*: float32 with H*C elements."""
+    H, C = _gat_check(tbl, H, C, "gat_scores")
+    a_s, a_d = att_src.reshape(-1).contiguous(), att_dst.reshape(-1).contiguous()
+    if a_s.dtype != torch.float32 or a_d.dtype != torch.float32 or a_s.numel() != H * C or a_d.numel() != H * C:
+        raise ValueError("att_src / att_dst must be float32 with H*C elements")
+    if a_s.data_ptr() % 16:
+        a_s = a_s.clone()
+    if a_d.data_ptr() % 16:
+        a_d = a_d.clone()
+    N = int(tbl.shape[0])
+    s_src = torch.empty(N, H, dtype=torch.float32, device=tbl.device)
+    s_dst = torch.empty(N, H, dtype=torch.float32, device=tbl.device)
+    rc = L.lib().bgnn_gat_scores_f32(L.ptr_rows(tbl), tbl.stride(0), N, H, C, L.ptr(a_s), L.ptr(a_d), L.ptr(s_src), L.ptr(s_dst),
+                                     L.stream())
+    L.check(rc, "bgnn_gat_scores_f32")
+    return s_src, s_dst
+
+
+def gat_aggregate(tbl, s_src, s_dst, rowptr, col, n_rows, H, C, bias=None, negative_slope=0.2, p_att=0.0, seed_att=0,
+                  seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_pre=False, return_alpha=False):
+    """GAT attention aggregation (models/backbones.py:404-438, bgnn.h: bgnn_gat_aggregate_f32) over a CSR that holds one self loop per
+    row (`build_dst_csr(rewrite_self_loops=True)`): out[i,h,:] = epi(sum_t a~[t,h] * tbl[col[t],h,:] + bias[h,:]) with
+    a~ = softmax_t(leaky_relu(s_src[col[t],h] + s_dst[i,h])) * m[t,h], m the attention-dropout mask at p_att (element t*H + h of the
+    counter hash, seed_att + seed_att_dev).  epilogue: None, "elu" (then dropout at p_drop, seed + seed_dev, element
+    i*(H*C) + column) or "log_softmax" (H == 1).  bias: float32 [>= H*C], 16-byte aligned, or None.
+    -> (out [n_rows, pad4(H*C)], state [n_rows, H, 2] = (max, denominator), pre | None, alpha | None): pre (want_pre) is the conv
+    output before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order."""
+    H, C = _gat_check(tbl, H, C, "gat_aggregate")
+    n_rows, E = int(n_rows), int(col.shape[0])
+    dev = tbl.device
+    if epilogue == "log_softmax" and H != 1:
+        raise RuntimeError("gat_aggregate: unsupported shape: the log_softmax epilogue needs heads == 1")
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
+        raise ValueError("bias must be float32 [>= H*C]")
+    _gat_need(s_src, "s_src", (int(tbl.shape[0]), H))
+    _gat_need(s_dst, "s_dst", (n_rows, H))
+    _gat_need(rowptr, "rowptr", (n_rows + 1,), torch.int32)
+    _gat_need(col, "col", (E,), torch.int32)
+    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
+    _gat_need_seed_word(seed_dev, "seed_dev")
+    if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
+        raise ValueError("p_att and p_drop must lie in [0, 1)")
+    W = pad4(H * C)
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    state = torch.empty(n_rows, H, 2, dtype=torch.float32, device=dev)
+    alpha = torch.empty(E, H, dtype=torch.float32, device=dev)       # always formed: the gather pass streams it
+    pre = None
+    if want_pre:
+        pre = out if GAT_EPILOGUES[epilogue] == 0 else torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    pre_arg = pre if (pre is not None and pre is not out) else None
+    sa, sad = _seed_args(seed_att, seed_att_dev)
+    sf, sfd = _seed_args(seed, seed_dev)
+    rc = L.lib().bgnn_gat_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows,
+        H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(state), L.ptr(alpha),
+        None, 0, L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gat_aggregate_f32")
+    return out, state, pre, (alpha if return_alpha else None)
+
+
+def gat_aggregate_bwd(tbl, s_src, s_dst, state, alpha, pre, grad_y, rowptr, col, t_rowptr, t_eid, t_dst, H, C, bias=None,
+                      negative_slope=0.2, p_att=0.0, seed_att=0, seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None,
+                      want_bias=True):
+    """Backward of `gat_aggregate` (bgnn.h: bgnn_gat_aggregate_bwd_f32) from what the forward returned (state, alpha with
+    return_alpha, pre with want_pre) and grad_y [N, >= pad4(H*C)] -> (grad_tbl [N, pad4(H*C)] = the gather part of dL/dtbl,
+    ds_src [N, H], ds_dst [N, H], grad_bias [H*C] | None).  The caller adds ds_src (x) att_src + ds_dst (x) att_dst to grad_tbl and
+    forms the att gradients.  (t_rowptr, t_eid, t_dst) = `DstCSR.transposed()`.  Three launches, no atomics: bit-identical runs."""
+    H, C = _gat_check(tbl, H, C, "gat_aggregate_bwd")
+    N, E = int(tbl.shape[0]), int(col.shape[0])
+    dev = tbl.device
+    W = pad4(H * C)
+    for t, what in ((s_src, "s_src"), (s_dst, "s_dst")):
+        _gat_need(t, what, (N, H))
+    _gat_need(state, "state", (N, H, 2))
+    _gat_need(alpha, "alpha", (E, H))
+    _gat_need_rows(pre, "pre", N, W)
+    _gat_need_rows(grad_y, "grad_y", N, W)
+    for t, what, n in ((rowptr, "rowptr", N + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
+        _gat_need(t, what, (n,), torch.int32)
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
+        raise ValueError("bias must be float32 [>= H*C]")
+    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
+    _gat_need_seed_word(seed_dev, "seed_dev")
+    lib = L.lib()
+    g = torch.empty(N, W, dtype=torch.float32, device=dev)
+    grad_tbl = torch.empty(N, W, dtype=torch.float32, device=dev)
+    ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+    ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+    wsb = int(lib.bgnn_gat_aggregate_workspace_bytes(E, N, H))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    sa, sad = _seed_args(seed_att, seed_att_dev)
+    sf, sfd = _seed_args(seed, seed_dev)
+    rc = lib.bgnn_gat_aggregate_bwd_f32(
+        L.ptr_rows(tbl), tbl.stride(0), N, L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(state), L.ptr(alpha), L.ptr_rows(pre),
+        pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E,
+        N, H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws), ws.numel(),
+        L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(ds_src), L.ptr(ds_dst), L.stream())
+    L.check(rc, "bgnn_gat_aggregate_bwd_f32")
+    return grad_tbl, ds_src, ds_dst, (column_sums(g)[:H * C] if want_bias else None)
 
 
 def rows_segment_add(src, seg_ptr, idx, row, dst, D=None, accumulate=True):

@@ -612,6 +612,22 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
         raise NotImplementedError('Not Implemented Model:{}'.format(gnn))
     from .gcn import GCNNet
     from .sage import GraphSAGE
+
+    def make_model():
+        if gnn == 'GCN':
+            return GCNNet(dataset, num_layer, hidden=hidden, dropout=dropout)
+        return GraphSAGE(dataset, num_layer, hidden, root_weight=True, dropout=dropout)
+
+    return _train_plain_backbone(args, dataset, data, make_model, gnn, lambda model: len(model.convs) - 1 if dropout > 0 else 0,
+                                 save, repeat, num_epoch, seed, lr, wd, use_scheduler, step_size, gamma, metric, f1_average, verbose,
+                                 ckpt_dir, history, graphed)
+
+
+def _train_plain_backbone(args, dataset, data, make_model, tag, dropout_words, save, repeat, num_epoch, seed, lr, wd, use_scheduler,
+                          step_size, gamma, metric, f1_average, verbose, ckpt_dir, history, graphed):
+    """The run of `train_gnn_noDTC` (:302-396) for any backbone whose forward returns log-probabilities: `make_model()` builds it (on
+    the host, after the seed is set), `tag` names it in the checkpoint file, `dropout_words(model)` is the number of dropout seeds
+    one training forward takes (the words a captured epoch prepares)."""
     dev = _device_of(args)
     with torch.cuda.device(dev):
         data = data.to(dev)
@@ -630,10 +646,7 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
             data_split_seed = 0
             model_init_seed = train_id - 1 if seed is None else seed
             set_random_seed(model_init_seed)
-            if gnn == 'GCN':
-                model = GCNNet(dataset, num_layer, hidden=hidden, dropout=dropout).to(dev)
-            else:
-                model = GraphSAGE(dataset, num_layer, hidden, root_weight=True, dropout=dropout).to(dev)
+            model = make_model().to(dev)
             _prime(model, data, lambda lp: ops.step2_nll(lp, plan.y, plan.train_u8))
             _say(verbose, data)
             _say(verbose, model)
@@ -670,11 +683,11 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
                         best_acc['loss'] = loss_train
                         best_epoch[0] = epoch - 1
                         if save:
-                            torch.save(model.state_dict(), os.path.join(ckpt_dir, f'model_{gnn}_{args.dataset_name}_share_best.ckpt'))
+                            torch.save(model.state_dict(), os.path.join(ckpt_dir, f'model_{tag}_{args.dataset_name}_share_best.ckpt'))
 
             ge = None
             if graphed:
-                ge = _GraphedEpoch(data, model, optimizer, hist, num_epoch, len(model.convs) - 1 if dropout > 0 else 0,
+                ge = _GraphedEpoch(data, model, optimizer, hist, num_epoch, dropout_words(model),
                                    lambda lp: ops.step2_nll(lp, plan.y, plan.train_u8, return_terms=True),
                                    lambda counts, auc: _eval_plain(data, model, plan, counts_out=counts, auc_out=auc))
             for epoch in range(1, 1 + num_epoch):
@@ -683,7 +696,7 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
                 if ge is not None:
                     ge.replay()
                 else:
-                    terms_slot.copy_(_train_step_noDTC(data, model, optimizer, plan, gnn)[1])
+                    terms_slot.copy_(_train_step_noDTC(data, model, optimizer, plan, None)[1])    # gnn=None: the forward returns log-probabilities alone
                     _eval_plain(data, model, plan, counts_out=counts_slot, auc_out=auc_slot)
                 if scheduler is not None:
                     scheduler.step()

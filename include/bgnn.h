@@ -34,7 +34,8 @@ extern "C" {
  * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
  * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size, and for the GCN baseline's
  * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for partitioned GCN's
- * bgnn_gcn_aggregate_rows_f32.
+ * bgnn_gcn_aggregate_rows_f32, and for the GAT baseline's bgnn_gat_scores_f32, bgnn_gat_aggregate_f32, bgnn_gat_aggregate_bwd_f32 and
+ * their workspace size (added after 114 without changing it).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
  * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone. */
@@ -526,6 +527,57 @@ int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, co
                                 int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
                                 const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
                                 void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
+ *     models/backbones.py:404-438 -- two PyG GATConv (heads, concat, negative_slope 0.2, attention dropout 0.6, add_self_loops,
+ *     bias) with F.elu + F.dropout(p=0.6) between them (:427-428) and F.log_softmax (:430).
+ * The caller transforms first (tbl = x W^T, [n, H*C], head h of row n at tbl[n*ldt + h*C]; ldt a multiple of 4, >= pad4(H*C))
+ * and hands the by-destination CSR with exactly one self loop per row (bgnn_build_dst_csr with rewrite_self_loops: PyG's
+ * remove_self_loops + add_self_loops; duplicate edges stay separate edges).  1 <= H <= 8, 1 <= C <= 128 (else BGNN_E_SHAPE).
+ * bgnn_gat_scores_f32: s_src[n,h] = <tbl[n,h,:], att_src[h,:]>, s_dst[n,h] = <tbl[n,h,:], att_dst[h,:]> ([n, H] each; att_* are
+ * [H*C] floats) in one read of tbl -- GATConv's (x_src * att_src).sum(-1) / (x_dst * att_dst).sum(-1).
+ * bgnn_gat_aggregate_f32, for row i, head h over the edges t of the row, j = col[t]:
+ *   z = s_src[j,h] + s_dst[i,h];  e = z > 0 ? z : negative_slope * z;  alpha = softmax_t(e) (row maximum subtracted);
+ *   a~ = alpha * m[t,h], m = 0 or 1/(1 - p_att) from the counter hash of bgnn_bn_relu_dropout_f32 at element t*H + h with
+ *   seed_att (+ *seed_att_dev_opt) -- t is the edge's position in this CSR, so duplicate edges draw independently;
+ *   out[i,h,:] = epi( sum_t a~ * tbl[j,h,:] + bias[h,:] ).
+ * Epilogues: 0 none; 1 ELU then dropout at p_drop over element index i*(H*C) + h*C + c with seed (+ *seed_dev_opt); 2 row
+ * log_softmax (H == 1 only).  Outputs: state [n_rows, H, 2] = the softmax's (maximum, denominator) per (row, head); the
+ * coefficients a~ as [n_edges, H] in CSR order, into alpha_out_opt when given, else into ws
+ * (bgnn_gat_aggregate_workspace_bytes(n_edges, n_rows, H)); pre_out_opt [n_rows, ldp]: the conv output before the epilogue
+ * (what the backward needs; NULL: not written); out [n_rows, ldo]; pad columns H*C .. pad4(H*C) of out and pre_out leave as 0.
+ * Two passes over the scores (state, then coefficients), one gather pass over tbl; rows of any degree, one lane group each.
+ * bgnn_gat_aggregate_bwd_f32: the atomic-free backward from the forward's (s_src, s_dst, state, alpha, pre) and grad_y.
+ * A row pass writes g [n_rows, ldg] (the gradient at the conv output: ELU' from pre and the feature mask REDRAWN from
+ * (seed, element index); grad_y - softmax(pre) * rowsum(grad_y) for epilogue 2) and r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]>;
+ * a pass over the by-destination CSR forms per edge da = m * <g[i,h,:], tbl[j,h,:]>, de = alpha * (da - r[i,h]),
+ * dz = de * (z > 0 ? 1 : negative_slope) into ws, and ds_dst[i,h] = sum_t dz in the per-side form
+ * (1 - negative_slope) (S+ Z- - S- Z+) / (Z+ + Z-), S and Z the row's sums of alpha * da and of alpha over its z > 0 / z <= 0 edges
+ * (the row's de sum to zero; summing the stored dz, whose r comes from pre, would leave a rounding of r in every row); a pass over the by-source view (t_rowptr [n_src+1],
+ * t_eid = the edge's position in the by-destination order, t_dst = its destination: `DstCSR.transposed()`) forms
+ * grad_tbl[j,h,:] = sum a~ * g[i,h,:] and ds_src[j,h] = sum dz.  The caller finishes: grad_bias = column sums of g,
+ * grad_tbl += ds_src (x) att_src + ds_dst (x) att_dst, grad_att_src[h,:] = sum_n ds_src[n,h] * tbl[n,h,:] (att_dst likewise).
+ * n_src == n_rows here (self loops make every node both); deterministic bits.  A row's edge range is cut to [0, n_edges] and ids are
+ * checked against their tables: a malformed CSR gives a wrong sum, never a stray access.  The entry points are defined in
+ * csrc/bgnn_gat.hip next to their kernels. */
+int bgnn_gat_scores_f32(const float* tbl, int64_t ldt, int64_t n, int32_t H, int32_t C, const float* att_src,
+                        const float* att_dst, float* s_src, float* s_dst, void* stream);
+size_t bgnn_gat_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H);
+int bgnn_gat_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s_src, const float* s_dst,
+                           const float* bias_opt, const int32_t* rowptr, const int32_t* col, int64_t n_edges,
+                           int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                           const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                           const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes,
+                           float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
+int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
+                               const float* bias_opt, const float* state, const float* alpha, const float* pre, int64_t ldp,
+                               const float* grad_y, int64_t ldgy, const int32_t* rowptr, const int32_t* col,
+                               const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges,
+                               int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                               const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                               const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
+                               float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
