@@ -30,6 +30,8 @@ SIGNATURES = {
                                                     _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "bgnn_adaptedconv_transform_need_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P,
                                                     _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "bgnn_adaptedconv_transform_need2_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P,
+                                                     _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]),
     "bgnn_classifier_stage_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
                                           _P, _P, _I32, _INT, _P, _P, _P, _P, _P, _P]),
     "bgnn_linear_narrow_transform_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _INT, _P, _P, _P, _P, _P, _P]),

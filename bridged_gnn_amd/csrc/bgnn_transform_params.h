@@ -36,6 +36,13 @@ struct GemmParams {
   // domain destinations: in a bridged graph with s -> t bridge edges no target node ever feeds a source destination, so half of
   // the h_t2s table is dead (C4: 256 MB of writes and a quarter of the matrix work per forward).  nullptr: every tile needs both.
   const int32_t* tile_need;
+  // stream kernel, MODE 0, NC = 256, optional: up to two runs of 32-row tiles [team_begin[r], team_end[r]) in which EVERY tile needs
+  // the single table team_table[r] (by tile_need or by the tail groups above).  Inside a run the four waves of the other table re-arm
+  // with their partner's columns of the needed table and the two teams take the block's tiles of the run in turn, instead of
+  // one team consuming every tile while the other only stages.  The host passes a run only if it gives every block >= 4 tiles
+  // (a re-arm costs about a tile's time) and tile numbers fit 32 bits; begin >= end: no run.  Zero-initialised: team mode off.
+  int64_t team_begin[2], team_end[2];
+  int32_t team_table[2];
   // stream kernel, fused classifier stage: a second packed operand on the SAME input rows (the narrow tables of two convs that read
   // x directly -- clf_base / clf_target on h) evaluated by one more consumer wave of the launch; nullptr: absent
   const float* sk_Wp; const float* sk_bias; const float* sk_wd; const float* sk_g; const float* sk_gc;

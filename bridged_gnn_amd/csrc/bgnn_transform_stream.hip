@@ -26,6 +26,21 @@
 // A first version with dedicated producer waves (4 stagers + 8 consumers) ran 0.36 ms: one wave executes a tile's ~1200 staging
 // instructions at ~13 cycles each, which bounded the launch.
 //
+// Team mode (MODE 0, 8 consumer waves; GemmParams::team_*).  Waves 0..3 own the 128 columns of h_s2t, waves 4..7 those of h_t2s.  A tile
+// that needs one table only (tile_need, tail_*) is sat out by the other table's four waves: they stage their rows and wait, and since
+// the ring couples all waves to the slowest, half of the CU idles through such a tile.  Where such tiles come in a long run (C4 with
+// [sources ; targets] order and s -> t bridges: every target tile needs h_s2t only) the host passes the run, and a block that enters
+// it RE-ARMS the idle team: wave w overwrites its stationary operand (the same 64 VGPRs) and epilogue constants with those of
+// wave w ^ 4 -- the same W loads, scale and split as at the kernel's start, so its fragments are the partner's bit for bit -- and
+// switches its output table.  Inside the run the teams take the block's tiles in turn: team (j & 1) consumes the run's j-th tile
+// (fused iteration as usual), the other team takes the sit-out path.  A wave then runs one fused iteration and one staging-only
+// iteration per two tiles instead of a fused one per tile.  Leaving the run the team re-arms back.  The ring protocol is
+// untouched (`ready`: NW shares, `done`: an arrival from every consumer wave), and every iteration still issues the same loads
+// and stores; the re-arm's own 16 W loads sit on a branch taken once or twice per launch in front of the tile's request and are
+// waited for in full there, so the vmcnt counts of the common path behind the join are what they were (35 / 36 / 37 in the
+// 8-wave kernel's assembly, before and after).  The re-arm stands at the head of the DEPTH-unrolled loop: a run is taken from a
+// multiple of DEPTH of the block's tile sequence to one; the host admits a run only if every block gets >= 4 of its tiles.
+//
 // fp16 x 2 split products.  A fp32 value v scaled into [2^10, 2^11) relative to its row (column) maximum is written as
 // hi = fp16(v), lo = fp16(v - hi): |v - hi - lo| <= 2^-22 |v| (two round-to-nearest 11-bit significands).  A product is the three
 // MFMAs hi*hi + hi*lo + lo*hi (fp32 accumulate); the dropped lo*lo term is <= 2^-22 relative.  Measured against the fp64 oracle
@@ -303,8 +318,6 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
 
   // ---------------------------------------------------------------- consumer state: columns col_base .. col_base + 31
   const int fr = lane & 31, fh = lane >> 5;
-  const int col_base = p.col_off + wave * 32;
-  const int n = col_base + fr;
   // stationary B operand: W[n][16kb + 8fh .. +7] scaled by this column's power of two, split into fp16 pieces
   h8 whi[KB16], wlo[KB16];
   float cinv = 0.f;
@@ -317,16 +330,22 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   const int roff0 = SL::chunk_off(fr, fh);
   static_assert(DK == 128, "fragment offsets: roff0 ^ (kb << 5) holds for 256-byte rows");
   auto roff = [&](int kb) { return roff0 ^ (kb << 5); };
-  if (consumer) {
+  // arm the wave with the packed column n per lane: stationary operand and the column's epilogue constants.  At the start n is the
+  // wave's own column; team mode re-arms a wave with its partner's (wave ^ 4: the same column of the other table) -- the same loads,
+  // the same scale, the same split, so the fragments are the partner's bit for bit.
+  auto arm = [&](int n) {
     float4 w[KB16][2];
     float mx = 0.f;
+    int din = p.Din;
+    asm volatile("" : "+s"(din));             // opaque: the re-arm's 16 load predicates are formed where they are used (hoisted out of the
+                                              // tile loop as loop invariants they are 32 SGPRs, which spill)
 #pragma unroll
     for (int kb = 0; kb < KB16; ++kb)
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         const int k = 16 * kb + 8 * fh + 4 * hf;
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n < p.NC && k < p.Din) t = *reinterpret_cast<const float4*>(p.Wp + (int64_t)n * p.Din + k);
+        if (n < p.NC && k < din) t = *reinterpret_cast<const float4*>(p.Wp + (int64_t)n * din + k);
         w[kb][hf] = t;
         mx = fmaxf(fmaxf(mx, fmaxf(fabsf(t.x), fabsf(t.y))), fmaxf(fabsf(t.z), fabsf(t.w)));
       }
@@ -342,33 +361,51 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
 #pragma unroll
         for (int e = 0; e < 4; ++e) { whi[kb][4 * hf + e] = hi[e]; wlo[kb][4 * hf + e] = lo[e]; }
       }
-    // epilogue constants of this lane's column; accumulator register v of a lane is row 8*(v/4) + 4*fh + v%4 of the tile.
+    bias_n = p.bias[n];                       // epilogue constants of this lane's column
+    if constexpr (MODE == 0) wd_n = p.wd[n];
+  };
+  const int col_base = p.col_off + wave * 32;
+  // Team mode (GemmParams::team_*): two 4-wave teams, wave w and wave w ^ 4 own the same column of the two tables.  (The re-arm sits at
+  // the head of the DEPTH-unrolled tile loop, so a run is taken from a multiple of DEPTH of the block's tile sequence to one.)
+  constexpr bool TEAMS = MODE == 0 && NW == 8 && NCW == 8 && AHEAD % DEPTH == 0;
+  const float* otab_own = nullptr;
+  const float* otab_alt = nullptr;            // team mode: the same head's other table
+  int own_table = 0;
+  if (consumer) {
+    arm(col_base + fr);
+    // accumulator register v of a lane is row 8*(v/4) + 4*fh + v%4 of the tile.
     // (host: NC % 32 == 0 and ldh % 32 == 0, so a wave's 32 columns lie in ONE table of one head)
     const int ld2 = 2 * (int)p.ldh;
     const int h = col_base / ld2, rem = col_base % ld2, t = rem >= p.ldh ? 1 : 0;
-    bias_n = p.bias[n];
-    if constexpr (MODE == 0) wd_n = p.wd[n];
-    otab = h == 0 ? (t == 0 ? p.out[0][0] : p.out[0][1]) : (t == 0 ? p.out[1][0] : p.out[1][1]);
+    otab_own = h == 0 ? (t == 0 ? p.out[0][0] : p.out[0][1]) : (t == 0 ? p.out[1][0] : p.out[1][1]);
+    if constexpr (TEAMS) otab_alt = t == 0 ? p.out[0][1] : p.out[0][0];
     ooff = (int)((4 * fh * p.row_stride + (rem - t * (int)p.ldh) + fr) * 4);
-    if constexpr (MODE == 0) my_table = __builtin_amdgcn_readfirstlane(t);
+    if constexpr (MODE == 0) own_table = __builtin_amdgcn_readfirstlane(t);
+    otab = otab_own;
+    my_table = own_table;
+  }
+  // local tile indices [tm_lo[r], tm_hi[r]) of this block lie inside run r (tile numbers fit 32 bits: host)
+  int tm_lo[2] = {0, 0}, tm_hi[2] = {0, 0};
+  if constexpr (TEAMS) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const uint32_t b = blockIdx.x, G = gridDim.x, rb = (uint32_t)p.team_begin[r], re = (uint32_t)p.team_end[r];
+      if (re > rb) {
+        const uint32_t lo = rb <= b ? 0u : (rb - b + G - 1) / G, hi = re <= b ? 0u : (re - b + G - 1) / G;
+        tm_lo[r] = (int)((lo + DEPTH - 1) / DEPTH * DEPTH);
+        tm_hi[r] = (int)(hi / DEPTH * DEPTH);
+      }
+    }
   }
   const int rs4 = (int)(p.row_stride * 4);    // bytes per output row
   // LDS part of a tile's consumption (no vector memory): -> res[16] for the stores; false: the wave sits the tile out
-  auto consume = [&](int64_t i, int slot, uint32_t round, float (&res)[16]) -> bool {
+  auto consume = [&](int64_t i, int slot, uint32_t round, bool wanted, float (&res)[16]) -> bool {
     if (!consumer || i >= nlocal) return false;
-    const int64_t tile = blockIdx.x + i * (int64_t)gridDim.x;
     const unsigned char* const sb = ring + slot * SL::BYTES;
     TS_MARK(0);
     lds_wait_ge(&ready[slot], (uint32_t)NW * (round + 1));
     TS_MARK(4);
-    bool skip = false;
-    if constexpr (MODE == 0) {
-      // single-table tail rows (GemmParams): a tile inside one tail group is sat out by the other table's waves
-      const int64_t tb = tile * 32, te = tb + 32;
-      skip = p.tail_s2t_begin > 0 && ((my_table == 0 && tb >= p.tail_t2s_begin && te <= p.tail_s2t_begin) || (my_table == 1 && tb >= p.tail_s2t_begin));
-      if (p.tile_need != nullptr) skip = skip || ((p.tile_need[tile] >> my_table) & 1) == 0;     // (scalar load: uniform address)
-    }
-    if (skip) {                               // wave-uniform
+    if (!wanted) {                            // wave-uniform: the tile is not this wave's (see `wanted` in the tile loop)
       lds_arrive(&done[slot]);
       return false;
     }
@@ -505,15 +542,15 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   };
   // the tile's 16 stores (2 rows x 128 contiguous bytes each); `live` false / rows past N: dropped by the descriptor's range check
   int64_t st_left = 0;                        // N - first row of the tile stored next (set where the loop starts)
-  const float* st_o = otab;
+  int64_t st_off = 0;                         // ... and its first row's element offset in the wave's table (otab: team mode switches it)
   auto store16 = [&](bool live, const float (&res)[16]) {
 #ifdef TS_X_NOSTORE
     const int rows_here = 0;                  // ablation: every store dropped by the range check
 #else
     const int rows_here = (!live || st_left < 0) ? 0 : (st_left > 32 ? 32 : (int)st_left);
 #endif
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(st_o), (short)0, rows_here * rs4, 0x00020000);
-    st_left -= tstep; st_o += tstep * p.row_stride;
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(otab != nullptr ? otab + st_off : nullptr), (short)0, rows_here * rs4, 0x00020000);
+    st_left -= tstep; st_off += tstep * p.row_stride;
 #ifdef TS_X_STORE4
     // experiment (wrong layout, same bytes): four 16-byte stores per lane instead of sixteen 4-byte ones
 #pragma unroll
@@ -552,8 +589,27 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   asm volatile("" : "+s"(i_first));            // opaque start: keeps the compiler from peeling the switched-off iterations off the
                                               // loop (peeled copies leave loads pending at the loop header, see above)
   st_left = p.N - ((int64_t)blockIdx.x + i_first * (int64_t)gridDim.x) * 32;
-  st_o = otab != nullptr ? otab + ((int64_t)blockIdx.x + i_first * (int64_t)gridDim.x) * 32 * p.row_stride : nullptr;
+  st_off = ((int64_t)blockIdx.x + i_first * (int64_t)gridDim.x) * 32 * p.row_stride;
   for (int64_t i0 = i_first; i0 < nlocal; i0 += DEPTH) {
+    // team mode: is this group of DEPTH tiles inside a run, and is the wave armed with the table the tiles are consumed for?  A re-arm
+    // happens when the block enters or leaves a run (once or twice per launch).  It sits in front of the request, so its wait for
+    // the W loads drains only what is in flight anyway, and it comes with that full wait of its own: behind the join the vmcnt
+    // counts of the common path hold as before.
+    int run_lo = -1;                          // first local tile of the run this group is in (-1: not in a run)
+    if constexpr (TEAMS) {
+      if (i0 >= 0) {
+        const int r = (i0 >= tm_lo[0] && i0 < tm_hi[0]) ? 0 : ((i0 >= tm_lo[1] && i0 < tm_hi[1]) ? 1 : -1);
+        if (r >= 0) run_lo = tm_lo[r];
+        const int want = r < 0 ? own_table : p.team_table[r];
+        if (consumer && want != my_table) {
+          const bool home = want == own_table;
+          arm((home ? col_base : col_base ^ 128) + fr);       // (NC = 256: the partner's columns are 128 = 4 waves x 32 away)
+          otab = home ? otab_own : otab_alt;
+          my_table = want;
+          TS_MARK(0);
+        }
+      }
+    }
 #pragma unroll
     for (int u = 0; u < DEPTH; ++u) {
       const int64_t i = i0 + u, s = i + AHEAD;        // (s + DEPTH) % DEPTH == u
@@ -580,10 +636,18 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
 #pragma unroll
       for (int r = 0; r < 16; ++r) res[r] = 0.f;
       bool live = false;
-      bool wanted = true;                     // does any row of tile i need this wave's table?  (GemmParams::tile_need)
+      // is tile i this wave's to consume?  Inside a team run both teams hold the run's table and take the block's tiles of the run
+      // in turn; elsewhere: does any row of the tile need the wave's table (GemmParams::tile_need, tail_*)?
+      bool wanted = true;
       if constexpr (MODE == 0) {
-        if (p.tile_need != nullptr && i >= 0 && i < nlocal)
-          wanted = ((p.tile_need[blockIdx.x + i * (int64_t)gridDim.x] >> my_table) & 1) != 0;
+        if (run_lo >= 0) {
+          wanted = (((int)i - run_lo) & 1) == (wave >> 2);
+        } else if (i >= 0 && i < nlocal) {
+          const int64_t tile = blockIdx.x + i * (int64_t)gridDim.x, tb = tile * 32, te = tb + 32;
+          // single-table tail rows: a tile inside one tail group is sat out by the other table's waves
+          wanted = !(p.tail_s2t_begin > 0 && ((my_table == 0 && tb >= p.tail_t2s_begin && te <= p.tail_s2t_begin) || (my_table == 1 && tb >= p.tail_s2t_begin)));
+          if (p.tile_need != nullptr) wanted = wanted && ((p.tile_need[tile] >> my_table) & 1) != 0;     // (scalar load: uniform address)
+        }
       }
       if (steady_wave && wanted && i >= 0 && s < nlocal) {      // block-uniform per wave; no vector memory in either branch
         fused(i, rv, mk, ss, sr, cs, cr, pf_done, pf_ready, res);
@@ -596,7 +660,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
           bump(ss, sr);
         }
         if (i >= 0) {
-          live = consume(i, cs, cr, res);
+          live = consume(i, cs, cr, wanted, res);
           bump(cs, cr);
         }
       }
@@ -1067,7 +1131,28 @@ static bool stream2_supported(const GemmParams& p) {
   return p.NC == 128 && p.Din <= 128 && p.Din > 64 && (p.Din & 3) == 0 && p.mask && p.w2 && p.g2 && p.raw && p.ldx * 4 * 32 <= 0x7fffffff;
 }
 
-int bgnn_tf_stream_launch(const GemmParams& p, int mode, hipStream_t st, int n_cu) {
+// Team mode's admission (GemmParams::team_*): a run the kernel should not take is emptied -- BGNN_TS_TEAMS=0 in the environment (read
+// once) empties all, for A/B measurements and the bit-for-bit tests; so do a shape without two 4-wave teams, a run outside the
+// tiles, a run that gives some block fewer than 4 tiles, a run that is not inside the tail group of its table when the launch
+// has tail groups, and overlapping runs.  With every run emptied the kernel is the launch it was without team mode.
+static void team_runs_admit(GemmParams& p, int64_t ntiles, int64_t nblocks) {
+  static const bool on = [] { const char* e = getenv("BGNN_TS_TEAMS"); return !(e && atoi(e) == 0); }();
+  for (int r = 0; r < 2; ++r) {
+    const int64_t b = p.team_begin[r], e = p.team_end[r];
+    const int t = p.team_table[r];
+    bool ok = on && p.NC == 256 && ntiles < 0x7fffffff && b >= 0 && b < e && e <= ntiles && (t == 0 || t == 1) && (e - b) / nblocks >= 4;
+    if (ok && p.tail_s2t_begin > 0) {          // tail groups: rows [tail_t2s_begin, tail_s2t_begin) table 1 only, [tail_s2t_begin, N) table 0 only
+      ok = t == 1 ? (b * 32 >= p.tail_t2s_begin && e * 32 <= p.tail_s2t_begin) : b * 32 >= p.tail_s2t_begin;
+    } else if (ok && p.tile_need == nullptr) {
+      ok = false;                              // neither a need mask nor tail groups: every tile needs both tables
+    }
+    if (ok && r == 1 && p.team_end[0] > p.team_begin[0]) ok = e <= p.team_begin[0] || b >= p.team_end[0];
+    if (!ok) { p.team_begin[r] = p.team_end[r] = 0; p.team_table[r] = 0; }
+  }
+}
+
+int bgnn_tf_stream_launch(const GemmParams& p_in, int mode, hipStream_t st, int n_cu) {
+  GemmParams p = p_in;
   if (mode == 2) {
     if (!stream2_supported(p)) return BGNN_E_SHAPE;
     const int64_t nt = (p.N + 31) / 32;
@@ -1101,6 +1186,7 @@ int bgnn_tf_stream_launch(const GemmParams& p, int mode, hipStream_t st, int n_c
   if (!bgnn_tf_stream_supported(p, mode)) return BGNN_E_SHAPE;
   const int64_t ntiles = (p.N + 31) / 32;
   const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu), 1u);
+  team_runs_admit(p, ntiles, (int64_t)grid.x);
 #ifdef TS_STAMP
   GemmParams q = p;
   static float* dbuf = nullptr;

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (one Python function per entry point of include/bgnn.h).
 Every function takes/returns CUDA(HIP) tensors on the current device and launches on torch's
 current stream.  No CPU path exists: host tensors raise."""
+import ctypes
 import os
 
 import torch
@@ -539,6 +540,62 @@ def pack_transform_heads(heads, din_pad):
     return Wp, bp, gates, D, ldh, gconst
 
 
+_N_CU = {}              # device -> compute units (the stream kernel launches one block per CU)
+TEAM_MIN_TILES = 4      # a team run must give every block of the launch this many tiles (a re-arm costs about one tile's time)
+
+
+def single_table_runs(tile_need):
+    """The longest run of consecutive tiles that need ONLY h_s2t (`tile_need` == 1) and the longest that need ONLY h_t2s (== 2):
+    -> [(first tile, one past the last, table), ...], at most two, by first tile.  Decided once per need mask (one host copy, like
+    DstCSR.tile_need itself) and kept on the tensor."""
+    key = (tile_need.data_ptr(), tile_need._version)
+    c = getattr(tile_need, "_single_table_runs", None)
+    if c is None or c[0] != key:
+        v = tile_need.detach().cpu()
+        runs = []
+        if v.numel():
+            cut = torch.nonzero(v[1:] != v[:-1]).reshape(-1) + 1
+            begin = torch.cat((cut.new_zeros(1), cut))
+            end = torch.cat((cut, cut.new_full((1,), v.numel())))
+            val = v[begin]
+            for table in (0, 1):
+                sel = torch.nonzero(val == (1 << table)).reshape(-1)
+                if sel.numel():
+                    k = sel[torch.argmax((end - begin)[sel])]
+                    runs.append((int(begin[k]), int(end[k]), table))
+        tile_need._single_table_runs = c = (key, sorted(runs))
+    return list(c[1])
+
+
+def transform_team_runs(N, device, tile_need=None, tail_single=(0, 0)):
+    """The plan of the hidden transform's team mode (bgnn.h: bgnn_adaptedconv_transform_need2_f32): the runs of single-table tiles
+    -- out of the need mask, or the two tail groups -- that give every block of the stream kernel's launch (one per CU) at least
+    TEAM_MIN_TILES tiles.  [] = team mode stays off for this graph."""
+    if tile_need is None and not (tail_single[0] or tail_single[1]):
+        return []
+    if tile_need is not None:                  # per need mask the plan is decided once (this runs in front of every launch)
+        c = getattr(tile_need, "_team_plan", None)
+        if c is not None and c[0] == (int(N), device, tile_need._version):
+            return c[1]
+    ntiles = (int(N) + 31) // 32
+    if ntiles == 0:
+        return []
+    n_cu = _N_CU.get(device)
+    if n_cu is None:
+        n_cu = _N_CU[device] = torch.cuda.get_device_properties(device).multi_processor_count
+    n_blocks = min(ntiles, n_cu)
+    if tile_need is not None:
+        cand = single_table_runs(tile_need)
+    else:
+        n_t2s, n_s2t = int(tail_single[0]), int(tail_single[1])
+        t2s_begin, s2t_begin = N - n_t2s - n_s2t, N - n_s2t             # rows: [t2s_begin, s2t_begin) h_t2s only, [s2t_begin, N) h_s2t only
+        cand = [((t2s_begin + 31) // 32, s2t_begin // 32, 1), ((s2t_begin + 31) // 32, ntiles, 0)] if (n_t2s or n_s2t) else []
+    plan = [(b, e, t) for b, e, t in cand if (e - b) // n_blocks >= TEAM_MIN_TILES]
+    if tile_need is not None:
+        tile_need._team_plan = ((int(N), device, tile_need._version), plan)
+    return plan
+
+
 def adaptedconv_transform(x, mask_u8, delta, packed, out=None, sums=None, tail_single=(0, 0), tile_need=None):
     """One pass over x -> per head (h_t2s, h_s2t) as [N, ldh] tensors (ldh = pad4(D); columns >= D are
     zero; `tile_need`: see DstCSR.tile_need).  `packed` = pack_transform_heads(...).  `out` = list of (h_t2s, h_s2t) preallocated tables
@@ -574,6 +631,13 @@ def adaptedconv_transform(x, mask_u8, delta, packed, out=None, sums=None, tail_s
         if tile_need.dtype != torch.int32 or tile_need.numel() != (N + 31) // 32:
             raise ValueError("tile_need: one int32 per 32-row tile")
         fn, name, tail = lib.bgnn_adaptedconv_transform_need_f32, "bgnn_adaptedconv_transform_need_f32", (L.ptr(tile_need),)
+    if delta is None and H == 1 and (tile_need is not None or tail_single[0] or tail_single[1]):
+        c = getattr(tile_need, "_team_plan", None)                    # (the plan of this need mask, decided at its first launch)
+        runs = c[1] if (c is not None and c[0] == (N, dev, tile_need._version)) else transform_team_runs(N, dev, tile_need, tail_single)
+        if runs:
+            flat = (ctypes.c_int64 * (3 * len(runs)))(*[v for r in runs for v in r])       # host memory, read during the call
+            fn, name = lib.bgnn_adaptedconv_transform_need2_f32, "bgnn_adaptedconv_transform_need2_f32"
+            tail = (int(tail_single[0]), int(tail_single[1]), L.ptr(tile_need) if tile_need is not None else None, flat, len(runs))
     rc = fn(L.ptr(x), N, Din, x.stride(0), L.ptr(mask_u8), L.ptr(first), H, D, L.ptr(Wp), L.ptr(bp), L.ptr(gates), L.ptr(gconst),
             L.ptr_rows(out[0][1]), L.ptr_rows(out[0][0]), L.ptr_rows(o1[1]), L.ptr_rows(o1[0]), ldh, row_stride, *tail,
             L.ptr(small), L.stream())

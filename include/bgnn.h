@@ -256,6 +256,22 @@ int bgnn_adaptedconv_transform_need_f32(const float* x, int64_t N, int32_t Din, 
                                         float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
                                         int64_t ldh, int64_t row_stride, const int32_t* tile_need_opt,
                                         float* small_ws, void* stream);
+/* The sums form with tail groups OR a need mask (not both), plus up to two "team runs" (additive entry: the revision does not
+ * move).  team_runs_host_opt: NULL, or n_team_runs <= 2 triples (first tile, one past the last tile, table) of int64 in HOST memory,
+ * read during the call: runs of 32-row tiles in which EVERY tile needs the one table `table` (0 = h_s2t, 1 = h_t2s) -- by
+ * tile_need_opt (value 1 << table) or by lying inside that table's tail group.  The caller vouches for that; it decides the runs once
+ * per graph.  Inside a run the stream kernel's two 4-wave teams both hold the needed table's columns and take a block's tiles in
+ * turn (csrc/bgnn_transform_stream.hip).  Outputs are bit for bit those of the entries above.  A run that gives some block of
+ * the launch fewer than 4 tiles, or a shape the stream kernel does not take at 256 packed columns, is ignored; so are all runs
+ * with BGNN_TS_TEAMS=0 in the environment (read once). */
+int bgnn_adaptedconv_transform_need2_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
+                                         const uint8_t* mask, const double* sums,
+                                         int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
+                                         const float* gates, const float* gate_const_opt,
+                                         float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
+                                         int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
+                                         const int32_t* tile_need_opt, const int64_t* team_runs_host_opt, int32_t n_team_runs,
+                                         float* small_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a11-a13) fused GATv2 logits + per-destination softmax + weighted neighbour sum.
