@@ -43,7 +43,8 @@ static inline hipError_t bgnn_zero_async(void* p, size_t bytes, hipStream_t st) 
 static inline bool bgnn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline size_t bgnn_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Counter-based dropout hash shared by every kernel that drops activations (bgnn_norm.hip, bgnn_sage.hip): element e of an
+// Counter-based dropout hash shared by every kernel that drops activations or attention coefficients (bgnn_norm.hip and, through
+// bgnn_conv_common.h, bgnn_sage.hip, bgnn_gcn.hip and bgnn_gat.hip): element e of an
 // [N, D] activation (e = row * D + column) belongs to word pair q = e / 4 and takes its 16 bits from w0 lo, w0 hi, w1 lo, w1 hi
 // for e % 4 = 0..3.
 // dropout: 16 random bits per element, keep <=> bits >= thr (thr = round(p * 65536)); two 32-bit words per float4

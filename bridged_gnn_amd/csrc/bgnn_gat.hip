@@ -16,7 +16,7 @@
 //             merged over the lanes, kept as state[i,h] = (max, denominator >= 1); a second sweep writes the post-dropout
 //             coefficient a~ = exp(e - max) / den * m to coef[t*H + h] (m from the counter hash at element t*H + h).
 //   aggregate out[i,h,:] = sum_t coef[t,h] * T[col[t],h,:] (+ bias, epilogue): LF lanes span the head's columns, EP sub-groups walk
-//             different edges, U rows in flight (bgnn_gcn.hip's mapping).  The coefficients stream, only T rows are gathered.
+//             different edges, U rows in flight (the mapping of bgnn_conv_common.h).  The coefficients stream, only T rows are gathered.
 // Backward, three launches (no float atomics):
 //   rows      g = the gradient at the conv output (ELU derivative from the kept pre-activation, the feature mask REDRAWN from
 //             (seed, row, col); log_softmax rule from the pre-activation), r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]>.
@@ -26,21 +26,14 @@
 //             dT[j,h,:] = sum_u coef[t_eid[u],h] * g[t_dst[u],h,:] and ds_src[j,h] = sum_u dz[t_eid[u],h].
 // Ids outside their table are never dereferenced and a row's edge range is cut to the edge arrays: a malformed CSR (ids or rowptr)
 // gives a wrong sum, not a stray read or write.
-#include "bgnn_common.h"
+#include "bgnn_conv_common.h"
 
 namespace {
 
+using namespace bgnn_conv;
+constexpr int EPI_ELU = EPI_ACT;   // code 1 here: ELU, then dropout
 constexpr int MAX_HEADS = 8;
-constexpr int MAX_C = 128;
-
-enum { EPI_NONE = 0, EPI_ELU = 1, EPI_LOGSOFTMAX = 2 };
-
-__device__ __forceinline__ uint32_t drop_bits(uint64_t e, uint64_t seed) {
-  uint32_t w0, w1;
-  drop_words(e >> 2, seed, w0, w1);
-  const uint32_t w = (e & 2) ? w1 : w0;
-  return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
+constexpr int MAX_C = SLICE;
 
 // leaky_relu with a ROUNDED product: never contracted into the subtraction of the row maximum that follows, so the three kernels
 // that form e (state sweep, coefficient sweep, backward edge pass) agree bit for bit
@@ -264,7 +257,6 @@ __global__ __launch_bounds__(256) void gat_agg_kernel(AggParams p) {
         for (int c = 0; c < 4; ++c) acc[c] += w[u] * x[u][c];
       }
     }
-    // sum of the EP sub-groups' partials (fixed butterfly: deterministic)
 #pragma unroll
     for (int off = LF; off < GL; off <<= 1) {
 #pragma unroll
@@ -289,6 +281,7 @@ __global__ __launch_bounds__(256) void gat_agg_kernel(AggParams p) {
       for (int c = 0; c < 4; ++c) o[c] = o[c] > 0.f ? o[c] : expm1f(o[c]);
       if (p.thr != 0u) {
         const uint64_t e = (uint64_t)i * (uint64_t)(p.H * p.C) + (uint64_t)(hoff + k0);
+        // drop4's law, in place: through the shared function this kernel's forward at (3, 64) measured 0.9 % slower
         if (vec) {                                                // the four columns share one word pair (as bgnn_norm.hip)
           uint32_t w0, w1;
           drop_words(e >> 2, seed, w0, w1);
@@ -301,18 +294,7 @@ __global__ __launch_bounds__(256) void gat_agg_kernel(AggParams p) {
         }
       }
     } else if (EPI == EPI_LOGSOFTMAX) {
-      // H == 1: the whole row (C <= 4*LF) sits in the LF lanes of the group; every lane takes part in the cross-lane steps
-      float m = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (k0 + c < p.C) m = fmaxf(m, o[c]);
-      m = bgnn::group_max<LF>(m);
-      float se = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (k0 + c < p.C) se += expf(o[c] - m);
-      se = bgnn::group_sum<LF>(se);
-      const float lse = m + logf(se);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] -= lse;
+      log_softmax4<LF>(o, k0, p.C);   // H == 1: the whole row (C <= 4*LF) sits in the LF lanes of the group
     }
     if (writer) {
       store4(p.out + i * p.ldo + hoff, k0, p.C, vec, o);
@@ -505,25 +487,6 @@ __global__ __launch_bounds__(256) void gat_bwd_edge_kernel(EdgeParams p) {
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------
-template <typename K>
-int persistent_grid(K kernel, int64_t ntiles, int* cap_cache) {
-  if (*cap_cache == 0) {
-    int per_cu = 0, dev = 0, cap = 2048;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) == hipSuccess && per_cu >= 1) {
-      if (per_cu > 8) per_cu = 8;
-      cap = per_cu * prop.multiProcessorCount / 8 * 8;
-      if (cap < 8) cap = 8;
-    }
-    __atomic_store_n(cap_cache, cap, __ATOMIC_RELEASE);
-  }
-  const int cap = __atomic_load_n(cap_cache, __ATOMIC_ACQUIRE);
-  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;     // multiple of 8 (XCD split)
-  if (grid < 8) grid = 8;
-  return (int)grid;
-}
-
 template <int LF, int EP, int U, int EPI, bool BWD>
 int launch_agg(const AggParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
@@ -537,13 +500,8 @@ int launch_agg(const AggParams& p, hipStream_t st) {
 
 template <int EPI, bool BWD>
 int dispatch_agg(const AggParams& p, hipStream_t st) {
-  const int nv = (p.C + 3) / 4;   // float4 slots of a head
-  if (nv <= 1) return launch_agg<1, 8, 4, EPI, BWD>(p, st);
-  if (nv <= 2) return launch_agg<2, 4, 4, EPI, BWD>(p, st);
-  if (nv <= 4) return launch_agg<4, 2, 4, EPI, BWD>(p, st);
-  if (nv <= 8) return launch_agg<8, 1, 8, EPI, BWD>(p, st);
-  if (nv <= 16) return launch_agg<16, 1, 8, EPI, BWD>(p, st);
-  return launch_agg<32, 1, 8, EPI, BWD>(p, st);
+  return lf_ladder((p.C + 3) / 4,   // float4 slots of a head
+                   [&](auto LF, auto EP, auto U) { return launch_agg<LF, EP, U, EPI, BWD>(p, st); });
 }
 
 template <int LF, int EP, int U>
@@ -558,13 +516,8 @@ int launch_edge(const EdgeParams& p, hipStream_t st) {
 }
 
 int dispatch_edge(const EdgeParams& p, hipStream_t st) {
-  const int nv = (p.C + 3) / 4;
-  if (nv <= 1) return launch_edge<1, 8, 4>(p, st);
-  if (nv <= 2) return launch_edge<2, 4, 4>(p, st);
-  if (nv <= 4) return launch_edge<4, 2, 4>(p, st);
-  if (nv <= 8) return launch_edge<8, 1, 4>(p, st);
-  if (nv <= 16) return launch_edge<16, 1, 4>(p, st);
-  return launch_edge<32, 1, 4>(p, st);
+  // four rows in flight on every rung: the ladder's U is not taken
+  return lf_ladder((p.C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_edge<LF, EP, 4>(p, st); });
 }
 
 template <int LF, int EPI>
@@ -578,19 +531,14 @@ int launch_rows(const RowParams& p, hipStream_t st) {
   return 0;
 }
 
-template <int EPI>
-int dispatch_rows(const RowParams& p, hipStream_t st) {
-  const int nv = (p.C + 3) / 4;
-  if (nv <= 1) return launch_rows<1, EPI>(p, st);
-  if (nv <= 2) return launch_rows<2, EPI>(p, st);
-  if (nv <= 4) return launch_rows<4, EPI>(p, st);
-  if (nv <= 8) return launch_rows<8, EPI>(p, st);
-  if (nv <= 16) return launch_rows<16, EPI>(p, st);
-  return launch_rows<32, EPI>(p, st);
+int dispatch_rows(int epilogue, const RowParams& p, hipStream_t st) {
+  return epi_switch(epilogue, [&](auto EPI) {
+    return lf_ladder((p.C + 3) / 4, [&](auto LF, auto, auto) { return launch_rows<LF, EPI>(p, st); });
+  });
 }
 
 // a [rows, H*C] table whose head slices the kernels touch: leading dimension >= pad4(H*C), a multiple of 4, 16-byte aligned base
-bool tbl_ok(const float* t, int64_t ld, int32_t HC) { return bgnn_aligned16(t) && (ld & 3) == 0 && ld >= ((int64_t)HC + 3) / 4 * 4; }
+bool tbl_ok(const float* t, int64_t ld, int32_t HC) { return bgnn_aligned16(t) && ld_ok(ld, HC); }
 
 bool shape_ok(int32_t H, int32_t C) { return H >= 1 && H <= MAX_HEADS && C >= 1 && C <= MAX_C; }
 
@@ -631,10 +579,9 @@ extern "C" int bgnn_gat_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_t
                                       float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream) {
   if (!tbl || !s_src || !s_dst || !rowptr || !col || !state || !out) return BGNN_E_NULL;
   if (!alpha_out_opt && !ws_opt) return BGNN_E_NULL;
-  if (n_rows < 0 || n_tbl < 0 || n_edges < 0 || !shape_ok(H, C) || epilogue < 0 || epilogue > 2) return BGNN_E_SHAPE;
-  if (!(p_att >= 0.f && p_att < 1.f) || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
+  if (n_rows < 0 || n_tbl < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
   if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
-  if (p_drop > 0.f && epilogue != EPI_ELU) return BGNN_E_SHAPE;
   const int32_t HC = H * C;
   if (!tbl_ok(tbl, ldt, HC) || !tbl_ok(out, ldo, HC) || (pre_out_opt && !tbl_ok(pre_out_opt, ldp, HC))) return BGNN_E_ALIGN;
   if (bias_opt && !bgnn_aligned16(bias_opt)) return BGNN_E_ALIGN;
@@ -664,8 +611,7 @@ extern "C" int bgnn_gat_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_t
   p.out = out; p.ldo = ldo; p.pre = pre_out_opt; p.ldp = ldp;
   drop_consts(p_drop, p.thr, p.keep_scale);
   p.seed = seed; p.seed_dev = seed_dev_opt;
-  return epilogue == EPI_ELU ? dispatch_agg<EPI_ELU, false>(p, st)
-       : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX, false>(p, st) : dispatch_agg<EPI_NONE, false>(p, st);
+  return epi_switch(epilogue, [&](auto EPI) { return dispatch_agg<EPI, false>(p, st); });
 }
 
 extern "C" int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
@@ -679,10 +625,9 @@ extern "C" int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t
   if (!tbl || !s_src || !s_dst || !state || !alpha || !pre || !grad_y || !rowptr || !col || !t_rowptr || !t_eid || !t_dst || !ws ||
       !g || !grad_tbl || !ds_src || !ds_dst)
     return BGNN_E_NULL;
-  if (n_rows < 0 || n_src < 0 || n_edges < 0 || !shape_ok(H, C) || epilogue < 0 || epilogue > 2) return BGNN_E_SHAPE;
-  if (!(p_att >= 0.f && p_att < 1.f) || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
+  if (n_rows < 0 || n_src < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
   if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
-  if (p_drop > 0.f && epilogue != EPI_ELU) return BGNN_E_SHAPE;
   const int32_t HC = H * C;
   if (!tbl_ok(tbl, ldt, HC) || !tbl_ok(pre, ldp, HC) || !tbl_ok(grad_y, ldgy, HC) || !tbl_ok(g, ldg, HC) || !tbl_ok(grad_tbl, ldgt, HC))
     return BGNN_E_ALIGN;
@@ -698,8 +643,7 @@ extern "C" int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t
     drop_consts(p_drop, p.thr, p.keep_scale);
     p.seed = seed; p.seed_dev = seed_dev_opt;
     p.g = g; p.ldg = ldg; p.r = r;
-    int rc = epilogue == EPI_ELU ? dispatch_rows<EPI_ELU>(p, st)
-           : epilogue == EPI_LOGSOFTMAX ? dispatch_rows<EPI_LOGSOFTMAX>(p, st) : dispatch_rows<EPI_NONE>(p, st);
+    int rc = dispatch_rows(epilogue, p, st);
     if (rc != 0) return rc;
     EdgeParams e{};
     e.tbl = tbl; e.ldt = ldt; e.n_tbl = n_src; e.g = g; e.ldg = ldg; e.s_src = s_src; e.s_dst = s_dst; e.state = state; e.r = r;

@@ -10,9 +10,8 @@
 //             forward walk (no epilogue, no bias) over the by-source view of the same edges.  No float atomics anywhere.
 // dinv[col[t]] is gathered in the edge loop (4 B per edge next to the 4*D B row).  Bytes at width D: E'(4D + 8) + N(8D + 4).
 //
-// Mapping (bgnn_sage.hip's): a group of GL = LF*EP consecutive lanes owns one output row; LF lanes span the columns (float4
-// per lane), EP sub-groups walk different edges of the row (narrow rows), each keeps U neighbour rows in flight; blocks are
-// persistent over the XCD-balanced segment order of bgnn_common.h; at most 128 columns per launch, wider rows run as slices.
+// Mapping, dropout hash, epilogue pieces, backward row kernel and launch helpers: bgnn_conv_common.h.  At most 128 columns per
+// launch, wider rows run as slices.
 //
 // Hub rows (a source node of a bridged graph after ToUndirected has thousands of in-edges): with hub tables the row kernel
 // skips every row of at least `hub_threshold` edges; the same kernel then runs twice more -- SEGMENT mode sums each segment
@@ -23,13 +22,12 @@
 // Rows of a larger graph (bgnn_gcn_aggregate_rows_f32, a rank's rows of a node partition): ROW_ID kernels draw the dropout mask
 // of output row io for row_id[io], its GLOBAL row, in the row kernel and in a hub's FINISH group alike; the id is loaded once per
 // row after the gather loop.  Without ids (or without dropout) the kernels launched are the ones without the template flag.
-#include "bgnn_common.h"
+#include "bgnn_conv_common.h"
 
 namespace {
 
-constexpr int SLICE = 128;   // columns per launch (LF <= 32)
-
-enum { EPI_NONE = 0, EPI_RELU = 1, EPI_LOGSOFTMAX = 2 };
+using namespace bgnn_conv;
+constexpr int EPI_RELU = EPI_ACT;   // code 1 here: ReLU, then dropout
 enum { MODE_ROWS = 0, MODE_SEGMENT = 1, MODE_FINISH = 2 };
 
 struct GcnParams {
@@ -46,15 +44,6 @@ struct GcnParams {
   int32_t d_full; int32_t c0;
   const int64_t* row_id;                           // ROW_ID: dropout row of output row io (element index row_id[io] * d_full + col)
 };
-
-__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-__device__ __forceinline__ uint32_t drop_bits(uint64_t e, uint64_t seed) {
-  uint32_t w0, w1;
-  drop_words(e >> 2, seed, w0, w1);
-  const uint32_t w = (e & 2) ? w1 : w0;
-  return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
 
 template <int LF, int EP, int U, int EPI, int MODE, bool ROW_ID = false>
 __global__ __launch_bounds__(256) void gcn_agg_kernel(GcnParams p) {
@@ -118,12 +107,7 @@ __global__ __launch_bounds__(256) void gcn_agg_kernel(GcnParams p) {
         acc.x += w[u] * v[u].x; acc.y += w[u] * v[u].y; acc.z += w[u] * v[u].z; acc.w += w[u] * v[u].w;
       }
     }
-    // sum of the EP sub-groups' partials (fixed butterfly: deterministic)
-#pragma unroll
-    for (int off = LF; off < GL; off <<= 1) {
-      acc.x += __shfl_xor(acc.x, off); acc.y += __shfl_xor(acc.y, off);
-      acc.z += __shfl_xor(acc.z, off); acc.w += __shfl_xor(acc.w, off);
-    }
+    acc = ep_sum<LF, GL>(acc);
     // the row written: the segment's partial row, the hub's own row, or row i
     int64_t io = i;
     if (MODE == MODE_FINISH) io = rvalid ? (int64_t)p.hub_rows[i] : 0;
@@ -145,30 +129,10 @@ __global__ __launch_bounds__(256) void gcn_agg_kernel(GcnParams p) {
         // the row the mask is drawn for: one 8-byte load per group after the gather loop (a hub's finish group reads its hub's)
         const int64_t ih = ovalid ? (ROW_ID ? p.row_id[io] : io) : 0;
         const uint64_t e = (uint64_t)ih * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
-        if ((p.d_full & 3) == 0) {                              // the four columns share one word pair (as bgnn_norm.hip)
-          uint32_t w0, w1;
-          drop_words(e >> 2, seed, w0, w1);
-          const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) o[c] = bits[c] >= p.thr ? o[c] * p.keep_scale : 0.f;
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) o[c] = drop_bits(e + c, seed) >= p.thr ? o[c] * p.keep_scale : 0.f;
-        }
+        drop4(o, e, (p.d_full & 3) == 0, seed, p.thr, p.keep_scale);
       }
     } else if (EPI == EPI_LOGSOFTMAX) {
-      // the whole row (D <= 4*LF) sits in the LF lanes of the group; every lane takes part in the cross-lane steps
-      float m = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) m = fmaxf(m, o[c]);
-      m = bgnn::group_max<LF>(m);
-      float se = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) se += expf(o[c] - m);
-      se = bgnn::group_sum<LF>(se);
-      const float lse = m + logf(se);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] -= lse;
+      log_softmax4<LF>(o, f0, p.D);
     }
     if (ovalid && sub == 0 && fvalid) {
 #pragma unroll
@@ -178,77 +142,12 @@ __global__ __launch_bounds__(256) void gcn_agg_kernel(GcnParams p) {
   }
 }
 
-// ---- backward row pass: g from (y, dy) ---------------------------------------------------------------------------
-struct RowParams {
-  const float* y; int64_t ldy;
-  const float* gy; int64_t ldgy;
-  int64_t n_rows;
-  int32_t D;
-  float keep_scale;
-  float* g; int64_t ldg;
-};
-
-template <int LF, int EPI>
-__global__ __launch_bounds__(256) void gcn_bwd_rows_kernel(RowParams p) {
-  constexpr int RPB = 256 / LF;
-  const int r = threadIdx.x / LF;
-  const int f0 = (threadIdx.x % LF) * 4;
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < p.n_rows; base += (int64_t)gridDim.x * RPB) {
-    const int64_t i = base + r;
-    const bool rvalid = i < p.n_rows;
-    const int64_t ic = rvalid ? i : 0;
-    if (EPI == EPI_LOGSOFTMAX) {
-      // g = dY - exp(Y) * sum(dY): one column chunk (D <= 4*LF); all lanes reach the group reduction
-      float4 y = f4_zero(), dy = f4_zero();
-      const bool fvalid = f0 < p.D && rvalid;
-      if (fvalid) {
-        y = *reinterpret_cast<const float4*>(p.y + ic * p.ldy + f0);
-        dy = *reinterpret_cast<const float4*>(p.gy + ic * p.ldgy + f0);
-      }
-      const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
-      float t = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) t += dv[c];
-      t = bgnn::group_sum<LF>(t);
-      float o[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] = (f0 + c < p.D) ? dv[c] - expf(yv[c]) * t : 0.f;
-      if (fvalid) *reinterpret_cast<float4*>(p.g + i * p.ldg + f0) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-      if (!rvalid) continue;
-      for (int f = f0; f < p.D; f += 4 * LF) {
-        float4 y = f4_zero();
-        if (EPI == EPI_RELU) y = *reinterpret_cast<const float4*>(p.y + i * p.ldy + f);
-        const float4 dy = *reinterpret_cast<const float4*>(p.gy + i * p.ldgy + f);
-        const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
-        float o[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          // ReLU then dropout: y > 0 <=> kept and positive, so no pre-activation is needed
-          o[c] = EPI == EPI_RELU ? (yv[c] > 0.f ? dv[c] * p.keep_scale : 0.f) : dv[c];
-          if (f + c >= p.D) o[c] = 0.f;
-        }
-        *reinterpret_cast<float4*>(p.g + i * p.ldg + f) = make_float4(o[0], o[1], o[2], o[3]);
-      }
-    }
-  }
-}
-
 template <int LF, int EP, int U, int EPI, int MODE, bool ROW_ID>
 int launch_agg(const GcnParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
-  static const int cap = [] {
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gcn_agg_kernel<LF, EP, U, EPI, MODE, ROW_ID>, 256, 0) != hipSuccess || per_cu < 1)
-      return 2048;
-    if (per_cu > 8) per_cu = 8;
-    return per_cu * prop.multiProcessorCount / 8 * 8;
-  }();
+  static int cap = 0;
   const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
-  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;   // multiple of 8 (XCD split)
-  if (grid < 8) grid = 8;
+  const int grid = persistent_grid(gcn_agg_kernel<LF, EP, U, EPI, MODE, ROW_ID>, ntiles, &cap);
   hipLaunchKernelGGL((gcn_agg_kernel<LF, EP, U, EPI, MODE, ROW_ID>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
@@ -256,46 +155,16 @@ int launch_agg(const GcnParams& p, hipStream_t st) {
 
 template <int EPI, int MODE, bool ROW_ID = false>
 int dispatch_agg(const GcnParams& p, hipStream_t st) {
-  const int nv = (p.D + 3) / 4;   // float4 slots of the slice
-  if (nv <= 1) return launch_agg<1, 8, 4, EPI, MODE, ROW_ID>(p, st);
-  if (nv <= 2) return launch_agg<2, 4, 4, EPI, MODE, ROW_ID>(p, st);
-  if (nv <= 4) return launch_agg<4, 2, 4, EPI, MODE, ROW_ID>(p, st);
-  if (nv <= 8) return launch_agg<8, 1, 8, EPI, MODE, ROW_ID>(p, st);
-  if (nv <= 16) return launch_agg<16, 1, 8, EPI, MODE, ROW_ID>(p, st);
-  return launch_agg<32, 1, 8, EPI, MODE, ROW_ID>(p, st);
+  return lf_ladder((p.D + 3) / 4,   // float4 slots of the slice
+                   [&](auto LF, auto EP, auto U) { return launch_agg<LF, EP, U, EPI, MODE, ROW_ID>(p, st); });
 }
 
 template <int MODE>
 int dispatch_epi(int epilogue, const GcnParams& p, hipStream_t st) {
   // the row-id variant exists only where a mask is drawn; every other call runs the kernels it always ran
   if (epilogue == EPI_RELU && p.row_id != nullptr && p.thr != 0u) return dispatch_agg<EPI_RELU, MODE, true>(p, st);
-  return epilogue == EPI_RELU ? dispatch_agg<EPI_RELU, MODE>(p, st)
-       : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX, MODE>(p, st) : dispatch_agg<EPI_NONE, MODE>(p, st);
+  return epi_switch(epilogue, [&](auto EPI) { return dispatch_agg<EPI, MODE>(p, st); });
 }
-
-template <int LF, int EPI>
-int launch_bwd_rows(const RowParams& p, hipStream_t st) {
-  constexpr int RPB = 256 / LF;
-  int64_t grid = (p.n_rows + RPB - 1) / RPB;
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((gcn_bwd_rows_kernel<LF, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
-  BGNN_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int EPI>
-int dispatch_bwd_rows(const RowParams& p, hipStream_t st) {
-  const int nv = (p.D + 3) / 4;
-  if (nv <= 1) return launch_bwd_rows<1, EPI>(p, st);
-  if (nv <= 2) return launch_bwd_rows<2, EPI>(p, st);
-  if (nv <= 4) return launch_bwd_rows<4, EPI>(p, st);
-  if (nv <= 8) return launch_bwd_rows<8, EPI>(p, st);
-  if (nv <= 16) return launch_bwd_rows<16, EPI>(p, st);
-  return launch_bwd_rows<32, EPI>(p, st);
-}
-
-bool ld_ok(int64_t ld, int32_t D) { return ld >= ((int64_t)D + 3) / 4 * 4 && (ld & 3) == 0; }
 
 int64_t part_ld(int32_t D) { return D < SLICE ? ((int64_t)D + 3) / 4 * 4 : SLICE; }
 
@@ -305,10 +174,8 @@ int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias, co
              const int32_t* seg_bounds, int64_t n_seg, void* ws, size_t ws_bytes, float* out, int64_t ldo, hipStream_t st,
              const int64_t* row_id = nullptr) {
   if (!tbl || !rowptr || !col || !dinv || !out) return BGNN_E_NULL;
-  if (n_rows < 0 || n_tbl < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
-  if (n_dinv < n_rows || n_dinv < n_tbl) return BGNN_E_SHAPE;
-  if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
-  if (p_drop > 0.f && epilogue != EPI_RELU) return BGNN_E_SHAPE;
+  if (n_rows < 0 || n_tbl < 0 || D <= 0 || n_dinv < n_rows || n_dinv < n_tbl) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
   if (!ld_ok(ldt, D) || !ld_ok(ldo, D)) return BGNN_E_ALIGN;
   if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (bias && !bgnn_aligned16(bias))) return BGNN_E_ALIGN;
   const bool hubs = n_hubs > 0;
@@ -391,20 +258,18 @@ extern "C" int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const flo
   if (!grad_y || !t_rowptr || !t_col || !dinv || !g || !grad_tbl) return BGNN_E_NULL;
   if (epilogue == EPI_RELU && !y) return BGNN_E_NULL;
   if (epilogue == EPI_LOGSOFTMAX && !y) return BGNN_E_NULL;
-  if (n_rows < 0 || n_src < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
-  if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
-  if (p_drop > 0.f && epilogue != EPI_RELU) return BGNN_E_SHAPE;
+  if (n_rows < 0 || n_src < 0 || D <= 0) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
   if ((y && !ld_ok(ldy, D)) || !ld_ok(ldgy, D) || !ld_ok(ldg, D) || !ld_ok(ldgt, D)) return BGNN_E_ALIGN;
   if ((y && !bgnn_aligned16(y)) || !bgnn_aligned16(grad_y) || !bgnn_aligned16(g) || !bgnn_aligned16(grad_tbl)) return BGNN_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (n_rows > 0) {
-    RowParams p{};
+    BwdRowsParams p{};
     p.y = y; p.ldy = ldy; p.gy = grad_y; p.ldgy = ldgy; p.n_rows = n_rows; p.D = D;
     uint32_t thr;
     drop_consts(p_drop, thr, p.keep_scale);
     p.g = g; p.ldg = ldg;
-    const int rc = epilogue == EPI_RELU ? dispatch_bwd_rows<EPI_RELU>(p, st)
-                 : epilogue == EPI_LOGSOFTMAX ? dispatch_bwd_rows<EPI_LOGSOFTMAX>(p, st) : dispatch_bwd_rows<EPI_NONE>(p, st);
+    const int rc = dispatch_bwd_rows<false>(epilogue, p, st);
     if (rc != 0) return rc;
   }
   // the forward walk over the by-source view (every id in t_col is a destination row < n_rows)

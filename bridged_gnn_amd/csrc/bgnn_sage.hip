@@ -10,22 +10,19 @@
 //             by-source view) -- two launches, no float atomics, bit-identical from run to run.
 // There is no attention math: the forward is gather-bound.  Algorithmic bytes at width D: E'(4D + 4) + N(8D + 4).
 //
-// Mapping (as agg_kernel in bgnn_aggregate.hip): a group of GL = LF*EP consecutive lanes owns one output row; LF lanes span
-// the columns (float4 per lane), EP sub-groups walk different edges of the row (narrow rows), each sub-group keeps U neighbour
-// rows in flight.  Blocks are persistent over the XCD-balanced segment order of bgnn_common.h.  A launch covers at most 128
-// columns; wider rows run as column slices (one launch per slice).
+// Mapping, dropout hash, epilogue pieces, backward row kernel and launch helpers: bgnn_conv_common.h.  A launch
+// covers at most 128 columns; wider rows run as column slices (one launch per slice).
 //
 // Two compile-time variants of the same kernel serve a destination-node partition (dist_sage.py): ROW_ID keys the dropout hash
 // on a caller-given GLOBAL row id per output row (a rank's rows then draw the masks of the whole-graph call), and OUT_ROW
 // writes output row s to dst[row[s]] (optionally adding what is there): bgnn_rows_segment_add_f32, which folds the gradient
 // rows returned by the reverse halo exchange into their owners' rows.  The plain entry point instantiates neither.
-#include "bgnn_common.h"
+#include "bgnn_conv_common.h"
 
 namespace {
 
-constexpr int SLICE = 128;   // columns per forward launch (LF <= 32)
-
-enum { EPI_NONE = 0, EPI_RELU = 1, EPI_LOGSOFTMAX = 2 };
+using namespace bgnn_conv;
+constexpr int EPI_RELU = EPI_ACT;   // code 1 here: ReLU, then dropout
 
 struct SageParams {
   const float* tbl; int64_t ldt; int64_t n_tbl;    // neighbour table (column-offset to the slice), its stride and row count
@@ -41,16 +38,6 @@ struct SageParams {
   const int64_t* row_id;                           // ROW_ID: dropout row of output row i (element index row_id[i] * d_full + col)
   const int32_t* out_row; int64_t n_out;          // OUT_ROW: output row i lands in (and its root is read from) row out_row[i]
 };
-
-__device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-// 16 dropout bits of element e (row * d_full + column)
-__device__ __forceinline__ uint32_t drop_bits(uint64_t e, uint64_t seed) {
-  uint32_t w0, w1;
-  drop_words(e >> 2, seed, w0, w1);
-  const uint32_t w = (e & 2) ? w1 : w0;
-  return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
 
 template <int LF, int EP, int U, int EPI, bool ROW_ID = false, bool OUT_ROW = false>
 __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
@@ -105,12 +92,7 @@ __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
         acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
       }
     }
-    // sum of the EP sub-groups' partials (fixed butterfly: deterministic)
-#pragma unroll
-    for (int off = LF; off < GL; off <<= 1) {
-      acc.x += __shfl_xor(acc.x, off); acc.y += __shfl_xor(acc.y, off);
-      acc.z += __shfl_xor(acc.z, off); acc.w += __shfl_xor(acc.w, off);
-    }
+    acc = ep_sum<LF, GL>(acc);
     const float s = (p.mean && deg > 0) ? 1.f / (float)deg : 1.f;
     float o[4] = {acc.x * s, acc.y * s, acc.z * s, acc.w * s};
     const int64_t io = OUT_ROW ? (rvalid ? (int64_t)p.out_row[i] : 0) : i;   // the row written (and whose root is added)
@@ -125,30 +107,10 @@ __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
       if (p.thr != 0u) {
         const int64_t ih = ROW_ID ? (rvalid ? p.row_id[i] : 0) : (rvalid ? i : 0);
         const uint64_t e = (uint64_t)ih * (uint64_t)p.d_full + (uint64_t)(p.c0 + f0);
-        if ((p.d_full & 3) == 0) {                              // the four columns share one word pair (as bgnn_norm.hip)
-          uint32_t w0, w1;
-          drop_words(e >> 2, seed, w0, w1);
-          const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) o[c] = bits[c] >= p.thr ? o[c] * p.keep_scale : 0.f;
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) o[c] = drop_bits(e + c, seed) >= p.thr ? o[c] * p.keep_scale : 0.f;
-        }
+        drop4(o, e, (p.d_full & 3) == 0, seed, p.thr, p.keep_scale);
       }
     } else if (EPI == EPI_LOGSOFTMAX) {
-      // the whole row (D <= 4*LF) sits in the LF lanes of the group; every lane takes part in the cross-lane steps
-      float m = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) m = fmaxf(m, o[c]);
-      m = bgnn::group_max<LF>(m);
-      float se = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) se += expf(o[c] - m);
-      se = bgnn::group_sum<LF>(se);
-      const float lse = m + logf(se);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] -= lse;
+      log_softmax4<LF>(o, f0, p.D);
     }
     if (ovalid && sub == 0 && fvalid) {
 #pragma unroll
@@ -158,84 +120,12 @@ __global__ __launch_bounds__(256) void sage_agg_kernel(SageParams p) {
   }
 }
 
-// ---- backward pass A: per destination row, g from (y, dy); dT_r = g, S = g / deg -------------------------------
-struct BwdParams {
-  const float* y; int64_t ldy;
-  const float* gy; int64_t ldgy;
-  const int32_t* rowptr;
-  int64_t n_rows;
-  int32_t D;
-  float keep_scale;
-  float* g; int64_t ldg;      // dT_r
-  float* s; int64_t lds;      // scratch
-};
-
-template <int LF, int EPI>
-__global__ __launch_bounds__(256) void sage_bwd_rows_kernel(BwdParams p) {
-  constexpr int RPB = 256 / LF;
-  const int r = threadIdx.x / LF;
-  const int f0 = (threadIdx.x % LF) * 4;
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < p.n_rows; base += (int64_t)gridDim.x * RPB) {
-    const int64_t i = base + r;
-    const bool rvalid = i < p.n_rows;
-    const int64_t ic = rvalid ? i : 0;
-    const int32_t deg = rvalid ? p.rowptr[i + 1] - p.rowptr[i] : 0;
-    const float inv = deg > 0 ? 1.f / (float)deg : 0.f;
-    if (EPI == EPI_LOGSOFTMAX) {
-      // g = dY - exp(Y) * sum(dY): one column chunk (D <= 4*LF); all lanes reach the group reduction
-      float4 y = f4_zero(), dy = f4_zero();
-      const bool fvalid = f0 < p.D && rvalid;
-      if (fvalid) {
-        y = *reinterpret_cast<const float4*>(p.y + ic * p.ldy + f0);
-        dy = *reinterpret_cast<const float4*>(p.gy + ic * p.ldgy + f0);
-      }
-      const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
-      float t = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (f0 + c < p.D) t += dv[c];
-      t = bgnn::group_sum<LF>(t);
-      float o[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] = (f0 + c < p.D) ? dv[c] - expf(yv[c]) * t : 0.f;
-      if (fvalid) {
-        *reinterpret_cast<float4*>(p.g + i * p.ldg + f0) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(p.s + i * p.lds + f0) = make_float4(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
-      }
-    } else {
-      if (!rvalid) continue;
-      for (int f = f0; f < p.D; f += 4 * LF) {
-        const float4 y = *reinterpret_cast<const float4*>(p.y + i * p.ldy + f);
-        const float4 dy = *reinterpret_cast<const float4*>(p.gy + i * p.ldgy + f);
-        const float yv[4] = {y.x, y.y, y.z, y.w}, dv[4] = {dy.x, dy.y, dy.z, dy.w};
-        float o[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          // ReLU then dropout: y > 0 <=> kept and positive, so no pre-activation is needed
-          o[c] = EPI == EPI_RELU ? (yv[c] > 0.f ? dv[c] * p.keep_scale : 0.f) : dv[c];
-          if (f + c >= p.D) o[c] = 0.f;
-        }
-        *reinterpret_cast<float4*>(p.g + i * p.ldg + f) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(p.s + i * p.lds + f) = make_float4(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
-      }
-    }
-  }
-}
-
 template <int LF, int EP, int U, int EPI, bool ROW_ID, bool OUT_ROW>
 int launch_agg(const SageParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
-  static const int cap = [] {
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sage_agg_kernel<LF, EP, U, EPI, ROW_ID, OUT_ROW>, 256, 0) != hipSuccess || per_cu < 1)
-      return 2048;
-    if (per_cu > 8) per_cu = 8;
-    return per_cu * prop.multiProcessorCount / 8 * 8;
-  }();
+  static int cap = 0;
   const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
-  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;   // multiple of 8 (XCD split)
-  if (grid < 8) grid = 8;
+  const int grid = persistent_grid(sage_agg_kernel<LF, EP, U, EPI, ROW_ID, OUT_ROW>, ntiles, &cap);
   hipLaunchKernelGGL((sage_agg_kernel<LF, EP, U, EPI, ROW_ID, OUT_ROW>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
@@ -243,46 +133,16 @@ int launch_agg(const SageParams& p, hipStream_t st) {
 
 template <int EPI, bool ROW_ID = false, bool OUT_ROW = false>
 int dispatch_agg(const SageParams& p, hipStream_t st) {
-  const int nv = (p.D + 3) / 4;   // float4 slots of the slice
-  if (nv <= 1) return launch_agg<1, 8, 4, EPI, ROW_ID, OUT_ROW>(p, st);
-  if (nv <= 2) return launch_agg<2, 4, 4, EPI, ROW_ID, OUT_ROW>(p, st);
-  if (nv <= 4) return launch_agg<4, 2, 4, EPI, ROW_ID, OUT_ROW>(p, st);
-  if (nv <= 8) return launch_agg<8, 1, 8, EPI, ROW_ID, OUT_ROW>(p, st);
-  if (nv <= 16) return launch_agg<16, 1, 8, EPI, ROW_ID, OUT_ROW>(p, st);
-  return launch_agg<32, 1, 8, EPI, ROW_ID, OUT_ROW>(p, st);
+  return lf_ladder((p.D + 3) / 4,   // float4 slots of the slice
+                   [&](auto LF, auto EP, auto U) { return launch_agg<LF, EP, U, EPI, ROW_ID, OUT_ROW>(p, st); });
 }
-
-template <int LF, int EPI>
-int launch_bwd_rows(const BwdParams& p, hipStream_t st) {
-  constexpr int RPB = 256 / LF;
-  int64_t grid = (p.n_rows + RPB - 1) / RPB;
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((sage_bwd_rows_kernel<LF, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
-  BGNN_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int EPI>
-int dispatch_bwd_rows(const BwdParams& p, hipStream_t st) {
-  const int nv = (p.D + 3) / 4;
-  if (nv <= 1) return launch_bwd_rows<1, EPI>(p, st);
-  if (nv <= 2) return launch_bwd_rows<2, EPI>(p, st);
-  if (nv <= 4) return launch_bwd_rows<4, EPI>(p, st);
-  if (nv <= 8) return launch_bwd_rows<8, EPI>(p, st);
-  if (nv <= 16) return launch_bwd_rows<16, EPI>(p, st);
-  return launch_bwd_rows<32, EPI>(p, st);
-}
-
-bool ld_ok(int64_t ld, int32_t D) { return ld >= ((int64_t)D + 3) / 4 * 4 && (ld & 3) == 0; }
 
 int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root, int64_t ldr, const int32_t* rowptr,
              const int32_t* col, int64_t n_rows, int32_t D, int mean, int epilogue, float p_drop, uint64_t seed,
              const uint64_t* seed_dev, float* out, int64_t ldo, hipStream_t st, const int64_t* row_id = nullptr) {
   if (!tbl || !rowptr || !col || !out) return BGNN_E_NULL;
-  if (n_rows < 0 || n_tbl < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
-  if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
-  if (p_drop > 0.f && epilogue != EPI_RELU) return BGNN_E_SHAPE;
+  if (n_rows < 0 || n_tbl < 0 || D <= 0) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
   if (!ld_ok(ldt, D) || !ld_ok(ldo, D) || (root && !(ldr == 0 || ld_ok(ldr, D)))) return BGNN_E_ALIGN;
   if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (root && !bgnn_aligned16(root))) return BGNN_E_ALIGN;
   if (n_rows == 0) return 0;
@@ -360,9 +220,8 @@ extern "C" int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, con
                                                 void* ws, size_t ws_bytes, void* stream) {
   if (!grad_y || !rowptr || !t_rowptr || !t_col || !grad_tbl || !grad_root || !ws) return BGNN_E_NULL;
   if (epilogue != EPI_NONE && !y) return BGNN_E_NULL;
-  if (n_rows < 0 || n_src < 0 || D <= 0 || epilogue < 0 || epilogue > 2 || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
-  if (epilogue == EPI_LOGSOFTMAX && D > SLICE) return BGNN_E_SHAPE;
-  if (p_drop > 0.f && epilogue != EPI_RELU) return BGNN_E_SHAPE;
+  if (n_rows < 0 || n_src < 0 || D <= 0) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
   if (ws_bytes < bgnn_sage_mean_aggregate_bwd_workspace_bytes(n_rows, D)) return BGNN_E_WORKSPACE;
   if ((y && !ld_ok(ldy, D)) || !ld_ok(ldgy, D) || !ld_ok(ldgt, D) || !ld_ok(ldgr, D)) return BGNN_E_ALIGN;
   if ((y && !bgnn_aligned16(y)) || !bgnn_aligned16(grad_y) || !bgnn_aligned16(grad_tbl) || !bgnn_aligned16(grad_root))
@@ -371,13 +230,12 @@ extern "C" int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, con
   const int64_t lds = ((int64_t)D + 3) / 4 * 4;
   float* s = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws), 16));
   if (n_rows > 0) {
-    BwdParams p{};
+    BwdRowsParams p{};
     p.y = y; p.ldy = ldy; p.gy = grad_y; p.ldgy = ldgy; p.rowptr = rowptr; p.n_rows = n_rows; p.D = D;
     uint32_t thr;
     drop_consts(p_drop, thr, p.keep_scale);
     p.g = grad_root; p.ldg = ldgr; p.s = s; p.lds = lds;
-    const int rc = epilogue == EPI_RELU ? dispatch_bwd_rows<EPI_RELU>(p, st)
-                 : epilogue == EPI_LOGSOFTMAX ? dispatch_bwd_rows<EPI_LOGSOFTMAX>(p, st) : dispatch_bwd_rows<EPI_NONE>(p, st);
+    const int rc = dispatch_bwd_rows<true>(epilogue, p, st);   // pass A: dT_r = g, S = g / deg
     if (rc != 0) return rc;
   }
   // pass B: plain sum of the scratch rows over the by-source view (every id in t_col is a destination row < n_rows)

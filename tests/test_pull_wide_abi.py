@@ -27,3 +27,8 @@ def test_wide_pull_entries_are_declared_and_bound():
     assert "bgnn_aggregate_bwd_wide.hip" in _lib._HASHED_SOURCES
     mk = open(os.path.join(ROOT, "bridged_gnn_amd", "csrc", "Makefile")).read()
     assert "bgnn_aggregate_bwd_wide.hip" in mk
+    # the shared conv header is hashed, and the Makefile's digest reads the same files in the same order as the loader's
+    assert "bgnn_conv_common.h" in _lib._HASHED_SOURCES
+    srcs = re.search(r"^SRCS\s*=\s*(.*)$", mk, flags=re.M).group(1).split()
+    hashed = re.search(r"^HASHED\s*=\s*(.*)$", mk, flags=re.M).group(1).replace("$(SRCS)", " ".join(srcs)).split()
+    assert [os.path.normpath(f) for f in hashed] == [os.path.normpath(f) for f in _lib._HASHED_SOURCES]
