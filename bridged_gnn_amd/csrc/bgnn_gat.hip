@@ -31,43 +31,6 @@
 namespace {
 
 using namespace bgnn_conv;
-constexpr int EPI_ELU = EPI_ACT;   // code 1 here: ELU, then dropout
-constexpr int MAX_HEADS = 8;
-constexpr int MAX_C = SLICE;
-
-// leaky_relu with a ROUNDED product: never contracted into the subtraction of the row maximum that follows, so the three kernels
-// that form e (state sweep, coefficient sweep, backward edge pass) agree bit for bit
-__device__ __forceinline__ float leaky(float z, float slope) { return z > 0.f ? z : __fmul_rn(slope, z); }
-
-// a row's edge range cut to the edge arrays: a malformed rowptr gives a wrong sum, never a read or write past them
-__device__ __forceinline__ void clamp_row(int32_t& beg, int32_t& end, int64_t n_edges) {
-  if (beg < 0) beg = 0;
-  if ((int64_t)end > n_edges) end = (int32_t)n_edges;
-  if (end < beg) end = beg;
-}
-
-// four columns k0..k0+3 of a head slice of C floats at `base` (vec: the slice is 16-byte aligned and C % 4 == 0)
-__device__ __forceinline__ void load4(const float* base, int k0, int C, bool vec, bool ok, float (&v)[4]) {
-  v[0] = v[1] = v[2] = v[3] = 0.f;
-  if (!ok || k0 >= C) return;
-  if (vec) {
-    const float4 t = *reinterpret_cast<const float4*>(base + k0);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) if (k0 + c < C) v[c] = base[k0 + c];
-  }
-}
-
-__device__ __forceinline__ void store4(float* base, int k0, int C, bool vec, const float (&v)[4]) {
-  if (k0 >= C) return;
-  if (vec) {
-    *reinterpret_cast<float4*>(base + k0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) if (k0 + c < C) base[k0 + c] = v[c];
-  }
-}
 
 // ---- scores ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gat_scores_kernel(const float* __restrict__ tbl, int64_t ldt, int64_t n, int H, int C,
@@ -102,13 +65,6 @@ struct AlphaParams {
   float* state;                                    // [n_rows, H, 2] = (max, denominator)
   float* coef;                                     // [E', H]
 };
-
-__device__ __forceinline__ void softmax_merge(float& m, float& s, float m2, float s2) {
-  const float M = fmaxf(m, m2);
-  const float a = m == -INFINITY ? 0.f : s * expf(m - M);
-  const float b = m2 == -INFINITY ? 0.f : s2 * expf(m2 - M);
-  m = M; s = a + b;
-}
 
 template <int GL, int U>
 __global__ __launch_bounds__(256) void gat_alpha_kernel(AlphaParams p) {
@@ -305,79 +261,6 @@ __global__ __launch_bounds__(256) void gat_agg_kernel(AggParams p) {
   }
 }
 
-// ---- backward row pass: g from (pre, dy), r = <g, pre - bias> per virtual row --------------------------------------
-struct RowParams {
-  const float* pre; int64_t ldp;
-  const float* gy; int64_t ldgy;
-  const float* bias;
-  int64_t n_rows; int32_t H; int32_t C; int32_t npad;
-  uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_dev;
-  float* g; int64_t ldg;
-  float* r;                                        // [n_rows, H]
-};
-
-template <int LF, int EPI>
-__global__ __launch_bounds__(256) void gat_bwd_rows_kernel(RowParams p) {
-  constexpr int RPB = 256 / LF;
-  const int q = threadIdx.x / LF;
-  const int k0 = (threadIdx.x % LF) * 4;
-  const bool vec = (p.C & 3) == 0;
-  uint64_t seed = p.seed;
-  if (EPI == EPI_ELU && p.thr != 0u && p.seed_dev != nullptr) seed += *p.seed_dev;
-  const int64_t nv = p.n_rows * p.H;
-  for (int64_t base = (int64_t)blockIdx.x * RPB; base < nv; base += (int64_t)gridDim.x * RPB) {   // block-uniform trip count
-    const int64_t v = base + q;
-    const bool valid = v < nv;
-    const int64_t i = valid ? v / p.H : 0;
-    const int h = valid ? (int)(v - i * p.H) : 0;
-    const int64_t hoff = (int64_t)h * p.C;
-    float pr[4], dy[4], b[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-    load4(p.pre + i * p.ldp + hoff, k0, p.C, vec, valid, pr);
-    load4(p.gy + i * p.ldgy + hoff, k0, p.C, vec, valid, dy);
-    if (p.bias != nullptr) load4(p.bias + hoff, k0, p.C, vec, true, b);
-    if (EPI == EPI_ELU) {
-      const uint64_t e = (uint64_t)i * (uint64_t)(p.H * p.C) + (uint64_t)(hoff + k0);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        // the mask is redrawn, never read off y: ELU is 0 at a pre-activation of exactly 0, kept or not
-        const float mk = p.thr == 0u ? 1.f : (drop_bits(e + c, seed) >= p.thr ? p.keep_scale : 0.f);
-        o[c] = dy[c] * mk * (pr[c] > 0.f ? 1.f : expf(pr[c]));
-      }
-    } else if (EPI == EPI_LOGSOFTMAX) {
-      float m = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (k0 + c < p.C) m = fmaxf(m, pr[c]);
-      m = bgnn::group_max<LF>(m);
-      float se = 0.f, t = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (k0 + c < p.C) { se += expf(pr[c] - m); t += dy[c]; }
-      se = bgnn::group_sum<LF>(se);
-      t = bgnn::group_sum<LF>(t);
-      const float lse = m + logf(se);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] = dy[c] - expf(pr[c] - lse) * t;
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] = dy[c];
-    }
-    float rr = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (k0 + c >= p.C) o[c] = 0.f;
-      rr += o[c] * (pr[c] - b[c]);
-    }
-    rr = bgnn::group_sum<LF>(rr);
-    if (valid) {
-      store4(p.g + i * p.ldg + hoff, k0, p.C, vec, o);
-      if (k0 == 0) {
-        p.r[v] = rr;
-        if (h == p.H - 1)
-          for (int c = 0; c < p.npad; ++c) p.g[i * p.ldg + (int64_t)p.H * p.C + c] = 0.f;
-      }
-    }
-  }
-}
-
 // ---- backward edge pass over the by-destination CSR: dz per edge, ds_dst per virtual row ---------------------------
 struct EdgeParams {
   const float* tbl; int64_t ldt; int64_t n_tbl;
@@ -519,37 +402,6 @@ int dispatch_edge(const EdgeParams& p, hipStream_t st) {
   // four rows in flight on every rung: the ladder's U is not taken
   return lf_ladder((p.C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_edge<LF, EP, 4>(p, st); });
 }
-
-template <int LF, int EPI>
-int launch_rows(const RowParams& p, hipStream_t st) {
-  constexpr int RPB = 256 / LF;
-  int64_t grid = (p.n_rows * p.H + RPB - 1) / RPB;
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((gat_bwd_rows_kernel<LF, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
-  BGNN_LAUNCH_CHECK();
-  return 0;
-}
-
-int dispatch_rows(int epilogue, const RowParams& p, hipStream_t st) {
-  return epi_switch(epilogue, [&](auto EPI) {
-    return lf_ladder((p.C + 3) / 4, [&](auto LF, auto, auto) { return launch_rows<LF, EPI>(p, st); });
-  });
-}
-
-// a [rows, H*C] table whose head slices the kernels touch: leading dimension >= pad4(H*C), a multiple of 4, 16-byte aligned base
-bool tbl_ok(const float* t, int64_t ld, int32_t HC) { return bgnn_aligned16(t) && ld_ok(ld, HC); }
-
-bool shape_ok(int32_t H, int32_t C) { return H >= 1 && H <= MAX_HEADS && C >= 1 && C <= MAX_C; }
-
-// attention dropout: the threshold of the shared hash, but the kept coefficients are scaled by exactly 1/(1 - p) as F.dropout does
-// (drop_consts scales by the reciprocal of the quantised keep probability, 1.5e-5 away at p = 0.6)
-void att_drop_consts(float p_att, uint32_t& thr, float& scale) {
-  drop_consts(p_att, thr, scale);
-  if (p_att > 0.f) scale = 1.f / (1.f - p_att);
-}
-
-size_t coef_bytes(int64_t n_edges, int32_t H) { return bgnn_align_up((size_t)n_edges * (size_t)H * sizeof(float), 16); }
 
 }  // namespace
 

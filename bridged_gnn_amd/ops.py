@@ -10,7 +10,7 @@ from . import _lib as L
 
 __all__ = ["DstCSR", "build_dst_csr", "domain_delta", "pack_transform_heads", "adaptedconv_transform", "adaptedconv_aggregate", "linear", "linear_supported", "linear_narrow_supported", "linear_narrow_transform", "narrow_transform_finish", "gram", "gram_supported", "rowdot", "transform_bwd_prep", "topk_edges_coalesced",
            "l2_normalize_rows", "cosine_topk", "mlp_pair_topk", "topk_edges", "coalesce", "gather_rows", "pad4",
-           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "gcn_aggregate", "gcn_aggregate_bwd", "gat_scores", "gat_aggregate", "gat_aggregate_bwd", "wide_heads_supported",
+           "sage_mean_aggregate", "sage_mean_aggregate_bwd", "rows_segment_add", "gcn_aggregate", "gcn_aggregate_bwd", "gat_scores", "gat_aggregate", "gat_aggregate_bwd", "gatv2_aggregate", "gatv2_aggregate_bwd", "wide_heads_supported",
            "adaptedconv_aggregate_heads_wide", "adaptedconv_aggregate_heads_wide_bwd", "pair_csr", "pair_mlp_stats", "pair_mlp_loss",
            "pair_mlp_segsum", "pair_mlp_eval", "pair_mlp_count", "PAIR_MLP_WIDTH", "pair_cos_loss", "pair_cos_segsum", "pair_cos_count",
            "PAIR_COS_WIDTH"]
@@ -1210,6 +1210,103 @@ def gat_aggregate_bwd(tbl, s_src, s_dst, state, alpha, pre, grad_y, rowptr, col,
         L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(ds_src), L.ptr(ds_dst), L.stream())
     L.check(rc, "bgnn_gat_aggregate_bwd_f32")
     return grad_tbl, ds_src, ds_dst, (column_sums(g)[:H * C] if want_bias else None)
+
+
+def _gatv2_check(tbl, att, H, C, what):
+    """the one table [N, >= 2 * pad4(H*C)] (XL at column 0, XR at column pad4(H*C)) and att [H*C] -> (H, C, att flat and aligned)"""
+    H, C = int(H), int(C)
+    if not tbl.is_cuda:
+        raise RuntimeError(f"bridged_gnn_amd ops need CUDA(HIP) tensors; there is no CPU path (got a {tbl.device} tensor)")
+    if not (1 <= H <= GAT_MAX_HEADS and 1 <= C <= GAT_MAX_C):
+        raise RuntimeError(f"{what}: unsupported shape: heads = {H}, channels per head = {C} (1 <= heads <= {GAT_MAX_HEADS}, "
+                           f"1 <= channels <= {GAT_MAX_C})")
+    if tbl.dtype != torch.float32 or tbl.dim() != 2 or tbl.shape[1] < 2 * pad4(H * C) or tbl.stride(1) != 1:
+        raise ValueError(f"{what}: the table must be float32 [N, >= 2 * pad4(H*C)] with unit column stride")
+    a = att.reshape(-1).contiguous()
+    if a.dtype != torch.float32 or a.numel() != H * C or a.device != tbl.device:
+        raise ValueError("att must be float32 with H*C elements on the table's device")
+    if a.data_ptr() % 16:
+        a = a.clone()
+    return H, C, a
+
+
+def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slope=0.2, p_att=0.0, seed_att=0, seed_att_dev=None,
+                    epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_pre=False, return_alpha=False):
+    """GATv2 attention conv in one pass (models/backbones.py:302-358, bgnn.h: bgnn_gatv2_aggregate_f32) over a CSR that holds one self
+    loop per row (`build_dst_csr(rewrite_self_loops=True)`).  tbl [N, >= 2P], P = pad4(H*C): x_l at columns [0, H*C), x_r at
+    [P, P + H*C).  out[i,h,:] = epi(sum_t a~[t,h] * x_l[col[t],h,:] + bias[h,:]), a~ = softmax_t(<att[h], leaky_relu(x_l[col[t],h] +
+    x_r[i,h])>) * m[t,h], m the attention-dropout mask at p_att (element t*H + h of the counter hash, seed_att + seed_att_dev).
+    epilogue: None, "elu" (then dropout at p_drop, seed + seed_dev, element i*(H*C) + column) or "log_softmax" (H == 1).  bias:
+    float32 [>= H*C], 16-byte aligned, or None.
+    -> (out [n_rows, P], state [n_rows, H, 2] = (max, denominator), pre | None, alpha | None): pre (want_pre) is the conv output
+    before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order."""
+    H, C, a = _gatv2_check(tbl, att, H, C, "gatv2_aggregate")
+    n_rows, E = int(n_rows), int(col.shape[0])
+    dev = tbl.device
+    if epilogue == "log_softmax" and H != 1:
+        raise RuntimeError("gatv2_aggregate: unsupported shape: the log_softmax epilogue needs heads == 1")
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
+        raise ValueError("bias must be float32 [>= H*C]")
+    if int(tbl.shape[0]) < n_rows:
+        raise ValueError("the table must hold a row for every destination row")
+    _gat_need(rowptr, "rowptr", (n_rows + 1,), torch.int32)
+    _gat_need(col, "col", (E,), torch.int32)
+    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
+    _gat_need_seed_word(seed_dev, "seed_dev")
+    if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
+        raise ValueError("p_att and p_drop must lie in [0, 1)")
+    W = pad4(H * C)
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    state = torch.empty(n_rows, H, 2, dtype=torch.float32, device=dev)
+    alpha = torch.empty(E, H, dtype=torch.float32, device=dev) if return_alpha else None
+    pre = None
+    if want_pre:
+        pre = out if GAT_EPILOGUES[epilogue] == 0 else torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    pre_arg = pre if (pre is not None and pre is not out) else None
+    sa, sad = _seed_args(seed_att, seed_att_dev)
+    sf, sfd = _seed_args(seed, seed_dev)
+    rc = L.lib().bgnn_gatv2_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(a), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows, H, C,
+        float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(state), L.ptr(alpha),
+        L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gatv2_aggregate_f32")
+    return out, state, pre, alpha
+
+
+def gatv2_aggregate_bwd(tbl, att, state, pre, grad_y, rowptr, col, t_rowptr, t_eid, t_dst, H, C, bias=None, negative_slope=0.2,
+                        p_att=0.0, seed_att=0, seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_bias=True):
+    """Backward of `gatv2_aggregate` (bgnn.h: bgnn_gatv2_aggregate_bwd_f32) from the forward's table, (state, pre with want_pre) and
+    grad_y [N, >= pad4(H*C)] -> (grad_tbl [N, 2P] = the whole dL/dtbl: dx_l at columns [0, H*C), dx_r at [P, P + H*C), pad columns 0;
+    grad_att [H*C]; grad_bias [H*C] | None).  (t_rowptr, t_eid, t_dst) = `DstCSR.transposed()`.  The coefficients are rebuilt from
+    the state and both dropout masks redrawn from their seeds.  Four launches, no atomics: bit-identical runs."""
+    H, C, a = _gatv2_check(tbl, att, H, C, "gatv2_aggregate_bwd")
+    N, E = int(tbl.shape[0]), int(col.shape[0])
+    dev = tbl.device
+    W = pad4(H * C)
+    _gat_need(state, "state", (N, H, 2))
+    _gat_need_rows(pre, "pre", N, W)
+    _gat_need_rows(grad_y, "grad_y", N, W)
+    for t, what, n in ((rowptr, "rowptr", N + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
+        _gat_need(t, what, (n,), torch.int32)
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
+        raise ValueError("bias must be float32 [>= H*C]")
+    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
+    _gat_need_seed_word(seed_dev, "seed_dev")
+    lib = L.lib()
+    g = torch.empty(N, W, dtype=torch.float32, device=dev)
+    grad_tbl = torch.empty(N, 2 * W, dtype=torch.float32, device=dev)
+    grad_att = torch.empty(H * C, dtype=torch.float32, device=dev)
+    wsb = int(lib.bgnn_gatv2_aggregate_workspace_bytes(E, N, H, C))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    sa, sad = _seed_args(seed_att, seed_att_dev)
+    sf, sfd = _seed_args(seed, seed_dev)
+    rc = lib.bgnn_gatv2_aggregate_bwd_f32(
+        L.ptr_rows(tbl), tbl.stride(0), L.ptr(a), L.ptr(bias), L.ptr(state), L.ptr_rows(pre), pre.stride(0), L.ptr_rows(grad_y),
+        grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E, N, H, C, float(negative_slope),
+        float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws), ws.numel(), L.ptr_rows(g), g.stride(0),
+        L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(grad_att), L.stream())
+    L.check(rc, "bgnn_gatv2_aggregate_bwd_f32")
+    return grad_tbl, grad_att, (column_sums(g)[:H * C] if want_bias else None)
 
 
 def rows_segment_add(src, seg_ptr, idx, row, dst, D=None, accumulate=True):

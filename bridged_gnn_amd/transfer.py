@@ -607,8 +607,9 @@ def train_gnn_noDTC(args, dataset, data, save=False, repeat=3, num_epoch=200, gn
     'loss_train', 'eval_res', 'best_epoch', 'best_acc', 'final_acc'.  `graphed=True`: as in `train_gnn`."""
     if gnn not in ('GraphSAGE', 'GCN'):
         if gnn in ('MLP', 'GAT', 'GATv2', 'KTGNN'):
-            raise NotImplementedError(f"train_gnn_noDTC(gnn={gnn!r}): the baselines implemented are GraphSAGE (the one `main` uses) "
-                                      "and GCN; MLP, GAT, GATv2 and KTGNN without DTC are not")
+            raise NotImplementedError(f"train_gnn_noDTC(gnn={gnn!r}): the baselines implemented here are GraphSAGE (the one `main` "
+                                      "uses) and GCN; GAT and GATv2 run through gat.train_gat_noDTC and gatv2.train_gatv2_noDTC; "
+                                      "MLP and KTGNN without DTC are not built")
         raise NotImplementedError('Not Implemented Model:{}'.format(gnn))
     from .gcn import GCNNet
     from .sage import GraphSAGE

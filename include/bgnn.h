@@ -35,7 +35,8 @@ extern "C" {
  * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size, and for the GCN baseline's
  * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for partitioned GCN's
  * bgnn_gcn_aggregate_rows_f32, and for the GAT baseline's bgnn_gat_scores_f32, bgnn_gat_aggregate_f32, bgnn_gat_aggregate_bwd_f32 and
- * their workspace size (added after 114 without changing it).
+ * their workspace size (added after 114 without changing it), and for the GATv2 baseline's bgnn_gatv2_aggregate_f32,
+ * bgnn_gatv2_aggregate_bwd_f32 and their workspace size (likewise).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
  * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone. */
@@ -594,6 +595,49 @@ int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, con
                                const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
                                const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
                                float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GATv2 attention conv (the `gnn='GATv2'` baseline of main_graph_knowledge_transfer.py:329-330):
+ *     models/backbones.py:302-358 -- PyG GATv2Conv (share_weights=False: lin_l and lin_r with bias; heads, concat,
+ *     negative_slope 0.2, attention dropout, add_self_loops, bias) with F.elu + F.dropout between the convs (:354-355) and
+ *     log_softmax (:358).
+ * The caller transforms first into ONE table tbl = x [W_l ; W_r]^T + [b_l ; b_r]: x_l[n,h,:] at tbl[n*ldt + h*C], x_r[n,h,:] at
+ * tbl[n*ldt + P + h*C], P = pad4(H*C); ldt a multiple of 4, >= 2P; n_tbl >= n_rows rows.  The CSR is GAT's: by destination with
+ * exactly one self loop per row (bgnn_build_dst_csr with rewrite_self_loops).  1 <= H <= 8, 1 <= C <= 128 (else BGNN_E_SHAPE).
+ * bgnn_gatv2_aggregate_f32, for row i, head h over the edges t of the row, j = col[t], in ONE pass (online softmax):
+ *   m = x_l[j,h,:] + x_r[i,h,:] (one rounded fp32 add per column);  e = sum_c att[h,c] * (m_c > 0 ? m_c : negative_slope * m_c);
+ *   alpha = softmax_t(e);  a~ = alpha * mask[t,h], mask = 0 or 1/(1 - p_att) from the counter hash at element t*H + h with
+ *   seed_att (+ *seed_att_dev_opt) -- GAT's contract; the denominator sums every edge;
+ *   out[i,h,:] = epi( sum_t a~ * x_l[j,h,:] + bias[h,:] ).
+ * att: [H*C] floats, 16-byte aligned.  Epilogues as bgnn_gat_aggregate_f32 (0 none; 1 ELU then dropout at p_drop over element
+ * i*(H*C) + h*C + c with seed (+ *seed_dev_opt); 2 row log_softmax, H == 1 only).  Outputs: state [n_rows, H, 2] = (maximum,
+ * denominator >= 1); alpha_out_opt [n_edges, H]: the coefficients a~ in CSR order (NULL: not formed; the pass parks the logits
+ * there and a sweep over the row's own words finishes them, no second gather); pre_out_opt [n_rows, ldp]: the conv output
+ * before the epilogue (NULL: not written); out [n_rows, ldo]; pad columns H*C .. P of out and pre_out leave as 0.
+ * bgnn_gatv2_aggregate_bwd_f32: the atomic-free backward from (tbl, att, state, pre) and grad_y; n_rows rows are both sources
+ * and destinations.  A row pass writes g [n_rows, ldg] and r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]> as GAT's does; a pass
+ * over the by-destination CSR regathers x_l[j], rebuilds e with the forward's own operations, alpha = exp(e - max) / den,
+ * da = mask * <g[i,h,:], x_l[j,h,:]>, de = alpha * (da - r); de and a~ go to ws, grad_tbl[i, P + h*C + c] = sum_t de * att[h,c] *
+ * leaky'(m_c), and grad_att[h,c] = sum over all edges of de * leaky(m_c): per block partial rows added in a fixed order by a small
+ * second kernel; a pass over the by-source view (t_rowptr, t_eid, t_dst: `DstCSR.transposed()`) gathers g[i] and x_r[i]:
+ * grad_tbl[j, h*C + c] = sum a~ * g[i,h,c] + de * att[h,c] * leaky'(x_l[j,h,c] + x_r[i,h,c]).  grad_tbl [n_rows, ldgt >= 2P] is the
+ * whole gradient of tbl (pad columns 0); the caller finishes with grad_bias = column sums of g.  No float atomics: two identical
+ * calls are bitwise equal.  ws: bgnn_gatv2_aggregate_workspace_bytes(n_edges, n_rows, H, C).  A row's edge range is cut to
+ * [0, n_edges] and ids are checked against their tables.  The entry points are defined in csrc/bgnn_gatv2.hip next to their
+ * kernels. */
+size_t bgnn_gatv2_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H, int32_t C);
+int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
+                             const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
+                             float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
+                             int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* state,
+                             float* alpha_out_opt, float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
+int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att, const float* bias_opt, const float* state,
+                                 const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr,
+                                 const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
+                                 int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
+                                 uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                 const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
+                                 float* grad_tbl, int64_t ldgt, float* grad_att, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
