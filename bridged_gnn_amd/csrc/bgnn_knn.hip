@@ -13,6 +13,8 @@
 //      and prove  kth_exact > (best score any excluded candidate can have) + eps ; unproven rows are queued;
 //   3. PRECISE pass on the queued rows only: the same kernel with three piece products (eps ~ 5e-5) + refine;
 //   4. rows still unproven (exact ties across the boundary) are re-done exhaustively in canonical arithmetic.
+// The mlp scorer runs stage 1 as an fp32 VALU pass, then stages 2 and 4, with a bound per query proven from the call's data
+// (derivation above mlp_colmax_kernel).
 // Index results are therefore bit-identical to oracle/oracle_c.c orc_cosine_topk / orc_mlp_topk.
 #include <cstdlib>
 #include "bgnn_common.h"
@@ -87,7 +89,8 @@ __device__ __forceinline__ uint32_t bgnn_wave_max_u32(uint32_t x) {
 // matter for a proof with error bound eps = margin / 2 -- or a KP-th-best bracket when more than KP entries lie above it,
 // and the kept entries are packed to the front by ballot prefix (their order is irrelevant).
 // Invariant: every candidate that was ever refused or dropped has an approximate score <= tau (tau never decreases).
-template <int CAPV, int KPV>
+// PERQ: margin_abs is a per-lane value, the margin of the lane's own query (lane & 31); else it is the same in every lane.
+template <int CAPV, int KPV, bool PERQ = false>
 struct WaveTopK {
   static constexpr int CAP = CAPV, KP = KPV, EPL = (CAPV + 63) / 64, HC = CAPV / 2;
   static_assert(CAPV <= 128 && CAPV % 2 == 0, "one or two buffer entries per lane");
@@ -97,7 +100,7 @@ struct WaveTopK {
   // keep the address space visible to the compiler across the noinline helpers (ds_* instead of flat_* accesses)
   unsigned base;                         // byte offset of this wave's state in knn_smem
   int k;                                 // wanted neighbours
-  float margin_abs, margin_rel;          // margin(a) = margin_abs + margin_rel * |a|
+  float margin_abs;                      // margin = 2 x (the error bound of the approximate scores) + slack
   __device__ __forceinline__ uint32_t* skey() const { return reinterpret_cast<uint32_t*>(knn_smem + base); }            // [QPW][2][HC] score bits
   __device__ __forceinline__ uint32_t* sidx() const { return skey() + QPW * CAP; }                                      // [QPW][2][HC] candidate
   __device__ __forceinline__ int* cnt() const { return reinterpret_cast<int*>(sidx() + QPW * CAP); }                    // [2][QPW]: mailbox, index = lane
@@ -148,7 +151,7 @@ struct WaveTopK {
     float tm = -INFINITY;
     if (n >= k) {
       const float a = unord_f32(bracket(k, lo0, hi0));         // a lower bound of the k-th best, tight to 2^-11
-      tm = a - (margin_abs + margin_rel * fabsf(a));
+      tm = a - (PERQ ? __shfl(margin_abs, q) : margin_abs);
     }
     tm = fmaxf(tm, tau_old);
     uint32_t tmo = ord_f32(tm);
@@ -438,7 +441,6 @@ __global__ __launch_bounds__(64 * NW) void cosine_pass1_kernel(const P1Params p)
   tk.carve((unsigned)((size_t)2 * STAGE_ELEMS * 2 + (size_t)wave * TK::BYTES));
   tk.k = p.k;
   tk.margin_abs = 2.f * knn_eps(p.eps, NPROD) + 1e-7f;
-  tk.margin_rel = 0.f;
 
   // staging: CT x NCH 16-byte chunks per piece over NT threads
   constexpr int CH_TILE = CT * NCH;
@@ -615,14 +617,67 @@ __global__ __launch_bounds__(64 * NW) void cosine_pass1_kernel(const P1Params p)
 constexpr int MLP_H = 128;
 constexpr int MLP_WAVES = 4;
 constexpr int MLP_CT = MT;          // candidates per staged tile of the mlp pass
+
+// ---- error bound of the mlp pass ---------------------------------------------------------------
+// Pass 1 evaluates, with u = 2^-24 (fp32 round to nearest) and x_h = a_h + b_h,
+//   acc_0 = b2,   acc_h = fl(w_h r_h + acc_{h-1}),   r_h = max(t_h, 0),   t_h = fl(sc_h fl(x_h) + sh_h)      (two fmas, one add)
+// against the real value  s = b2 + sum_h w_h max(sc_h x_h + sh_h, 0).  With m_h = |sc_h| |x_h| + |sh_h|:
+//   t_h = (sc_h x_h (1+d1) + sh_h)(1+d2), |d| <= u   ->  |t_h - (sc_h x_h + sh_h)| <= (2u + u^2) m_h ; max(., 0) is 1-Lipschitz, so
+//   |r_h - r*_h| <= (2u + u^2) m_h  and  |r_h| <= (1+u)^2 m_h ;
+//   acc_H = b2 prod_{j<=H}(1+e_j) + sum_h w_h r_h prod_{j>=h}(1+e_j)  ->  |acc_H - (b2 + sum_h w_h r_h)| <= ((1+u)^H - 1)(|b2| + sum_h |w_h| |r_h|) ;
+//   together  |acc_H - s| <= (H + 2) u (1 + O(H u)) S ,   S = |b2| + sum_h |w_h| m_h .
+// The bound follows S, NOT |s|: where large terms cancel |s| is small and the error is not.  S is bounded per QUERY over all
+// candidates by |x_h| <= colmax_h + |b_qh|, colmax_h = max_c |A[c][h]| (one column reduction per call), so
+//   eps_q = (H + 4) u 1.01 (|b2| + sum_h |w_h| (|sc_h| (colmax_h + |b_qh|) + |sh_h|)) + 1e-30 .
+// H + 4 instead of H + 2 and the factor 1.01 cover the second-order terms, the fp32 evaluation of this very sum (all terms >= 0:
+// relative error < (H + 4) u), and the distance of the CANONICAL fp64 score from s (five fp64 roundings per unit: < (H + 6) 2^-53 S); 1e-30 covers results
+// that underflow.  mlp_eps_kernel writes eps_q to the workspace once; pass 1's margin, the refine stage's T and its proof all read that value.
+__global__ __launch_bounds__(256) void mlp_colmax_kernel(const float* __restrict__ A, int64_t Nc, uint32_t* __restrict__ colmax /*[MLP_H], zeroed*/) {
+  // thread = (float4 column group, one of 8 row phases); blocks stride over the rows; |x| >= 0, so the raw bits order like the values
+  __shared__ float4 red[256];
+  const int c4 = threadIdx.x & 31, ph = threadIdx.x >> 5;
+  float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int64_t row = (int64_t)blockIdx.x * 8 + ph; row < Nc; row += (int64_t)gridDim.x * 8) {
+    const float4 v = *reinterpret_cast<const float4*>(A + row * MLP_H + c4 * 4);
+    m.x = fmaxf(m.x, fabsf(v.x)); m.y = fmaxf(m.y, fabsf(v.y)); m.z = fmaxf(m.z, fabsf(v.z)); m.w = fmaxf(m.w, fabsf(v.w));
+  }
+  red[threadIdx.x] = m;
+  __syncthreads();
+  if (ph == 0) {
+    for (int r = 1; r < 8; ++r) {
+      const float4 o = red[r * 32 + c4];
+      m.x = fmaxf(m.x, o.x); m.y = fmaxf(m.y, o.y); m.z = fmaxf(m.z, o.z); m.w = fmaxf(m.w, o.w);
+    }
+    atomicMax(&colmax[c4 * 4 + 0], __float_as_uint(m.x));
+    atomicMax(&colmax[c4 * 4 + 1], __float_as_uint(m.y));
+    atomicMax(&colmax[c4 * 4 + 2], __float_as_uint(m.z));
+    atomicMax(&colmax[c4 * 4 + 3], __float_as_uint(m.w));
+  }
+}
+
+// one wave per query: eps_q of the comment above
+__global__ __launch_bounds__(256) void mlp_eps_kernel(const float* __restrict__ B, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                      const float* __restrict__ w2, float b2, const uint32_t* __restrict__ colmax, int64_t Nq,
+                                                      float* __restrict__ eps_q) {
+  const int lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= Nq) return;                               // wave-uniform
+  float s = 0.f;
+#pragma unroll
+  for (int h = lane; h < MLP_H; h += 64)
+    s += fabsf(w2[h]) * (fabsf(scale[h]) * (__uint_as_float(colmax[h]) + fabsf(B[q * MLP_H + h])) + fabsf(shift[h]));
+  s = bgnn::group_sum<64>(s);
+  if (lane == 0) eps_q[q] = (float)(MLP_H + 4) * 5.9604645e-8f * 1.01f * (fabsf(b2) + s) + 1e-30f;
+}
+
 template <int CAPV, int KPV>
 __global__ __launch_bounds__(256, 1) void mlp_pass1_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            const float* __restrict__ w2, float b2, int64_t Nq, int64_t Nc, int k,
-                                                           float err_abs, float err_rel,
+                                                           const float* __restrict__ eps_q,
                                                            float* __restrict__ sl_score, int32_t* __restrict__ sl_idx,
                                                            float* __restrict__ sl_tau) {
-  typedef WaveTopK<CAPV, KPV> TK;
+  typedef WaveTopK<CAPV, KPV, true> TK;
   constexpr int H = MLP_H, LD = H + 4;
   float* stage = reinterpret_cast<float*>(knn_smem);                                // [MLP_CT][LD]
   float* coefs = stage + MLP_CT * LD;                                                   // scale|shift|w2 [3][H]
@@ -631,8 +686,7 @@ __global__ __launch_bounds__(256, 1) void mlp_pass1_kernel(const float* __restri
   TK tk;
   tk.carve((unsigned)(sizeof(float) * (MLP_CT * LD + 3 * H) + (size_t)wave * TK::BYTES));
   tk.k = k;
-  tk.margin_abs = 2.f * err_abs + 1e-7f;
-  tk.margin_rel = 2.f * err_rel;
+  tk.margin_abs = 2.f * (q0 + (lane & 31) < Nq ? eps_q[q0 + (lane & 31)] : 0.f) + 1e-7f;      // this lane's query
   tk.init(lane, -INFINITY);
   for (int t = tid; t < H; t += 256) { coefs[t] = scale[t]; coefs[H + t] = shift[t]; coefs[2 * H + t] = w2[t]; }
   float4 bqv[H / 4];                 // this lane's query row B[q][:], statically indexed (registers)
@@ -692,7 +746,7 @@ __device__ __forceinline__ double quad_bcast_f64(double v) {
 
 struct CosineCanon {
   const float* qq; const float* qc; int d;
-  static constexpr bool COOP4 = true;
+  static constexpr bool COOP4 = true, EPS_PER_QUERY = false;
   // The same sum, evaluated by a QUAD of lanes for one candidate: lane j holds floats 16i + 4j .. + 3 of both rows, so one load
   // instruction of the quad covers one 64-byte line (a lane walking "its" row alone touches a line per lane and instruction, and
   // the refine stage was bound by that request rate).  The running sum visits the elements in index order: within a line lane 0's
@@ -732,7 +786,7 @@ struct CosineCanon {
 };
 struct MlpCanon {
   const float* A; const float* B; const float* scale; const float* shift; const float* w2; float b2; int H;
-  static constexpr bool COOP4 = false;
+  static constexpr bool COOP4 = false, EPS_PER_QUERY = true;
   __device__ __forceinline__ double coop4(int64_t, int64_t, int) const { return 0.0; }
   __device__ __forceinline__ double operator()(int64_t q, int64_t c) const {
     const float* a = A + c * H;
@@ -761,8 +815,8 @@ struct RefineParams {
   int64_t Nq; const int32_t* qlist; const int32_t* nq_dev;
   int k, L, KP, nslots;
   const float* sl_score; const int32_t* sl_idx; const float* sl_tau;
-  EpsSrc eps; int nprod;                 // nprod > 0: bound from the residual maxima; else err_abs + err_rel |T|
-  double err_abs, err_rel;
+  EpsSrc eps; int nprod;                 // cosine: bound from the residual maxima of the product set
+  const float* eps_q;                    // mlp: bound per query row [Nq] (mlp_eps_kernel)
   int apply_sigmoid;
   int64_t* idx_out; float* val_out;
   int32_t* fail_list; int32_t* fail_count;
@@ -776,9 +830,11 @@ __global__ __launch_bounds__(256) void refine_kernel(Canon canon, const RefinePa
   int32_t* ei = reinterpret_cast<int32_t*>(reinterpret_cast<double*>(knn_smem) + (size_t)4 * L) + (size_t)wave * L;
   uint32_t* ea = reinterpret_cast<uint32_t*>(reinterpret_cast<int32_t*>(reinterpret_cast<double*>(knn_smem) + (size_t)4 * L) + (size_t)4 * L) + (size_t)wave * L;
   const int64_t nq = p.nq_dev ? (int64_t)*p.nq_dev : p.Nq;
-  const double eps = p.nprod > 0 ? (double)knn_eps(p.eps, p.nprod) : 0.0;
+  const double eps_call = Canon::EPS_PER_QUERY ? 0.0 : (double)knn_eps(p.eps, p.nprod);
   for (int64_t qi = (int64_t)blockIdx.x * 4 + wave; qi < nq; qi += (int64_t)gridDim.x * 4) {
     const int64_t q = p.qlist ? (int64_t)p.qlist[qi] : qi;
+    double eps = eps_call;
+    if constexpr (Canon::EPS_PER_QUERY) eps = (double)p.eps_q[q];
     float alast = -INFINITY;
     for (int s = lane; s < p.nslots; s += 64) alast = fmaxf(alast, p.sl_tau[qi * p.nslots + s]);
     alast = bgnn::group_max<64>(alast);
@@ -817,7 +873,7 @@ __global__ __launch_bounds__(256) void refine_kernel(Canon canon, const RefinePa
         hi = ge ? hi : mid;
       }
       const float ak = unord_f32(lo);                 // a lower bound of the k-th best approximate score
-      const float margin = p.nprod > 0 ? (float)(2.0 * eps) + 1e-7f : (float)(2.0 * (p.err_abs + p.err_rel * fabs((double)ak))) + 1e-7f;
+      const float margin = (float)(2.0 * eps) + 1e-7f;
       T = fmaxf(alast, ak - margin);
     }
     // (3) survivors above T: exact canonical scores
@@ -870,8 +926,7 @@ __global__ __launch_bounds__(256) void refine_kernel(Canon canon, const RefinePa
       kmax = other > kmax ? other : kmax;
     }
     const bool have = ns >= p.k;
-    const double bound = p.nprod > 0 ? eps : p.err_abs + p.err_rel * fabs((double)T);
-    const bool proven = have && ((T == -INFINITY) || kmax > (double)T + bound);
+    const bool proven = have && ((T == -INFINITY) || kmax > (double)T + eps);
     if (!proven && lane == 0) {
       const int slot = atomicAdd(p.fail_count, 1);
       p.fail_list[slot] = (int32_t)q;
@@ -1010,6 +1065,7 @@ struct TopkWs {
   uint32_t* mx;                                         // residual maxima [4]
   __bf16 *qh, *qm, *ch, *cm;
   double* scratch;
+  uint32_t* colmax; float* eps_q;                       // mlp: column maxima of |A| [MLP_H], error bound per query [Nq]
   int fb_blocks;
 };
 constexpr int FB_BLOCKS = 64;
@@ -1034,12 +1090,14 @@ static size_t topk_ws_layout(int64_t Nq, int64_t Nc, int k, int d, TopkWs* w, vo
   char* ch = take(sizeof(__bf16) * Nc * d);
   char* cm = take(sizeof(__bf16) * Nc * d);
   char* sc = take(sizeof(double) * FB_BLOCKS * Nc);
+  char* cx = take(sizeof(uint32_t) * MLP_H);
+  char* eq = take(sizeof(float) * Nq);
   if (w) {
     w->sl_score = (float*)a0; w->sl_idx = (int32_t*)a1; w->sl_tau = (float*)a2; w->tau_init = (float*)a3;
     w->sl2_score = (float*)b0; w->sl2_idx = (int32_t*)b1; w->sl2_tau = (float*)b2;
     w->fail1 = (int32_t*)f1; w->fail2 = (int32_t*)f2; w->counts = (int32_t*)cn; w->mx = (uint32_t*)mx;
     w->qh = (__bf16*)qh; w->qm = (__bf16*)qm; w->ch = (__bf16*)ch; w->cm = (__bf16*)cm;
-    w->scratch = (double*)sc; w->fb_blocks = FB_BLOCKS;
+    w->scratch = (double*)sc; w->colmax = (uint32_t*)cx; w->eps_q = (float*)eq; w->fb_blocks = FB_BLOCKS;
   }
   return total + 256;
 }
@@ -1193,7 +1251,7 @@ extern "C" int bgnn_cosine_topk_f32(const float* qn_query, const float* qn_cand,
     }
     p.Nc = NcB; p.cand_lo = NcA; p.slot_base = plA.nslots; p.tau_init = head_tiles ? w.tau_init : nullptr; p.carry_slots = plA.nslots; p.known_tiles = (int)head_tiles;
     if ((rc = pass1_any(d, fast_nprod, k, p, &plB, nullptr, st))) return rc;
-    RefineParams rp{Nq, nullptr, nullptr, k, nslots * kp, kp, nslots, w.sl_score, w.sl_idx, w.sl_tau, eps, fast_nprod, 0.0, 0.0,
+    RefineParams rp{Nq, nullptr, nullptr, k, nslots * kp, kp, nslots, w.sl_score, w.sl_idx, w.sl_tau, eps, fast_nprod, nullptr,
                     apply_sigmoid, idx_out, val_out, w.fail1, w.counts};
     if ((rc = launch_refine(canon, rp, st))) return rc;
   }
@@ -1205,7 +1263,7 @@ extern "C" int bgnn_cosine_topk_f32(const float* qn_query, const float* qn_cand,
                        (int64_t)MAX_SLOTS, w.counts);
     BGNN_LAUNCH_CHECK();
     if ((rc = pass1_any(d, 3, k, p, nullptr, nullptr, st))) return rc;
-    RefineParams rp{Nq, w.fail1, w.counts, k, MAX_SLOTS * kp2, kp2, MAX_SLOTS, w.sl2_score, w.sl2_idx, w.sl2_tau, eps, 3, 0.0, 0.0,
+    RefineParams rp{Nq, w.fail1, w.counts, k, MAX_SLOTS * kp2, kp2, MAX_SLOTS, w.sl2_score, w.sl2_idx, w.sl2_tau, eps, 3, nullptr,
                     apply_sigmoid, idx_out, val_out, w.fail2, w.counts + 1};
     if ((rc = launch_refine(canon, rp, st))) return rc;
   } else {
@@ -1233,16 +1291,22 @@ extern "C" int bgnn_mlp_pair_topk_f32(const float* A_cand, const float* B_query,
   if (H != MLP_H) return BGNN_E_SHAPE;   // Similar_v2 'mlp' hidden width is fixed at 128 (models.py:921)
   if (k <= 0 || k > 56 || k > Nc) return BGNN_E_RANGE;
   if (!bgnn_aligned16(A_cand) || !bgnn_aligned16(B_query)) return BGNN_E_ALIGN;
-  if (ws_bytes < topk_ws_layout(Nq < 1 ? 1 : Nq, Nc, k, 32, nullptr, nullptr)) return BGNN_E_WORKSPACE;
+  if (ws_bytes < bgnn_topk_workspace_bytes(Nq, Nc, k)) return BGNN_E_WORKSPACE;      // the declared figure, as bgnn.h states
   if (Nq == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   TopkWs w;
   topk_ws_layout(Nq, Nc, k, 32, &w, ws);
   hipError_t e;
   if ((e = bgnn_zero_async(w.counts, 256, st)) != hipSuccess) return (int)e;
-  // fp32 evaluation of a 128-term sum of O(1) terms: relative bound on the logit magnitude plus an absolute floor;
-  // generous (a loose bound only widens the shortlist / costs a few more exhaustive rows)
-  const float err_abs = 1e-4f, err_rel = 1e-4f;
+  // the proven bound eps_q of |fp32 pass-1 score - canonical score| for every query (derivation above mlp_colmax_kernel)
+  if ((e = bgnn_zero_async(w.colmax, sizeof(uint32_t) * MLP_H, st)) != hipSuccess) return (int)e;
+  {
+    const int64_t cg = (Nc + 7) / 8;
+    hipLaunchKernelGGL(mlp_colmax_kernel, dim3((unsigned)(cg < 1024 ? cg : 1024)), dim3(256), 0, st, A_cand, Nc, w.colmax);
+    BGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mlp_eps_kernel, dim3((unsigned)((Nq + 3) / 4)), dim3(256), 0, st, B_query, bn_scale, bn_shift, w2, b2, w.colmax, Nq, w.eps_q);
+    BGNN_LAUNCH_CHECK();
+  }
   const Geom g = geom_mlp(k);
   int rc;
   if ((rc = init_shortlists(w.sl_idx, Nq * (int64_t)g.kp, w.sl_tau, Nq, st))) return rc;
@@ -1254,20 +1318,20 @@ extern "C" int bgnn_mlp_pair_topk_f32(const float* A_cand, const float* B_query,
       const size_t sh = stage + MLP_WAVES * WaveTopK<64, 40>::BYTES;
       static int done[BGNN_MAX_DEVICES];
       if ((e = bgnn_set_max_dynamic_lds(reinterpret_cast<const void*>(kern), (int)sh, done)) != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, A_cand, B_query, bn_scale, bn_shift, w2, b2, Nq, Nc, (int)k, err_abs, err_rel,
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, A_cand, B_query, bn_scale, bn_shift, w2, b2, Nq, Nc, (int)k, w.eps_q,
                          w.sl_score, w.sl_idx, w.sl_tau);
     } else {
       auto kern = mlp_pass1_kernel<128, 112>;
       const size_t sh = stage + MLP_WAVES * WaveTopK<128, 112>::BYTES;
       static int done[BGNN_MAX_DEVICES];
       if ((e = bgnn_set_max_dynamic_lds(reinterpret_cast<const void*>(kern), (int)sh, done)) != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, A_cand, B_query, bn_scale, bn_shift, w2, b2, Nq, Nc, (int)k, err_abs, err_rel,
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sh, st, A_cand, B_query, bn_scale, bn_shift, w2, b2, Nq, Nc, (int)k, w.eps_q,
                          w.sl_score, w.sl_idx, w.sl_tau);
     }
     BGNN_LAUNCH_CHECK();
   }
   MlpCanon canon{A_cand, B_query, bn_scale, bn_shift, w2, b2, H};
-  RefineParams rp{Nq, nullptr, nullptr, k, g.kp, g.kp, 1, w.sl_score, w.sl_idx, w.sl_tau, EpsSrc{nullptr, 0}, 0, (double)err_abs, (double)err_rel,
+  RefineParams rp{Nq, nullptr, nullptr, k, g.kp, g.kp, 1, w.sl_score, w.sl_idx, w.sl_tau, EpsSrc{nullptr, 0}, 0, w.eps_q,
                   apply_sigmoid, idx_out, val_out, w.fail2, w.counts + 1};
   if ((rc = launch_refine(canon, rp, st))) return rc;
   hipLaunchKernelGGL((fallback_kernel<MlpCanon>), dim3(w.fb_blocks), dim3(256), 0, st, canon, Nc, k, apply_sigmoid,

@@ -652,7 +652,12 @@ int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att
  * candidate, keeping per query the candidates within 2 eps of the running k-th best; (2) the survivors are re-scored
  * in canonical arithmetic and the row is proven (kth_exact > best excluded approximate score + eps) or queued;
  * (3) queued rows go through a PRECISE pass (three piece products, eps ~ 5e-5) and the same proof; (4) rows that are
- * still unproven (exact ties across the boundary) are re-done exhaustively.  mlp: fp32 VALU pass + stages (2), (4).
+ * still unproven (exact ties across the boundary) are re-done exhaustively.  mlp: fp32 VALU pass + stages (2), (4), with a
+ * bound per QUERY proven from the call's own data: the fp32 chain (one add and two fmas per hidden unit) errs by at most
+ * (H + 2) 2^-24 S, S = |b2| + sum_h |w2_h| (|scale_h| |a_h + b_h| + |shift_h|) -- it follows the magnitude of the TERMS, not
+ * of the score, which may be small where they cancel -- and eps_q takes S over all candidates from the column maxima of |A|
+ * (one reduction per call) and the query's own |B| row, with (H + 4) 1.01 for the constant.  The shortlist margin, the refine
+ * stage and the proof read the same eps_q; terms that cancel to within eps_q send the row to stage (4), never to a wrong index.
  * n_fallback_opt (optional, int32[2] on the device): [0] = rows re-done exhaustively, [1] = rows sent to the precise pass.
  * val_out = sigmoid(score) as fp32 if apply_sigmoid (models.py:129,:953) else the fp32 score.
  * k <= 56.  q* must already be L2-normalised by bgnn_l2_normalize_rows_f32 (cosine).          */
