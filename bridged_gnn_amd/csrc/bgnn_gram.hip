@@ -765,7 +765,7 @@ extern "C" size_t bgnn_gram_workspace_bytes(int32_t p, int32_t q) {
 
 extern "C" int bgnn_gram_f32(const float* A, int64_t lda, int32_t p, const float* B, int64_t ldb, int32_t q, int64_t N,
                              float* out, void* ws, size_t ws_bytes, void* stream) {
-  if (!A || !B || !out || !ws) return BGNN_E_NULL;
+  if (((!A || !B) && N != 0) || !out || !ws) return BGNN_E_NULL;   // no rows: nothing is read (an empty tensor's pointer is NULL), out = 0
   if (N < 0 || p <= 0 || q <= 0 || p > 32 * GR_PA || q > 128 || (p & 3) || (q & 3) || lda < p || ldb < q || (lda & 3) || (ldb & 3))
     return BGNN_E_SHAPE;
   if (!bgnn_aligned16(A) || !bgnn_aligned16(B)) return BGNN_E_ALIGN;

@@ -142,7 +142,7 @@ int bgnn_narrow_transform_finish_f32(const float* raw, int64_t N, const uint8_t*
 /* bgnn_gram_f32: out[a][b] = sum_i A[i][a] * B[i][b] for tall-skinny A [N,p], B [N,q] (p <= 288, q <= 128, both % 4 == 0).
  *   The training path's weight / gate gradients of the dense transform (KTGNN.py:275-284 under autograd) are
  *   [G_s2t | G_t2s | dgate]^T . x with the node count as the reduction dimension; one streaming pass, deterministic
- *   two-stage sum.  ws: bgnn_gram_workspace_bytes(p, q). */
+ *   two-stage sum.  ws: bgnn_gram_workspace_bytes(p, q).  N = 0: out is all zeros, A and B are not read and may be NULL. */
 size_t bgnn_gram_workspace_bytes(int32_t p, int32_t q);
 int bgnn_gram_f32(const float* A, int64_t lda, int32_t p, const float* B, int64_t ldb, int32_t q, int64_t N,
                   float* out /*[p][q]*/, void* ws, size_t ws_bytes, void* stream);
