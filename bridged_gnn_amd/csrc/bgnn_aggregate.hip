@@ -14,6 +14,7 @@
 // Blocks are persistent over an XCD-contiguous range of row tiles so neighbouring destination
 // rows (which share in-neighbours in a bridged / kNN graph) hit the same XCD's L2.
 #include <cstdlib>
+#include <cstring>
 #include "bgnn_common.h"
 
 namespace {
@@ -40,7 +41,10 @@ struct AggParams {
   unsigned int* tile_queue;   // optional [8], zeroed per launch: per-XCD dynamic tile counters.  Static striding lets the
                      // blocks of an XCD drift apart (the set of rows in flight outgrows the 4 MB L2); pulling the next
                      // CHUNK of 4 tiles from a shared counter keeps them on neighbouring rows (HBM traffic 7.3 -> 2.4 GB;
-                     // one atomic per tile was itself the bound: same-address device atomics retire at ~11 M/s)
+                     // one atomic per tile on ONE counter per XCD was itself the bound: same-address device atomics retire at
+                     // ~11 M/s, a floor of 1.4 ms under C4's 125 k tiles on 8 counters.  agg_wide_fast_kernel's single-tile claims
+                     // spread them over NQ counters per XCD, a cache line each -- per address the rate chunks of NQ tiles have --
+                     // and need no block barrier around a claim: tq_subqueues below)
   double* colsum;    // optional [2*ldo + 2]: per-domain column sums (+ node counts) of the finished output rows, i.e. the
                      // domain sums the NEXT conv needs (KTGNN.py:275) without another pass over the activations
   int32_t heads;     // H convs evaluated together: tables/out are [N, H*ldh'] interleaved, a_* are [H][D]; a (row, head)
@@ -71,6 +75,10 @@ struct AggParams {
   uint32_t tbl_bytes, off_t2s, off_s2t;
   int32_t gather_hint; // 0 unknown, 1 neighbouring rows share neighbours (L2-resident gathers), 2 scattered (HBM-bound): resident blocks per CU
   uint32_t dead_off;   // row offset of a dead slot: lane base + dead_off is past the window and below 2^32, or 0 (row 0) when that does not fit
+  // agg_wide_fast_kernel's single-tile claims (filled by launch_wide_fast; tq_subqueues == 0: chunk claims, the fields above)
+  int64_t tq_words;    // uint32 words the caller's tile_queue holds (8: the contract of the entries older than ..._queued_f32)
+  int tq_subqueues;    // NQ counters per XCD, counter c hands out positions NQ * k + c of the XCD's sequence, one tile per claim
+  int tq_ahead;        // 1: the claim for tile n + 2 is in flight behind tile n's first step; 0: it is waited for where it is issued
 };
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
@@ -596,6 +604,7 @@ __global__ __launch_bounds__(256) void agg_wide_kernel(AggParams p) {
 //    attention coefficients, written exactly as agg_wide_kernel writes them);
 //  * the per-domain column sums take the row with weight 1 / 0 (packed FMAs) instead of two divergent branches.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+constexpr int TQ_SPACING_WORDS = 32;   // uint32 words between two claim counters of agg_wide_fast_kernel: a cache line each
 
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_movu(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true); }
@@ -619,10 +628,14 @@ __global__ __launch_bounds__(256) void agg_wide_fast_kernel(AggParams p) {
   const int32_t row0 = (int32_t)p.row_begin, row1 = (int32_t)p.row_end;
   const int32_t ntiles = (row1 - row0 + RPB - 1) / RPB;
   __shared__ float red[2][LF * 4 + 1];
-  if (p.colsum != nullptr) {
+  // single-tile claims (below): ring slot n % 4 = (n + 1) << 32 | counter value of the block's n-th tile; tiles taken per wave
+  __shared__ unsigned long long cl_ring[4];
+  __shared__ uint32_t cl_prog[4];
+  const bool tile_claims = p.tile_queue != nullptr && p.tq_subqueues > 0;             // kernel-uniform; else chunk claims / static stride
+  if (tile_claims && threadIdx.x < 4) { cl_ring[threadIdx.x] = 0ull; cl_prog[threadIdx.x] = 0u; }
+  if (p.colsum != nullptr)
     for (int t = threadIdx.x; t < 2 * (LF * 4 + 1); t += 256) (&red[0][0])[t] = 0.f;
-    __syncthreads();
-  }
+  if (p.colsum != nullptr || tile_claims) __syncthreads();
   __shared__ unsigned int dyn_tile;
   const uint32_t nstride = (uint32_t)(p.ldh * 4);
   const uint32_t ostride = (uint32_t)(p.ldo * 4);
@@ -655,8 +668,89 @@ __global__ __launch_bounds__(256) void agg_wide_fast_kernel(AggParams p) {
   const int32_t xend = NSEG > 1 ? xbase + NSEG * seg_len : min((xcd + 1) * per_x, ntiles);
   int32_t tile = xbase + slot - G;
   int32_t chunk_left = 0;
+  // Single-tile claims from striped sub-queues (NQ > 0).  Counter c = slot % NQ of the XCD hands out positions NQ * k + c, ONE tile
+  // per claim: the XCD's blocks sweep its sequence as one front however far they drift apart in time, where a chunk claim leaves
+  // each block on its own stripe of a super-chunk (a wider window of live rows in the L2).  NQ counters, a cache line each, keep
+  // the same-address atomic rate where chunks of NQ tiles have it.  No block barrier per tile -- the waves of a block run free, a
+  // wave's step count is the maximum over its rows --: the block's n-th claim goes through LDS ring slot n % 4.  Wave n % 4 owns
+  // it: it issues the atomic in front of the step loop of tile n - 2, without waiting (cl_issue), and publishes (tag << 32 | value,
+  // one 8-byte LDS write from one lane) behind that tile's first step, whose take_id waits for vmcnt(0) anyway: the round trip
+  // runs beside the first step's gathers (returns are in order, so that step's first use of a gather waits for the claim too).
+  // A tile without a step, a padded position and BGNN_AGG_CLAIM_AHEAD=0 wait for the claim where it is issued.  A wave that finds
+  // another tag polls.
+  // A slot is overwritten only when every wave has taken the tile it held (cl_prog), so the fastest wave leads the slowest by at
+  // most 4 tiles.  No cycle of waits: the wave that has taken the fewest tiles never waits -- the owner of its next tile has
+  // started the tile behind the one that publishes it, and its own publishes wait only for waves that took fewer tiles.
+  // The end: claims return in the order of their atomics, not of n -- the owner of tile n + 1 (issued in its tile n - 1) may be a
+  // tile behind the owner of n + 2.  So the first claim past the end, tile n, does not end the block: tile n + 1, issued before
+  // it may be, is still walked if it lies in front of the end.  Claim n + 2 would be issued behind tile n's return and therefore
+  // lie past the end as well: it is not made.  All waves see the same values and leave at the same n.
+  // Measured on C4 (profiles/agg_claim/README.md): fabric reads of the launch 3.63 -> 2.66 GB, TCC miss rate 0.320 -> 0.247, the launch
+  // 909.5 -> 884.6 us (2.7 %).  NQ = 2, 4, 8 and the claim waited for where it is issued (BGNN_AGG_CLAIM_AHEAD=0) are not told apart
+  // by runs that differ by +-10 us: one wave in four pays the round trip once per tile while the CU's other waves keep the gathers
+  // going.  Round 1's 1.4 ms floor under per-tile claims came from ONE counter per XCD and a block barrier around every claim;
+  // what the ring buys for certain is the absence of that barrier and a two-tile lead for the waves that do not own the claim.
+  // (a counter needs a block: an XCD with fewer than NQ blocks uses as many counters as it has blocks)
+  const int32_t NQ = tile_claims ? min((int32_t)p.tq_subqueues, G) : 0;
+  const int32_t wave_u = __builtin_amdgcn_readfirstlane(wave);
+  uint32_t* const qctr = NQ > 0 ? p.tile_queue + (xcd * NQ + slot % NQ) * TQ_SPACING_WORDS : nullptr;
+  const int32_t qpos0 = xbase + (NQ > 0 ? slot % NQ : 0);
+  uint32_t cl_n = 0;                             // tiles this wave has taken
+  uint32_t cl_val = 0;                           // lane 0 of the owner: the counter's value for tile cl_n + 1
+  bool cl_own = false, cl_pending = false;       // wave-uniform
+  bool cl_ending = false, cl_stop = false;       // a claim past the end has been seen; the tile behind it has been taken
+  // The claim itself, as INLINE ASSEMBLY like load_id's load: written as atomicAdd the compiler's atomic optimiser wraps it into
+  // mbcnt / readfirstlane logic and waits for vmcnt(0) right behind it -- a device-scope round trip in front of every step loop.
+  // Lane 0 alone issues it (exec is the whole wave here: the tile loop is block-uniform).  The compiler does not count it in its
+  // s_waitcnt vmcnt(n), so it waits for one access more than it needs, never less; the value is read behind an explicit wait only.
+  auto cl_issue = [&](uint32_t& v) {
+    uint64_t ex;
+    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add %0, %2, %3, %4 sc0\n\ts_mov_b64 exec, %1"
+                 : "+v"(v), "=&s"(ex) : "v"(0u), "v"(1u), "s"(qctr) : "memory");
+  };
+  auto cl_wait = [&](uint32_t& v) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(v) : : "memory"); };
+  auto cl_publish = [&](uint32_t tn, uint32_t v) {
+    while (tn >= 4u) {                           // every wave has taken tile tn - 4, whose slot this is
+      const uint32_t mn = min(min(__hip_atomic_load(&cl_prog[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP),
+                                  __hip_atomic_load(&cl_prog[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)),
+                              min(__hip_atomic_load(&cl_prog[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP),
+                                  __hip_atomic_load(&cl_prog[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)));
+      if ((uint32_t)__builtin_amdgcn_readfirstlane(mn) + 3u >= tn) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    if (lane == 0)
+      __hip_atomic_store(&cl_ring[tn & 3u], ((unsigned long long)(tn + 1u) << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+  if (NQ > 0 && wave_u < 2) {                    // tiles 0 and 1
+    uint32_t v = 0;
+    cl_issue(v);
+    cl_wait(v);
+    cl_publish((uint32_t)wave_u, v);
+  }
   for (;;) {
-    if (p.tile_queue != nullptr) {
+    if (NQ > 0) {
+      if (cl_stop) break;
+      uint32_t tag, kq;
+      for (;;) {
+        const unsigned long long w = __hip_atomic_load(&cl_ring[cl_n & 3u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        tag = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32));
+        kq = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w);
+        if (tag == cl_n + 1u) break;
+        __builtin_amdgcn_s_sleep(1);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      if (lane == 0) __hip_atomic_store(&cl_prog[wave], cl_n + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      tile = qpos0 + (int32_t)kq * NQ;
+      cl_stop = cl_ending;
+      cl_own = !cl_ending && ((cl_n + 2u) & 3u) == (uint32_t)wave_u;           // this wave claims tile cl_n + 2 while it walks tile cl_n
+      ++cl_n;
+      if (tile >= xend) {
+        if (cl_stop) break;
+        cl_ending = true;
+        continue;
+      }
+    } else if (p.tile_queue != nullptr) {
       if (chunk_left == 0) {                     // block-uniform
         __syncthreads();
         if (threadIdx.x == 0) dyn_tile = atomicAdd(&p.tile_queue[xcd], 1u);
@@ -683,7 +777,15 @@ __global__ __launch_bounds__(256) void agg_wide_fast_kernel(AggParams p) {
     if (NSEG > 1) {
       const int32_t j = tile - xbase, sg = j / seg_len;
       gt = (sg * 8 + xcd) * seg_len + (j - sg * seg_len);
-      if (gt >= ntiles) continue;                // padding of the last segments (block-uniform)
+      if (gt >= ntiles) {                        // padding of the last segments (block-uniform)
+        if (cl_own) {                            // (no step to hide the claim behind)
+          uint32_t v = 0;
+          cl_issue(v);
+          cl_wait(v);
+          cl_publish(cl_n + 1u, v);
+        }
+        continue;
+      }
     }
     const int32_t i0 = row0 + gt * RPB + wave * GPW + g;
     const bool rvalid = i0 < row1;
@@ -791,6 +893,13 @@ __global__ __launch_bounds__(256) void agg_wide_fast_kernel(AggParams p) {
     bool ok = e < end;
     uint32_t myoff = p.dead_off;           // byte offset of my slot's neighbour row inside its table
     if (nw > 0) myoff = row_off((uint32_t)p.col[max(min(e, end - 1), 0)], ok);
+    // (the row's own h is taken HERE: its wait, which the loop needs anyway, then stands in front of the claim and not behind it)
+    asm volatile("" : "+v"(h01), "+v"(h23) : : "memory");
+    if (cl_own) {                          // the claim for the tile after next (wave-uniform; see the scheduler's comment)
+      cl_issue(cl_val);
+      if (p.tq_ahead) cl_pending = true;
+      else { cl_wait(cl_val); cl_publish(cl_n + 1u, cl_val); }
+    }
     for (int32_t it = 0; it < nw; ++it) {
       float4 v[U];
       issue(v, myoff);
@@ -801,7 +910,18 @@ __global__ __launch_bounds__(256) void agg_wide_fast_kernel(AggParams p) {
       update(v, ok, e_cur);
       ok = ok2;
       take_id(nextid);
+      if (cl_pending) {                    // behind the first step's wait: the claim has returned
+        asm volatile("" : "+v"(cl_val) : : "memory");      // (read here, not where instruction selection likes: behind take_id's wait)
+        cl_publish(cl_n + 1u, cl_val);
+        cl_pending = false;
+        __builtin_amdgcn_sched_barrier(0);
+      }
       myoff = row_off(nextid, ok);
+    }
+    if (cl_pending) {                      // a tile without a step
+      cl_wait(cl_val);
+      cl_publish(cl_n + 1u, cl_val);
+      cl_pending = false;
     }
     s += bgnn::dpp_mov<0xB1>(s);
     s += bgnn::dpp_mov<0x4E>(s);
@@ -1098,6 +1218,24 @@ static bool fast_plan(AggParams& p, int64_t table_rows) {
   return true;
 }
 
+// How agg_wide_fast_kernel's blocks claim tiles from the queue (read once per process).  BGNN_AGG_CLAIM=chunk | tile: chunks of
+// BGNN_AGG_CHUNK tiles from one counter per XCD, or single tiles from BGNN_AGG_SUBQUEUES (1..8, default 4) striped counters per
+// XCD, a cache line (128 bytes; 256 and 512 measured the same time) apart, the claim in flight two tiles ahead unless BGNN_AGG_CLAIM_AHEAD=0.
+constexpr int kClaimTileDefault = 1;
+struct ClaimCfg { int tile, nq, ahead; };
+static const ClaimCfg& claim_cfg() {
+  static const ClaimCfg c = [] {
+    ClaimCfg r{kClaimTileDefault, 4, 1};
+    if (const char* e = getenv("BGNN_AGG_CLAIM")) r.tile = strcmp(e, "chunk") == 0 ? 0 : (strcmp(e, "tile") == 0 ? 1 : r.tile);
+    if (const char* e = getenv("BGNN_AGG_SUBQUEUES")) { const int v = atoi(e); if (v >= 1 && v <= 8) r.nq = v; }
+    if (const char* e = getenv("BGNN_AGG_CLAIM_AHEAD")) r.ahead = atoi(e) != 0;
+    return r;
+  }();
+  return c;
+}
+// uint32 words of queue a single-tile launch uses; a caller's queue that holds fewer gets chunk claims (8 words)
+static int64_t claim_queue_words() { return (int64_t)8 * claim_cfg().nq * TQ_SPACING_WORDS; }
+
 template <int LF, bool ALPHA>
 int launch_wide_fast(const AggParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / LF);
@@ -1131,6 +1269,10 @@ int launch_wide_fast(const AggParams& p, hipStream_t st) {
   q.tq_interleave = il;
   static const int nseg = [] { const char* e = getenv("BGNN_XCD_SEGMENTS"); return e ? atoi(e) : 8; }();
   q.xcd_segments = nseg;
+  const ClaimCfg& cc = claim_cfg();
+  const bool tile_claims = cc.tile && p.tile_queue != nullptr && p.tq_words >= claim_queue_words();
+  q.tq_subqueues = tile_claims ? cc.nq : 0;
+  q.tq_ahead = cc.ahead;
   hipLaunchKernelGGL((agg_wide_fast_kernel<LF, ALPHA>), dim3((unsigned)grid), dim3(256), 0, st, q);
   BGNN_LAUNCH_CHECK();
   return 0;
@@ -1321,8 +1463,10 @@ static int aggregate_impl(const float* h_t2s, const float* h_s2t, int64_t ldh,
                           float* out, int64_t ldo, float* alpha_opt,
                           const float* ep_scale_opt, const float* ep_shift_opt, int ep_relu,
                           float* state_ms_opt, int part, int64_t park_begin, int32_t heads,
-                          double* colsum_opt, uint32_t* tile_queue_opt, int64_t table_rows, int32_t gather_hint, void* stream) {
+                          double* colsum_opt, uint32_t* tile_queue_opt, int64_t tile_queue_words, int64_t table_rows, int32_t gather_hint,
+                          void* stream) {
   if (colsum_opt && heads != 1) return BGNN_E_SHAPE;
+  if (tile_queue_opt && tile_queue_words < 8) return BGNN_E_WORKSPACE;
   if (part == 1 && (park_begin < row_begin || park_begin > row_end)) return BGNN_E_SHAPE;
   if (part < 0 || part > 3 || (part != 0 && (!state_ms_opt || alpha_opt))) return BGNN_E_NULL;
   if (part == 3 && !((heads == 3 || heads == 2) && D <= 4 && ldh == 4 && ldo == 4)) return BGNN_E_SHAPE;
@@ -1340,9 +1484,11 @@ static int aggregate_impl(const float* h_t2s, const float* h_s2t, int64_t ldh,
               out, ldo, alpha_opt, ep_scale_opt, ep_shift_opt, ep_relu, tile_queue_opt, colsum_opt, heads, state_ms_opt, part,
               park_begin, 4};
   p.gather_hint = gather_hint;
+  p.tq_words = tile_queue_words;
   hipStream_t st = (hipStream_t)stream;
-  if (tile_queue_opt) {
-    hipError_t e = bgnn_zero_async(tile_queue_opt, 8 * sizeof(uint32_t), st);
+  if (tile_queue_opt) {     // the counters a launch may use: the striped ones (which cover the first 8 words) when the queue holds them
+    const int64_t zw = claim_cfg().tile && tile_queue_words >= claim_queue_words() ? claim_queue_words() : 8;
+    hipError_t e = bgnn_zero_async(tile_queue_opt, (size_t)zw * sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
   }
   return dispatch_aggregate(p, st, table_rows);
@@ -1357,7 +1503,7 @@ extern "C" int bgnn_adaptedconv_aggregate_f32(const float* h_t2s, const float* h
                                               float* state_ms_opt, int part, int64_t park_begin, int32_t heads,
                                               double* colsum_opt, uint32_t* tile_queue_opt, void* stream) {
   return aggregate_impl(h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, row_begin, row_end, D, negative_slope, out, ldo, alpha_opt,
-                        ep_scale_opt, ep_shift_opt, ep_relu, state_ms_opt, part, park_begin, heads, colsum_opt, tile_queue_opt, 0, 0, stream);
+                        ep_scale_opt, ep_shift_opt, ep_relu, state_ms_opt, part, park_begin, heads, colsum_opt, tile_queue_opt, 8, 0, 0, stream);
 }
 
 extern "C" int bgnn_adaptedconv_aggregate_bounded_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
@@ -1371,7 +1517,24 @@ extern "C" int bgnn_adaptedconv_aggregate_bounded_f32(const float* h_t2s, const 
                                                       void* stream) {
   if (table_rows < row_end || gather_hint < 0 || gather_hint > 2) return BGNN_E_SHAPE;
   return aggregate_impl(h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, row_begin, row_end, D, negative_slope, out, ldo, alpha_opt,
-                        ep_scale_opt, ep_shift_opt, ep_relu, state_ms_opt, part, park_begin, heads, colsum_opt, tile_queue_opt, table_rows, gather_hint, stream);
+                        ep_scale_opt, ep_shift_opt, ep_relu, state_ms_opt, part, park_begin, heads, colsum_opt, tile_queue_opt, 8, table_rows, gather_hint, stream);
+}
+
+extern "C" int64_t bgnn_aggregate_tile_queue_words(void) { return claim_cfg().tile ? claim_queue_words() : 8; }
+
+extern "C" int bgnn_adaptedconv_aggregate_queued_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
+                                                     const float* a_t2s, const float* a_s2t,
+                                                     const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                                     int64_t row_begin, int64_t row_end, int32_t D, float negative_slope,
+                                                     float* out, int64_t ldo, float* alpha_opt,
+                                                     const float* ep_scale_opt, const float* ep_shift_opt, int ep_relu,
+                                                     float* state_ms_opt, int part, int64_t park_begin, int32_t heads,
+                                                     double* colsum_opt, uint32_t* tile_queue_opt, int64_t tile_queue_words,
+                                                     int64_t table_rows, int32_t gather_hint, void* stream) {
+  if (table_rows < row_end || gather_hint < 0 || gather_hint > 2) return BGNN_E_SHAPE;
+  return aggregate_impl(h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, row_begin, row_end, D, negative_slope, out, ldo, alpha_opt,
+                        ep_scale_opt, ep_shift_opt, ep_relu, state_ms_opt, part, park_begin, heads, colsum_opt, tile_queue_opt,
+                        tile_queue_words, table_rows, gather_hint, stream);
 }
 
 extern "C" size_t bgnn_aggregate_hub_workspace_bytes(int64_t n_segments, int32_t heads, int64_t ldo) {

@@ -650,11 +650,19 @@ def adaptedconv_transform(x, mask_u8, delta, packed, out=None, sums=None, tail_s
 _P2_STATIC = os.environ.get("BGNN_P2_STATIC", "1") != "0"
 
 
+_TILE_QUEUE_WORDS = None
+
+
 def _tile_queue(dev):
-    """8 x uint32 scratch for the aggregation kernel's per-XCD dynamic tile counters (the C entry zeroes it on the stream per
-    launch, with a kernel of its own -- see bgnn_zero_async in csrc/bgnn_common.h).  A fresh allocation per call: the scratch has
-    no life outside its launch, so nothing created inside a HIP-graph capture has to stay valid between replays."""
-    return torch.empty(8, dtype=torch.int32, device=dev)
+    """uint32 scratch for the aggregation kernels' per-XCD dynamic tile counters: `bgnn_aggregate_tile_queue_words()` words, 8 for
+    chunk claims or 8 * NQ counters a cache line apart for the fast wide kernel's single-tile claims (the C entry zeroes what the
+    launch uses on the stream per launch, with one kernel of its own -- see bgnn_zero_async in csrc/bgnn_common.h).  A fresh
+    allocation per call: the scratch has no life outside its launch, so nothing created inside a HIP-graph capture has to stay
+    valid between replays."""
+    global _TILE_QUEUE_WORDS
+    if _TILE_QUEUE_WORDS is None:
+        _TILE_QUEUE_WORDS = max(8, int(L.lib().bgnn_aggregate_tile_queue_words()))
+    return torch.empty(_TILE_QUEUE_WORDS, dtype=torch.int32, device=dev)
 
 
 def heads_log_softmax_supported(heads, D):
@@ -714,14 +722,15 @@ def adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, negative_
             L.check(rc, "bgnn_adaptedconv_aggregate_hub_f32")
             return (out, alpha) if want_alpha else out
     # the tables' row count bounds every id in csr.col (a CSR over these tables): lets the plain wide launch use 32-bit addressing
-    rc = lib.bgnn_adaptedconv_aggregate_bounded_f32(
+    queue = tq if not (part == 2 and _P2_STATIC) else None
+    rc = lib.bgnn_adaptedconv_aggregate_queued_f32(
         L.ptr_rows(h_t2s), L.ptr_rows(h_s2t), ldh, L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col),
         L.ptr(mask_u8), int(row_begin), row_end, D, float(negative_slope), L.ptr_rows(out), out.stride(0) // heads, L.ptr(alpha),
         L.ptr(ep_scale), L.ptr(ep_shift), 2 if log_softmax else (1 if ep_relu else 0), L.ptr(state_ms), int(part),
         int(row_begin) if park_begin is None else int(park_begin), int(heads), L.ptr(colsum),
-        L.ptr(tq) if not (part == 2 and _P2_STATIC) else None, min(int(h_t2s.shape[0]), int(h_s2t.shape[0])),
+        L.ptr(queue), 0 if queue is None else int(queue.numel()), min(int(h_t2s.shape[0]), int(h_s2t.shape[0])),
         csr.gather_hint() if (heads == 1 and D > 32 and part == 0) else 0, L.stream())
-    L.check(rc, "bgnn_adaptedconv_aggregate_bounded_f32")
+    L.check(rc, "bgnn_adaptedconv_aggregate_queued_f32")
     return (out, alpha) if want_alpha else out
 
 

@@ -36,7 +36,8 @@ extern "C" {
  * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for partitioned GCN's
  * bgnn_gcn_aggregate_rows_f32, and for the GAT baseline's bgnn_gat_scores_f32, bgnn_gat_aggregate_f32, bgnn_gat_aggregate_bwd_f32 and
  * their workspace size (added after 114 without changing it), and for the GATv2 baseline's bgnn_gatv2_aggregate_f32,
- * bgnn_gatv2_aggregate_bwd_f32 and their workspace size (likewise).
+ * bgnn_gatv2_aggregate_bwd_f32 and their workspace size (likewise), and for bgnn_adaptedconv_aggregate_queued_f32 with
+ * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
  * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone. */
@@ -331,6 +332,25 @@ int bgnn_adaptedconv_aggregate_bounded_f32(const float* h_t2s, const float* h_s2
                                            const float* ep_scale_opt, const float* ep_shift_opt, int ep_relu,
                                            float* state_ms_opt, int part, int64_t park_begin, int32_t heads, double* colsum_opt,
                                            uint32_t* tile_queue_opt, int64_t table_rows, int32_t gather_hint, void* stream);
+
+/* bgnn_adaptedconv_aggregate_bounded_f32 with a tile queue of a stated size: tile_queue_opt holds tile_queue_words uint32 (>= 8, else
+ * BGNN_E_WORKSPACE; zeroed here on `stream`, as far as the launch uses it).  With bgnn_aggregate_tile_queue_words() words or more the
+ * plain wide launch (agg_wide_fast_kernel) claims SINGLE tiles from striped counters, 8 * NQ of them a cache line apart,
+ * instead of chunks of four from the 8 counters every other kernel and entry uses; a smaller queue gets those chunk claims, and no
+ * entry writes past the words it was given.  Results are bit-identical either way (column sums: fp32 partials in claim order).
+ * Environment (read once): BGNN_AGG_CLAIM=chunk | tile, BGNN_AGG_SUBQUEUES = NQ (1..8, default 4),
+ * BGNN_AGG_CLAIM_AHEAD=0 (the claim waited for where it is issued); bgnn_aggregate_tile_queue_words() follows them (8 under BGNN_AGG_CLAIM=chunk).  An additive pair:
+ * bgnn_adaptedconv_aggregate_f32, _bounded_f32 and _hub_f32 keep their 8-word contract and their schedule. */
+int64_t bgnn_aggregate_tile_queue_words(void);
+int bgnn_adaptedconv_aggregate_queued_f32(const float* h_t2s, const float* h_s2t, int64_t ldh,
+                                          const float* a_t2s, const float* a_s2t,
+                                          const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                          int64_t row_begin, int64_t row_end, int32_t D, float negative_slope,
+                                          float* out, int64_t ldo, float* alpha_opt,
+                                          const float* ep_scale_opt, const float* ep_shift_opt, int ep_relu,
+                                          float* state_ms_opt, int part, int64_t park_begin, int32_t heads, double* colsum_opt,
+                                          uint32_t* tile_queue_opt, int64_t tile_queue_words, int64_t table_rows, int32_t gather_hint,
+                                          void* stream);
 
 /* The same aggregation for graphs with HUB rows.  A destination row is walked by one lane group, so a row with hundreds of
  * in-edges (the 581 source nodes of the Twitter_Graph stand-in have ~750) is a chain of dependent gather steps that outlives
