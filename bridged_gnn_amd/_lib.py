@@ -24,14 +24,8 @@ SIGNATURES = {
     "bgnn_domain_sums_workspace_bytes": (_SZ, [_I32]),
     "bgnn_domain_sums_ws_f64": (_INT, [_P, _I64, _I32, _I64, _P, _P, _P, _SZ, _P]),
     "bgnn_domain_delta_f32": (_INT, [_P, _I32, _P, _P]),
-    "bgnn_adaptedconv_transform_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P,
-                                               _P, _P, _P, _P, _I64, _I64, _P, _P]),
-    "bgnn_adaptedconv_transform_sums_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P,
-                                                    _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
-    "bgnn_adaptedconv_transform_need_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P,
-                                                    _P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
-    "bgnn_adaptedconv_transform_need2_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P,
-                                                     _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]),
+    "bgnn_adaptedconv_transform_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P, _P,
+                                               _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]),
     "bgnn_classifier_stage_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
                                           _P, _P, _I32, _INT, _P, _P, _P, _P, _P, _P]),
     "bgnn_linear_narrow_transform_f32": (_INT, [_P, _I64, _I32, _I64, _P, _P, _I32, _INT, _P, _P, _P, _P, _P, _P]),
@@ -170,7 +164,7 @@ def _sidecar_hash():
 
 
 # the ABI revision this binding was written for (include/bgnn.h: BGNN_VERSION); checked against the loaded library
-ABI_VERSION = 114
+ABI_VERSION = 115
 
 
 def _make():

@@ -931,18 +931,54 @@ extern "C" int bgnn_domain_delta_f32(const double* sums, int32_t Din, float* del
   return 0;
 }
 
-static int transform_impl(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                          const uint8_t* mask, const float* delta, const double* sums,
-                          int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                          const float* gates, const float* gate_const_opt,
-                          float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                          int64_t ldh, int64_t row_stride, float* small_ws, void* stream,
-                          int64_t n_tail_t2s = 0, int64_t n_tail_s2t = 0, const int32_t* tile_need = nullptr,
-                          const int64_t* team_runs_host = nullptr, int32_t n_team_runs = 0) {
-  if (n_team_runs < 0 || n_team_runs > 2 || (n_team_runs > 0 && !team_runs_host)) return BGNN_E_SHAPE;
-  if (tile_need && (n_tail_t2s || n_tail_s2t)) return BGNN_E_SHAPE;
+// CU count of the current device (read once; 256 if the query fails)
+static int n_cu() {
+  static const int n = [] {
+    int dev = 0; hipDeviceProp_t prop;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+  }();
+  return n;
+}
+
+// The one launch of transform_wreg_kernel<.., MODE> (0: AdaptedConv transform, 1: plain Linear, 2: Linear -> narrow stage A).
+// The caller has checked its envelope: NC % 64 == 0 and Din <= 128 (128 weight registers per lane at Din = 256 would spill).
+// Persistent blocks, column groups of 32 * NCT in grid.y (full groups only).  NC % 128 != 0: 4-wave blocks (2 column tiles x 2 row
+// sub-tiles), two per CU; wider: 8-wave blocks, one per CU.  Products are bf16 x 3 from NCT = 4 on, fp32 MFMA at NCT = 2.
+template <int MODE, int DK, int NCT, int NW>
+static void launch_wreg_tile(const GemmParams& p, hipStream_t st) {
+  constexpr int BMW = 32 * (NW / NCT);
+  const int64_t ntiles = (p.N + BMW - 1) / BMW;
+  const int64_t gx = (int64_t)n_cu() * (NW == 4 ? 2 : 1);
+  const dim3 grid((unsigned)(ntiles < gx ? ntiles : gx), (unsigned)(p.NC / (32 * NCT)));
+  hipLaunchKernelGGL((transform_wreg_kernel<DK, NCT, NW, (NCT >= 4), MODE>), grid, dim3(64 * NW), 0, st, p);
+}
+template <int MODE, int NCT, int NW>
+static void launch_wreg_dk(const GemmParams& p, hipStream_t st) {
+  if (p.Din <= 64) launch_wreg_tile<MODE, 64, NCT, NW>(p, st); else launch_wreg_tile<MODE, 128, NCT, NW>(p, st);
+}
+template <int MODE>
+static int launch_wreg(const GemmParams& p, hipStream_t st) {
+  if (p.NC % 256 == 0) launch_wreg_dk<MODE, 8, 8>(p, st);
+  else if (p.NC % 128 == 0) launch_wreg_dk<MODE, 4, 8>(p, st);
+  else launch_wreg_dk<MODE, 2, 4>(p, st);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int bgnn_adaptedconv_transform_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
+                                              const uint8_t* mask, const float* delta_opt, const double* sums_opt,
+                                              int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
+                                              const float* gates, const float* gate_const_opt,
+                                              float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
+                                              int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
+                                              const int32_t* tile_need_opt, const int64_t* team_runs_host_opt, int32_t n_team_runs,
+                                              float* small_ws, void* stream) {
+  if ((delta_opt != nullptr) == (sums_opt != nullptr)) return BGNN_E_NULL;      // exactly one form
+  if (delta_opt && !bgnn_aligned16(delta_opt)) return BGNN_E_ALIGN;
+  if (n_team_runs < 0 || n_team_runs > 2 || (n_team_runs > 0 && !team_runs_host_opt)) return BGNN_E_SHAPE;
+  if (tile_need_opt && (n_tail_t2s || n_tail_s2t)) return BGNN_E_SHAPE;
   if (n_tail_t2s < 0 || n_tail_s2t < 0 || n_tail_t2s + n_tail_s2t > N) return BGNN_E_SHAPE;
-  if (!x || !mask || (!delta && !sums) || !Wp || !bias_p || !gates || !h_s2t_0 || !h_t2s_0 || !small_ws) return BGNN_E_NULL;
+  if (!x || !mask || !Wp || !bias_p || !gates || !h_s2t_0 || !h_t2s_0 || !small_ws) return BGNN_E_NULL;
   if (n_heads < 1 || n_heads > MAXH || (n_heads == 2 && (!h_s2t_1 || !h_t2s_1))) return BGNN_E_NULL;
   if (N < 0 || Din <= 0 || D <= 0 || ldx < Din || ldh < D) return BGNN_E_SHAPE;
   if ((Din & 3) || (ldx & 3) || (ldh & 3) || (row_stride & 3) || row_stride < ldh) return BGNN_E_SHAPE;
@@ -952,7 +988,7 @@ static int transform_impl(const float* x, int64_t N, int32_t Din, int64_t ldx,
   const int NC = n_heads * 2 * (int)ldh;
   float* wd = small_ws;            // [NC]
   float* gc = small_ws + NC;       // [n_heads*2]
-  hipLaunchKernelGGL(wd_kernel, dim3((unsigned)((NC + 2 * n_heads + 3) / 4)), dim3(256), 0, st, Wp, NC, Din, delta, sums, gates,
+  hipLaunchKernelGGL(wd_kernel, dim3((unsigned)((NC + 2 * n_heads + 3) / 4)), dim3(256), 0, st, Wp, NC, Din, delta_opt, sums_opt, gates,
                      gate_const_opt, n_heads, wd, gc);
   BGNN_LAUNCH_CHECK();
   GemmParams p{};
@@ -961,48 +997,28 @@ static int transform_impl(const float* x, int64_t N, int32_t Din, int64_t ldx,
   p.ldh = ldh; p.row_stride = row_stride; p.NC = NC; p.n_heads = n_heads; p.relu = 0; p.colsum = nullptr; p.col_off = 0;
   const int64_t nrt = (N + BM - 1) / BM;
   const int64_t nrt8 = (nrt + 7) / 8 * 8;        // row tiles rounded up to the XCD group size
-  static const int n_cu = [] {
-    int dev = 0; hipDeviceProp_t prop;
-    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }();
-  static const bool use_wreg = [] { const char* e = getenv("BGNN_GEMM_WREG"); return !e || atoi(e) != 0; }();
+  const bool wreg = NC % 64 == 0 && Din <= 128;  // the W-stationary kernel's envelope
   // Tail rows that need ONE table (the resident input halo of a partitioned graph: a halo row feeds destinations of one
   // domain): the W-stationary kernel lets the other table's waves sit those row tiles out (GemmParams::tail_*).  Outside
   // its envelope the tail rows simply get both tables like every other row.
   p.tail_t2s_begin = 0; p.tail_s2t_begin = 0;
-  if ((n_tail_t2s || n_tail_s2t) && use_wreg && n_heads == 1 && NC % 64 == 0 && Din <= 128) {
+  if ((n_tail_t2s || n_tail_s2t) && n_heads == 1 && wreg) {
     p.tail_t2s_begin = N - n_tail_t2s - n_tail_s2t;
     p.tail_s2t_begin = N - n_tail_s2t;
     if (p.tail_s2t_begin == 0) p.tail_s2t_begin = 1, p.tail_t2s_begin = p.tail_t2s_begin > 1 ? 1 : p.tail_t2s_begin;   // (rows from 0: keep the "tails on" encoding; a tile never ends at row 0)
   }
   // barrier-free producer / consumer pipeline (bgnn_transform_stream.hip): one head, 128 or 256 packed columns, 64 < Din <= 128
   static const bool use_stream = [] { const char* e = getenv("BGNN_GEMM_STREAM"); return !e || atoi(e) != 0; }();
-  p.tile_need = tile_need;                       // (honoured by the stream kernel only; the others write both tables everywhere)
+  p.tile_need = tile_need_opt;                   // (honoured by the stream kernel only; the others write both tables everywhere)
   for (int r = 0; r < n_team_runs; ++r) {        // (the stream launcher admits or empties each run)
-    p.team_begin[r] = team_runs_host[3 * r]; p.team_end[r] = team_runs_host[3 * r + 1]; p.team_table[r] = (int32_t)team_runs_host[3 * r + 2];
+    p.team_begin[r] = team_runs_host_opt[3 * r]; p.team_end[r] = team_runs_host_opt[3 * r + 1]; p.team_table[r] = (int32_t)team_runs_host_opt[3 * r + 2];
   }
-  if (use_stream && bgnn_tf_stream_supported(p, 0)) return bgnn_tf_stream_launch(p, 0, st, n_cu);
-  if (use_wreg && NC % 64 == 0 && Din <= 128) {   // (Din = 256 needs 128 weight registers per lane and spills)
-    // W-stationary persistent kernel: one 512-thread block per CU, column groups of 32*NCT in grid.y
-    // NC <= 64: 4-wave blocks (2 column tiles x 2 row sub-tiles), two per CU; wider: 8-wave blocks, one per CU
-    const int nct = NC % 256 == 0 ? 8 : NC % 128 == 0 ? 4 : 2;   // full column groups only
-    const int nw = nct == 2 ? 4 : 8;
-    const int bmw = 32 * (nw / nct);
-    const int64_t ntiles = (N + bmw - 1) / bmw;
-    const int ncg = (NC + 32 * nct - 1) / (32 * nct);
-    const int64_t gx = (int64_t)n_cu * (nw == 4 ? 2 : 1);
-    const dim3 grid((unsigned)(ntiles < gx ? ntiles : gx), (unsigned)ncg);
-    static const bool bf3 = [] { const char* e = getenv("BGNN_GEMM_BF3"); return !e || atoi(e) != 0; }();
-#define BGNN_WREG(DK, NCT, NW) do { if (bf3 && NCT >= 4) hipLaunchKernelGGL((transform_wreg_kernel<DK, NCT, NW, true, 0>), grid, dim3(64 * NW), 0, st, p); \
-                                     else hipLaunchKernelGGL((transform_wreg_kernel<DK, NCT, NW, false, 0>), grid, dim3(64 * NW), 0, st, p); } while (0)
-#define BGNN_WREG_DK(NCT, NW) do { if (Din <= 64) BGNN_WREG(64, NCT, NW); else BGNN_WREG(128, NCT, NW); } while (0)
-    if (nct == 2) BGNN_WREG_DK(2, 4); else if (nct == 4) BGNN_WREG_DK(4, 8); else BGNN_WREG_DK(8, 8);
-#undef BGNN_WREG_DK
-#undef BGNN_WREG
-  } else if (use_wreg && NC <= 24 && Din <= 128) {
+  if (use_stream && bgnn_tf_stream_supported(p)) return bgnn_tf_stream_launch(p, st, n_cu());
+  if (wreg) return launch_wreg<0>(p, st);
+  if (NC <= 24 && Din <= 128) {
     // wave-autonomous stream: two 4-wave blocks per CU, each wave strides over 32-row tiles
     const int64_t nt = (N + 31) / 32, nb = (nt + 3) / 4;
-    const unsigned grid = (unsigned)(nb < 2 * n_cu ? nb : 2 * n_cu);
+    const unsigned grid = (unsigned)(nb < 2 * n_cu() ? nb : 2 * n_cu());
     if (Din <= 64) hipLaunchKernelGGL((transform_skinny_kernel<64>), dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((transform_skinny_kernel<128>), dim3(grid), dim3(256), 0, st, p);
   } else if (NC <= 32) {
@@ -1017,56 +1033,6 @@ static int transform_impl(const float* x, int64_t N, int32_t Din, int64_t ldx,
   return 0;
 }
 
-extern "C" int bgnn_adaptedconv_transform_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                              const uint8_t* mask, const float* delta,
-                                              int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                              const float* gates, const float* gate_const_opt,
-                                              float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                              int64_t ldh, int64_t row_stride, float* small_ws, void* stream) {
-  if (!delta) return BGNN_E_NULL;
-  if (!bgnn_aligned16(delta)) return BGNN_E_ALIGN;
-  return transform_impl(x, N, Din, ldx, mask, delta, nullptr, n_heads, D, Wp, bias_p, gates, gate_const_opt,
-                        h_s2t_0, h_t2s_0, h_s2t_1, h_t2s_1, ldh, row_stride, small_ws, stream);
-}
-
-extern "C" int bgnn_adaptedconv_transform_sums_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                                   const uint8_t* mask, const double* sums,
-                                                   int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                                   const float* gates, const float* gate_const_opt,
-                                                   float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                                   int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
-                                                   float* small_ws, void* stream) {
-  if (!sums) return BGNN_E_NULL;
-  return transform_impl(x, N, Din, ldx, mask, nullptr, sums, n_heads, D, Wp, bias_p, gates, gate_const_opt,
-                        h_s2t_0, h_t2s_0, h_s2t_1, h_t2s_1, ldh, row_stride, small_ws, stream, n_tail_t2s, n_tail_s2t);
-}
-
-extern "C" int bgnn_adaptedconv_transform_need_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                                   const uint8_t* mask, const double* sums,
-                                                   int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                                   const float* gates, const float* gate_const_opt,
-                                                   float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                                   int64_t ldh, int64_t row_stride, const int32_t* tile_need_opt,
-                                                   float* small_ws, void* stream) {
-  if (!sums) return BGNN_E_NULL;
-  return transform_impl(x, N, Din, ldx, mask, nullptr, sums, n_heads, D, Wp, bias_p, gates, gate_const_opt,
-                        h_s2t_0, h_t2s_0, h_s2t_1, h_t2s_1, ldh, row_stride, small_ws, stream, 0, 0, tile_need_opt);
-}
-
-extern "C" int bgnn_adaptedconv_transform_need2_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                                    const uint8_t* mask, const double* sums,
-                                                    int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                                    const float* gates, const float* gate_const_opt,
-                                                    float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                                    int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
-                                                    const int32_t* tile_need_opt, const int64_t* team_runs_host_opt, int32_t n_team_runs,
-                                                    float* small_ws, void* stream) {
-  if (!sums) return BGNN_E_NULL;
-  return transform_impl(x, N, Din, ldx, mask, nullptr, sums, n_heads, D, Wp, bias_p, gates, gate_const_opt,
-                        h_s2t_0, h_t2s_0, h_s2t_1, h_t2s_1, ldh, row_stride, small_ws, stream, n_tail_t2s, n_tail_s2t, tile_need_opt,
-                        team_runs_host_opt, n_team_runs);
-}
-
 extern "C" int bgnn_linear_f32(const float* x, int64_t N, int32_t Din, int64_t ldx, const float* W, const float* bias,
                                int32_t Dout, int relu, const uint8_t* mask_opt, double* colsum_opt,
                                float* out, int64_t ldo, void* stream) {
@@ -1076,29 +1042,12 @@ extern "C" int bgnn_linear_f32(const float* x, int64_t N, int32_t Din, int64_t l
     return BGNN_E_SHAPE;
   if (!bgnn_aligned16(x) || !bgnn_aligned16(W) || !bgnn_aligned16(bias) || !bgnn_aligned16(out)) return BGNN_E_ALIGN;
   if (N == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
   GemmParams p{};
   p.x = x; p.ldx = ldx; p.N = N; p.Din = Din; p.mask = mask_opt; p.Wp = W; p.bias = bias; p.wd = nullptr; p.g = nullptr; p.gc = nullptr;
   p.out[0][0] = out; p.out[0][1] = out; p.out[1][0] = out; p.out[1][1] = out;
   p.ldh = Dout;            // one "table" spanning all columns: column c -> (h, t) = (0, 0), offset c
   p.row_stride = ldo; p.NC = Dout; p.n_heads = 1; p.relu = relu; p.colsum = colsum_opt;
-  static const int n_cu = [] {
-    int dev = 0; hipDeviceProp_t prop;
-    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }();
-  const int nct = Dout % 256 == 0 ? 8 : Dout % 128 == 0 ? 4 : 2;
-  const int nw = nct == 2 ? 4 : 8;
-  const int bmw = 32 * (nw / nct);
-  const int64_t ntiles = (N + bmw - 1) / bmw;
-  const int64_t gx = (int64_t)n_cu * (nw == 4 ? 2 : 1);
-  const dim3 grid((unsigned)(ntiles < gx ? ntiles : gx), (unsigned)(Dout / (32 * nct)));
-#define BGNN_LIN(DK, NCT, NW, BF) hipLaunchKernelGGL((transform_wreg_kernel<DK, NCT, NW, BF, 1>), grid, dim3(64 * NW), 0, st, p)
-#define BGNN_LIN_DK(NCT, NW, BF) do { if (Din <= 64) BGNN_LIN(64, NCT, NW, BF); else BGNN_LIN(128, NCT, NW, BF); } while (0)
-  if (nct == 2) BGNN_LIN_DK(2, 4, false); else if (nct == 4) BGNN_LIN_DK(4, 8, true); else BGNN_LIN_DK(8, 8, true);
-#undef BGNN_LIN_DK
-#undef BGNN_LIN
-  BGNN_LAUNCH_CHECK();
-  return 0;
+  return launch_wreg<1>(p, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ linear -> narrow AdaptedConv transform, fused
@@ -1145,34 +1094,11 @@ extern "C" int bgnn_linear_narrow_transform_f32(const float* x, int64_t N, int32
     return BGNN_E_SHAPE;
   if (!bgnn_aligned16(x) || !bgnn_aligned16(W) || !bgnn_aligned16(bias) || !bgnn_aligned16(raw)) return BGNN_E_ALIGN;
   if (N == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
   GemmParams p{};
   p.x = x; p.ldx = ldx; p.N = N; p.Din = Din; p.mask = mask; p.Wp = W; p.bias = bias;
   p.ldh = Dout; p.row_stride = Dout; p.NC = Dout; p.n_heads = 1; p.relu = relu ? 1 : 0; p.colsum = colsum;
   p.w2 = Wp2; p.g2 = gates2; p.raw = raw;
-  static const int n_cu = [] {
-    int dev = 0; hipDeviceProp_t prop;
-    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }();
-  // The barrier-free pipeline's form of this launch (transform_stream2_kernel) is OPT-IN (BGNN_GEMM_STREAM2=1): measured
-  // 0.270 ms against this kernel's 0.254-0.276 ms on C4 -- its waves spend the time the block kernel spends at barriers waiting
-  // at the ring's counters instead (profiles/r03/README.md); same results, kept for the next round's work on the tail behind
-  // the first-stage MFMAs.
-  static const bool use_stream2 = [] { const char* e = getenv("BGNN_GEMM_STREAM2"); return e && atoi(e) != 0; }();
-  if (use_stream2 && bgnn_tf_stream_supported(p, 2)) return bgnn_tf_stream_launch(p, 2, st, n_cu);
-  const int nct = Dout == 256 ? 8 : Dout == 128 ? 4 : 2;
-  const int nw = nct == 2 ? 4 : 8;
-  const int bmw = 32 * (nw / nct);
-  const int64_t ntiles = (N + bmw - 1) / bmw;
-  const int64_t gx = (int64_t)n_cu * (nw == 4 ? 2 : 1);
-  const dim3 grid((unsigned)(ntiles < gx ? ntiles : gx), 1u);
-#define BGNN_LIN2(DK, NCT, NW, BF) hipLaunchKernelGGL((transform_wreg_kernel<DK, NCT, NW, BF, 2>), grid, dim3(64 * NW), 0, st, p)
-#define BGNN_LIN2_DK(NCT, NW, BF) do { if (Din <= 64) BGNN_LIN2(64, NCT, NW, BF); else BGNN_LIN2(128, NCT, NW, BF); } while (0)
-  if (nct == 2) BGNN_LIN2_DK(2, 4, false); else if (nct == 4) BGNN_LIN2_DK(4, 8, true); else BGNN_LIN2_DK(8, 8, true);
-#undef BGNN_LIN2_DK
-#undef BGNN_LIN2
-  BGNN_LAUNCH_CHECK();
-  return 0;
+  return launch_wreg<2>(p, (hipStream_t)stream);      // (gridDim.y == 1: NC is one column group)
 }
 
 extern "C" int bgnn_classifier_stage_f32(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
@@ -1205,11 +1131,7 @@ extern "C" int bgnn_classifier_stage_f32(const float* x, int64_t N, int32_t Din,
   hipLaunchKernelGGL(wd_kernel, dim3((unsigned)((sk_NC + 2 * sk_heads + 3) / 4)), dim3(256), 0, st, sk_Wp, sk_NC, Din, (const float*)nullptr,
                      sums_x, sk_gates, sk_gate_const_opt, sk_heads, wd, gc);
   BGNN_LAUNCH_CHECK();
-  static const int n_cu = [] {
-    int dev = 0; hipDeviceProp_t prop;
-    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }();
-  return bgnn_tf_cls_launch(p, st, n_cu);
+  return bgnn_tf_cls_launch(p, st, n_cu());
 }
 
 extern "C" int bgnn_narrow_transform_finish_f32(const float* raw, int64_t N, const uint8_t* mask, const double* sums,

@@ -26,7 +26,7 @@
 // A first version with dedicated producer waves (4 stagers + 8 consumers) ran 0.36 ms: one wave executes a tile's ~1200 staging
 // instructions at ~13 cycles each, which bounded the launch.
 //
-// Team mode (MODE 0, 8 consumer waves; GemmParams::team_*).  Waves 0..3 own the 128 columns of h_s2t, waves 4..7 those of h_t2s.  A tile
+// Team mode (8 consumer waves; GemmParams::team_*).  Waves 0..3 own the 128 columns of h_s2t, waves 4..7 those of h_t2s.  A tile
 // that needs one table only (tile_need, tail_*) is sat out by the other table's four waves: they stage their rows and wait, and since
 // the ring couples all waves to the slowest, half of the CU idles through such a tile.  Where such tiles come in a long run (C4 with
 // [sources ; targets] order and s -> t bridges: every target tile needs h_s2t only) the host passes the run, and a block that enters
@@ -74,13 +74,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define TS_DEPTH 2        // loads are requested this many tiles in front of staging
 #endif
 constexpr int TS_TARGET_EXP = 10;   // a row's / column's largest magnitude is scaled into [2^10, 2^11)
-
-// raw buffer descriptor (gfx9 dword 3 = 0x00020000: 32-bit data format, no swizzle); `bytes` <= 0: every access is out of range
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int64_t bytes) {
-  const int64_t cap = 0x7fffffff;
-  const int nrec = (int)(bytes < 0 ? 0 : (bytes > cap ? cap : bytes));
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, nrec, 0x00020000);
-}
 
 // ---- LDS ring ---------------------------------------------------------------------------------------------------------
 // slot = [hi: 32 rows x DK fp16][lo: same][coef0[32] | coef1[32] | inv_scale[32] | domain[32]] ; DK = 128: 16.5 KB
@@ -145,10 +138,10 @@ __device__ __forceinline__ void split4(const float4 v, const float sc, h4& hi, h
   }
 }
 
-// MODE 0: AdaptedConv transform (one head: NC = 2 * ldh).
+// AdaptedConv transform (one head: NC = 2 * ldh).
 // NW waves stage; waves < NCW also own a 32-column tile (NC = 32 * NCW).  SLOTS ring slots, staging runs AHEAD tiles in front of
 // consumption, loads DEPTH tiles in front of staging.
-template <int DK, int NW, int NCW, int SLOTS, int AHEAD, int DEPTH, int MODE>
+template <int DK, int NW, int NCW, int SLOTS, int AHEAD, int DEPTH>
 __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p) {
   using SL = Slot<DK>;
   static_assert(AHEAD >= 1 && AHEAD < SLOTS && NCW <= NW && 32 % (4 * NW) == 0, "pipeline shape");
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   constexpr int RPW = 32 / NW;               // rows a wave stages per tile
   __shared__ __attribute__((aligned(16))) unsigned char ring[SLOTS * SL::BYTES];
   __shared__ uint32_t ready[SLOTS], done[SLOTS];
-  __shared__ __attribute__((aligned(16))) float gtab[MODE == 0 ? 2 * DK : 4];
+  __shared__ __attribute__((aligned(16))) float gtab[2 * DK];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < SLOTS) { ready[tid] = 0u; done[tid] = 0u; }
@@ -178,14 +171,11 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   const int l16 = lane & 15, rsub = lane >> 4;
   // gate vectors as (g_s2t[k], g_t2s[k]) pairs in LDS: a lane reads the pairs of its fixed k chunks when it stages (16 VGPRs
   // if kept in registers -- the fused iteration has none to spare)
-  float gcs[2] = {0.f, 0.f};
-  if constexpr (MODE == 0) {
-    for (int k = tid; k < DK; k += 64 * NW) {
-      gtab[2 * k] = k < p.Din ? p.g[k] : 0.f;
-      gtab[2 * k + 1] = k < p.Din ? p.g[2 * p.Din + k] : 0.f;
-    }
+  for (int k = tid; k < DK; k += 64 * NW) {
+    gtab[2 * k] = k < p.Din ? p.g[k] : 0.f;
+    gtab[2 * k + 1] = k < p.Din ? p.g[2 * p.Din + k] : 0.f;
   }
-  if constexpr (MODE == 0) { gcs[0] = p.gc[0]; gcs[1] = p.gc[1]; }
+  const float gcs[2] = {p.gc[0], p.gc[1]};
   __syncthreads();                            // the only block-wide barrier (flags zeroed, gate table written)
   const bool din_full = p.Din == DK;          // (block-uniform) no zero-fill of chunks past Din needed
   // per-lane offsets that are the same in every tile: LDS bytes of the chunks this lane writes, byte offsets of its loads
@@ -211,11 +201,10 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   int64_t rq_left = p.N - (int64_t)blockIdx.x * 32;              // N - first row of the tile requested next
   const float* rq_x = p.x + (int64_t)blockIdx.x * 32 * p.ldx;
   const uint8_t* rq_m = p.mask + (int64_t)blockIdx.x * 32;
-  const bool has_mask = MODE == 0 || p.mask != nullptr;
   auto request = [&](int set) {
     const int rows_here = rq_left > 32 ? 32 : (rq_left < 0 ? 0 : (int)rq_left);     // tile past the end: 0 rows, an empty descriptor
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rq_x), (short)0, rows_here * (int)p.ldx * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rmk = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(rq_m), (short)0, has_mask ? rows_here : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rmk = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(rq_m), (short)0, rows_here, 0x00020000);
 #pragma unroll
     for (int g = 0; g < GPW; ++g) {
 #pragma unroll
@@ -230,14 +219,12 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   constexpr int STAGE_STEPS = CPT + 4 + 3 * CPT + 4;
   auto stage_step = [&](StageState& q, int m, unsigned char* sb, int g) {
     if (m < CPT) {                            // gate dot products, both gates per v_pk_fma_f32
-      if constexpr (MODE == 0) {
-        const float4 ga = *reinterpret_cast<const float4*>(&gtab[8 * (l16 + 16 * m)]);
-        const float4 gb = *reinterpret_cast<const float4*>(&gtab[8 * (l16 + 16 * m) + 4]);
-        q.d = __builtin_elementwise_fma(f2{q.f[4 * m], q.f[4 * m]}, f2{ga.x, ga.y}, q.d);
-        q.d = __builtin_elementwise_fma(f2{q.f[4 * m + 1], q.f[4 * m + 1]}, f2{ga.z, ga.w}, q.d);
-        q.d = __builtin_elementwise_fma(f2{q.f[4 * m + 2], q.f[4 * m + 2]}, f2{gb.x, gb.y}, q.d);
-        q.d = __builtin_elementwise_fma(f2{q.f[4 * m + 3], q.f[4 * m + 3]}, f2{gb.z, gb.w}, q.d);
-      }
+      const float4 ga = *reinterpret_cast<const float4*>(&gtab[8 * (l16 + 16 * m)]);
+      const float4 gb = *reinterpret_cast<const float4*>(&gtab[8 * (l16 + 16 * m) + 4]);
+      q.d = __builtin_elementwise_fma(f2{q.f[4 * m], q.f[4 * m]}, f2{ga.x, ga.y}, q.d);
+      q.d = __builtin_elementwise_fma(f2{q.f[4 * m + 1], q.f[4 * m + 1]}, f2{ga.z, ga.w}, q.d);
+      q.d = __builtin_elementwise_fma(f2{q.f[4 * m + 2], q.f[4 * m + 2]}, f2{gb.x, gb.y}, q.d);
+      q.d = __builtin_elementwise_fma(f2{q.f[4 * m + 3], q.f[4 * m + 3]}, f2{gb.z, gb.w}, q.d);
     } else if (m == CPT) {                    // row maximum (this lane's share)
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
@@ -256,7 +243,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
       q.mx = __builtin_bit_cast(float, b);
     } else if (m == CPT + 3) {
       pow2_scales(q.mx, q.sc, q.inv);
-      if constexpr (MODE == 0) q.t = q.sdom ? q.d.x : q.d.y;     // a row needs ONE of its two gates: select before the sum and the tanh
+      q.t = q.sdom ? q.d.x : q.d.y;     // a row needs ONE of its two gates: select before the sum and the tanh
     } else if (m < CPT + 4 + 3 * CPT) {       // per chunk: hi pieces, lo pieces, the two LDS writes
       const int c = (m - (CPT + 4)) / 3, part = (m - (CPT + 4)) % 3;
       if (part == 0) {
@@ -271,15 +258,14 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
       }
     } else {
       const int r = m - (CPT + 4 + 3 * CPT);
-      if (r == 0) { if constexpr (MODE == 0) { q.t += bgnn::dpp_mov<0xB1>(q.t); q.t += bgnn::dpp_mov<0x4E>(q.t); } }
-      else if (r == 1) { if constexpr (MODE == 0) { q.t += bgnn::dpp_mov<0x141>(q.t); q.t += bgnn::dpp_mov<0x140>(q.t); q.t += q.sdom ? gcs[0] : gcs[1]; } }
-      else if (r == 2) { if constexpr (MODE == 0) q.t = tanh_fast(q.t); }
+      if (r == 0) { q.t += bgnn::dpp_mov<0xB1>(q.t); q.t += bgnn::dpp_mov<0x4E>(q.t); }
+      else if (r == 1) { q.t += bgnn::dpp_mov<0x141>(q.t); q.t += bgnn::dpp_mov<0x140>(q.t); q.t += q.sdom ? gcs[0] : gcs[1]; }
+      else if (r == 2) { q.t = tanh_fast(q.t); }
       else {
         // rank-1 coefficients (KTGNN.py:277-280): -gate_s2t on source rows (table 0), +gate_t2s on target rows (table 1);
         // lanes 0..3 of the row's 16 publish coef0 / coef1 / inverse scale / domain flag
         // (branch-free: lanes 4..15 write the same word of a dump row -- an exec-masked store splits the block the MFMAs sit in)
-        float c0 = 0.f, c1 = 0.f;
-        if constexpr (MODE == 0) { c0 = q.sdom ? -q.t : 0.f; c1 = q.sdom ? 0.f : q.t; }
+        const float c0 = q.sdom ? -q.t : 0.f, c1 = q.sdom ? 0.f : q.t;
         float val = l16 == 0 ? c0 : c1;
         val = l16 == 2 ? q.inv : val;
         val = l16 >= 3 ? (q.sdom ? 1.f : 0.f) : val;
@@ -362,12 +348,12 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
         for (int e = 0; e < 4; ++e) { whi[kb][4 * hf + e] = hi[e]; wlo[kb][4 * hf + e] = lo[e]; }
       }
     bias_n = p.bias[n];                       // epilogue constants of this lane's column
-    if constexpr (MODE == 0) wd_n = p.wd[n];
+    wd_n = p.wd[n];
   };
   const int col_base = p.col_off + wave * 32;
   // Team mode (GemmParams::team_*): two 4-wave teams, wave w and wave w ^ 4 own the same column of the two tables.  (The re-arm sits at
   // the head of the DEPTH-unrolled tile loop, so a run is taken from a multiple of DEPTH of the block's tile sequence to one.)
-  constexpr bool TEAMS = MODE == 0 && NW == 8 && NCW == 8 && AHEAD % DEPTH == 0;
+  constexpr bool TEAMS = NW == 8 && NCW == 8 && AHEAD % DEPTH == 0;
   const float* otab_own = nullptr;
   const float* otab_alt = nullptr;            // team mode: the same head's other table
   int own_table = 0;
@@ -380,7 +366,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
     otab_own = h == 0 ? (t == 0 ? p.out[0][0] : p.out[0][1]) : (t == 0 ? p.out[1][0] : p.out[1][1]);
     if constexpr (TEAMS) otab_alt = t == 0 ? p.out[0][1] : p.out[0][0];
     ooff = (int)((4 * fh * p.row_stride + (rem - t * (int)p.ldh) + fr) * 4);
-    if constexpr (MODE == 0) own_table = __builtin_amdgcn_readfirstlane(t);
+    own_table = __builtin_amdgcn_readfirstlane(t);
     otab = otab_own;
     my_table = own_table;
   }
@@ -445,18 +431,17 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       sq[q] = *reinterpret_cast<const float4*>(cf + 64 + 8 * q + 4 * fh);
-      if constexpr (MODE == 0) cq[q] = *reinterpret_cast<const float4*>(cf + 32 * my_table + 8 * q + 4 * fh);
+      cq[q] = *reinterpret_cast<const float4*>(cf + 32 * my_table + 8 * q + 4 * fh);
     }
     lds_arrive(&done[slot]);                  // everything this wave needs from the slot is in registers
     TS_MARK(5);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float s4[4] = {sq[q].x, sq[q].y, sq[q].z, sq[q].w};
-      float c4[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (MODE == 0) { c4[0] = cq[q].x; c4[1] = cq[q].y; c4[2] = cq[q].z; c4[3] = cq[q].w; }
+      const float c4[4] = {cq[q].x, cq[q].y, cq[q].z, cq[q].w};
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        res[4 * q + e] = fmaf(acc[4 * q + e], s4[e] * cinv, MODE == 0 ? fmaf(c4[e], wd_n, bias_n) : bias_n);
+        res[4 * q + e] = fmaf(acc[4 * q + e], s4[e] * cinv, fmaf(c4[e], wd_n, bias_n));
     }
     return true;
   };
@@ -510,7 +495,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
             const int qq = step - STAGE_STEPS;
             const float c4[4] = {cq[qq].x, cq[qq].y, cq[qq].z, cq[qq].w};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) tt[4 * qq + e] = MODE == 0 ? fmaf(c4[e], wd_n, bias_n) : bias_n;
+            for (int e = 0; e < 4; ++e) tt[4 * qq + e] = fmaf(c4[e], wd_n, bias_n);
           } else if (step < STAGE_STEPS + 8) {
             const int qq = step - STAGE_STEPS - 4;
             const float s4[4] = {sq[qq].x, sq[qq].y, sq[qq].z, sq[qq].w};
@@ -519,8 +504,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
           }
           if (step == STAGE_STEPS - 6) {
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq)
-              if constexpr (MODE == 0) cq[qq] = *reinterpret_cast<const float4*>(cf + 32 * my_table + 8 * qq + 4 * fh);
+            for (int qq = 0; qq < 4; ++qq) cq[qq] = *reinterpret_cast<const float4*>(cf + 32 * my_table + 8 * qq + 4 * fh);
           }
           if (step == STAGE_STEPS - 2) {
 #pragma unroll
@@ -580,7 +564,7 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
   // the LDS parts, empty descriptors for the loads and stores).  Loads issued in front of the loop would still be pending at
   // its header, and the compiler merges that state with the back edge's conservatively: it then waits for all but ~1 tile of
   // operations in every iteration instead of DEPTH tiles.
-  const bool steady_wave = consumer && otab != nullptr && !(MODE == 0 && p.tail_s2t_begin > 0) && GPW == 1;
+  const bool steady_wave = consumer && otab != nullptr && !(p.tail_s2t_begin > 0) && GPW == 1;
   uint32_t pf_done = 0, pf_ready = 0;         // counters of the next iteration's slots as read at the end of the previous one
   int ss = 0, cs = 0;                         // ring slot of the next tile to stage / to consume
   uint32_t sr = 0, cr = 0;                    // ... and its round (tile index / SLOTS)
@@ -639,15 +623,13 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
       // is tile i this wave's to consume?  Inside a team run both teams hold the run's table and take the block's tiles of the run
       // in turn; elsewhere: does any row of the tile need the wave's table (GemmParams::tile_need, tail_*)?
       bool wanted = true;
-      if constexpr (MODE == 0) {
-        if (run_lo >= 0) {
-          wanted = (((int)i - run_lo) & 1) == (wave >> 2);
-        } else if (i >= 0 && i < nlocal) {
-          const int64_t tile = blockIdx.x + i * (int64_t)gridDim.x, tb = tile * 32, te = tb + 32;
-          // single-table tail rows: a tile inside one tail group is sat out by the other table's waves
-          wanted = !(p.tail_s2t_begin > 0 && ((my_table == 0 && tb >= p.tail_t2s_begin && te <= p.tail_s2t_begin) || (my_table == 1 && tb >= p.tail_s2t_begin)));
-          if (p.tile_need != nullptr) wanted = wanted && ((p.tile_need[tile] >> my_table) & 1) != 0;     // (scalar load: uniform address)
-        }
+      if (run_lo >= 0) {
+        wanted = (((int)i - run_lo) & 1) == (wave >> 2);
+      } else if (i >= 0 && i < nlocal) {
+        const int64_t tile = blockIdx.x + i * (int64_t)gridDim.x, tb = tile * 32, te = tb + 32;
+        // single-table tail rows: a tile inside one tail group is sat out by the other table's waves
+        wanted = !(p.tail_s2t_begin > 0 && ((my_table == 0 && tb >= p.tail_t2s_begin && te <= p.tail_s2t_begin) || (my_table == 1 && tb >= p.tail_s2t_begin)));
+        if (p.tile_need != nullptr) wanted = wanted && ((p.tile_need[tile] >> my_table) & 1) != 0;     // (scalar load: uniform address)
       }
       if (steady_wave && wanted && i >= 0 && s < nlocal) {      // block-uniform per wave; no vector memory in either branch
         fused(i, rv, mk, ss, sr, cs, cr, pf_done, pf_ready, res);
@@ -681,454 +663,13 @@ __global__ __launch_bounds__(64 * NW) void transform_stream_kernel(GemmParams p)
 #endif
 }
 
-
-// ======================================================================================================================
-// Linear -> ReLU -> narrow AdaptedConv transform in the same pipeline (KTGNN_no_complement.forward :433: clf_target on
-// clf_transformer(h); stage A of bgnn_linear_narrow_transform_f32).  The activation a1 = relu(x W^T + b) of a tile never
-// leaves the registers: NA = 4 waves own 32 of its 128 columns each, here with W as the MFMA's A operand, so that a lane ends
-// up with 16 columns of ONE row -- which is the B operand of the second stage as it stands (k slot = register index).  The
-// second stage (6 fp16 MFMAs per wave against the stationary 10 x 32 slice of the consumer conv's packed rows and gate vectors)
-// leaves 12 partial sums per row in the tile's LDS slot of that wave; the wave whose arrival completes the slot's counter adds
-// the four slices and stores the tile's 32 x 12 floats.  The per-domain column sums of a1 (the next delta) accumulate per lane
-// (fp32, ~120 rows per lane) and are reduced once at the end.  The W operands get ONE power-of-two scale per matrix (a lane's
-// registers hold 16 different columns, so per-column scales do not factor out); rows are scaled per row as in the transform.
-// All waves issue the same vector-memory instructions per iteration (3 loads, 2 stores; empty descriptors where a wave has
-// nothing to store), see the header comment.
-template <int DK, int NW, int NA, int SLOTS, int AHEAD, int DEPTH>
-__global__ __launch_bounds__(64 * NW) void transform_stream2_kernel(GemmParams p) {
-  using SL = Slot<DK>;
-  static_assert(DK == 128 && NW == 8 && AHEAD >= 1 && AHEAD < SLOTS, "pipeline shape");
-  constexpr int KB16 = DK / 16, CPT = DK / 64, RPW = 32 / NW;
-  constexpr int R2 = 12;                      // floats per row of a partial / of the raw output
-  __shared__ __attribute__((aligned(16))) unsigned char ring[SLOTS * SL::BYTES];
-  __shared__ __attribute__((aligned(16))) float red[SLOTS][NA][32 * R2];
-  __shared__ uint32_t ready[SLOTS], done[SLOTS], redcnt[SLOTS], wmax[2];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (tid < SLOTS) { ready[tid] = 0u; done[tid] = 0u; redcnt[tid] = 0u; }
-  if (tid < 2) wmax[tid] = 0u;
-  __syncthreads();
-  const int64_t ntiles = (p.N + 31) / 32;
-  const int64_t nlocal = (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
-  // two teams of NA waves (waves 0..3 / 4..7, one of each per SIMD) take the tiles in turn: the long tail behind a tile's first-stage
-  // MFMAs (activation, column sums, split, second stage, reduction) then overlaps with the partner's next chain instead of
-  // running beside an idle wave (one team of 4 consumers + 4 staging-only waves measured 0.27 ms, no better than the block kernel)
-  static_assert(NW == 2 * NA, "two consumer teams");
-  const bool consumer = true;
-  const int team = wave / NA, cw = wave % NA;
-  const int NC = p.NC;                        // = 32 * NA
-#ifdef TS_STAMP
-  uint32_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t st_last = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-
-  // ---------------------------------------------------------------- staging (no gates here: the coefficient block carries the
-  // row's inverse scale and its domain flag)
-  const int l16 = lane & 15, rsub = lane >> 4;
-  const bool din_full = p.Din == DK;
-  int woff[CPT], xoff[CPT];
-  const int srow = RPW * wave + rsub;
-#pragma unroll
-  for (int c = 0; c < CPT; ++c) {
-    const int c4 = l16 + 16 * c, k = c4 * 4;
-    woff[c] = SL::chunk_off(srow, c4 >> 1) + ((c4 & 1) << 3);
-    xoff[c] = (int)((srow * p.ldx + (din_full || k < p.Din ? k : 0)) * 4);
-  }
-  const int coff = l16 < 4 ? 32 * l16 + srow : 128 + srow;
-  u32x4 ra[DEPTH][CPT];
-  uint8_t rm[DEPTH];
-  const int64_t tstep = (int64_t)gridDim.x * 32;
-  int64_t rq_left = p.N - (int64_t)blockIdx.x * 32;
-  const float* rq_x = p.x + (int64_t)blockIdx.x * 32 * p.ldx;
-  const uint8_t* rq_m = p.mask + (int64_t)blockIdx.x * 32;
-  auto request = [&](int set) {
-    const int rows_here = rq_left > 32 ? 32 : (rq_left < 0 ? 0 : (int)rq_left);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rq_x), (short)0, rows_here * (int)p.ldx * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rmk = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(rq_m), (short)0, rows_here, 0x00020000);
-#pragma unroll
-    for (int c = 0; c < CPT; ++c) ra[set][c] = __builtin_amdgcn_raw_buffer_load_b128(rx, xoff[c], 0, 0);
-    rm[set] = __builtin_amdgcn_raw_buffer_load_b8(rmk, srow, 0, 0);
-    rq_left -= tstep; rq_x += tstep * p.ldx; rq_m += tstep;
-  };
-  struct StageState { float f[4 * CPT]; bool sdom; float mx, sc, inv; h4 hi[CPT], lo[CPT]; };
-  constexpr int STAGE_STEPS = 4 + 3 * CPT + 1;
-  auto stage_step = [&](StageState& q, int m, unsigned char* sb) {
-    if (m == 0) {
-#pragma unroll
-      for (int c = 0; c < CPT; ++c) {
-        q.mx = fmaxf(fmaxf(fabsf(q.f[4 * c]), fabsf(q.f[4 * c + 1])), q.mx);
-        q.mx = fmaxf(fmaxf(fabsf(q.f[4 * c + 2]), fabsf(q.f[4 * c + 3])), q.mx);
-      }
-    } else if (m == 1) {
-      unsigned b = __builtin_bit_cast(unsigned, q.mx);
-      b = max(b, (unsigned)__builtin_amdgcn_update_dpp(0, (int)b, 0xB1, 0xF, 0xF, true));
-      b = max(b, (unsigned)__builtin_amdgcn_update_dpp(0, (int)b, 0x4E, 0xF, 0xF, true));
-      q.mx = __builtin_bit_cast(float, b);
-    } else if (m == 2) {
-      unsigned b = __builtin_bit_cast(unsigned, q.mx);
-      b = max(b, (unsigned)__builtin_amdgcn_update_dpp(0, (int)b, 0x141, 0xF, 0xF, true));
-      b = max(b, (unsigned)__builtin_amdgcn_update_dpp(0, (int)b, 0x140, 0xF, 0xF, true));
-      q.mx = __builtin_bit_cast(float, b);
-    } else if (m == 3) {
-      pow2_scales(q.mx, q.sc, q.inv);
-    } else if (m < 4 + 3 * CPT) {
-      const int c = (m - 4) / 3, part = (m - 4) % 3;
-      if (part == 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q.hi[c][e] = (_Float16)(q.f[4 * c + e] * q.sc);
-      } else if (part == 1) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q.lo[c][e] = (_Float16)fmaf(q.f[4 * c + e], q.sc, -(float)q.hi[c][e]);
-      } else {
-        *reinterpret_cast<h4*>(sb + woff[c]) = q.hi[c];
-        *reinterpret_cast<h4*>(sb + SL::PIECE + woff[c]) = q.lo[c];
-      }
-    } else {
-      float val = l16 == 2 ? q.inv : 0.f;
-      val = l16 >= 3 ? (q.sdom ? 1.f : 0.f) : val;
-      reinterpret_cast<float*>(sb + SL::COEF)[coff] = val;
-    }
-  };
-  auto stage_init = [&](StageState& q, const u32x4 (&rv)[CPT], uint8_t mk) {
-#pragma unroll
-    for (int c = 0; c < CPT; ++c) {
-      float4 v = __builtin_bit_cast(float4, rv[c]);
-      if (!din_full && (l16 + 16 * c) * 4 >= p.Din) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      q.f[4 * c] = v.x; q.f[4 * c + 1] = v.y; q.f[4 * c + 2] = v.z; q.f[4 * c + 3] = v.w;
-    }
-    q.sdom = mk != 0; q.mx = 0.f; q.sc = q.inv = 0.f;
-  };
-  auto stage = [&](int64_t j, const u32x4 (&rv)[CPT], uint8_t mk, int slot, uint32_t round) {
-    if (j >= nlocal) return;
-    lds_wait_ge(&done[slot], (uint32_t)NA * round);
-    unsigned char* const sb = ring + slot * SL::BYTES;
-    StageState q;
-    stage_init(q, rv, mk);
-#pragma unroll
-    for (int m = 0; m < STAGE_STEPS; ++m) stage_step(q, m, sb);
-    lds_arrive(&ready[slot]);
-  };
-
-  // ---------------------------------------------------------------- consumer state
-  const int fr = lane & 31, fh = lane >> 5;
-  const int col_base = cw * 32;
-  h8 whi[KB16], wlo[KB16];                    // stationary A operand: W[col_base + fr][16kb + 8fh .. +7]
-  h8 w2h[2], w2l[2];                          // second stage, stationary A operand: row fr of (w2 | g2), k slot r = column col_base + 8(r/4) + 4fh + r%4
-  float bias16[16];
-  float cinvW = 0.f, cinvW2 = 0.f;
-  float cs_s[16], cs_t[16], cnt_s = 0.f, cnt_t = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { cs_s[r] = cs_t[r] = 0.f; bias16[r] = 0.f; }
-  {
-    float4 w[KB16][2];
-    float w2v[16];
-    float mx = 0.f, mx2 = 0.f;
-    if (consumer) {
-#pragma unroll
-      for (int kb = 0; kb < KB16; ++kb)
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          const int k = 16 * kb + 8 * fh + 4 * hf;
-          float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (k < p.Din) t = *reinterpret_cast<const float4*>(p.Wp + (int64_t)(col_base + fr) * p.Din + k);
-          w[kb][hf] = t;
-          mx = fmaxf(fmaxf(mx, fmaxf(fabsf(t.x), fabsf(t.y))), fmaxf(fabsf(t.z), fabsf(t.w)));
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int c = col_base + 8 * (r >> 2) + 4 * fh + (r & 3);
-        float v = 0.f;
-        if (fr < 8) v = p.w2[(int64_t)fr * NC + c];
-        else if (fr < 10) v = p.g2[(int64_t)(fr - 8) * 2 * NC + c];
-        w2v[r] = v;
-        mx2 = fmaxf(mx2, fabsf(v));
-        bias16[r] = p.bias[c];
-      }
-      mx = bgnn::group_max<64>(mx);
-      mx2 = bgnn::group_max<64>(mx2);
-      if (lane == 0) { atomicMax(&wmax[0], __builtin_bit_cast(unsigned, mx)); atomicMax(&wmax[1], __builtin_bit_cast(unsigned, mx2)); }
-    }
-    __syncthreads();                          // one scale per matrix: the largest magnitude over all NA waves' slices
-    if (consumer) {
-      float sc, sc2;
-      pow2_scales(__builtin_bit_cast(float, wmax[0]), sc, cinvW);
-      pow2_scales(__builtin_bit_cast(float, wmax[1]), sc2, cinvW2);
-#pragma unroll
-      for (int kb = 0; kb < KB16; ++kb)
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          h4 hi, lo;
-          split4(w[kb][hf], sc, hi, lo);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { whi[kb][4 * hf + e] = hi[e]; wlo[kb][4 * hf + e] = lo[e]; }
-        }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const _Float16 h = (_Float16)(w2v[r] * sc2);
-        w2h[r >> 3][r & 7] = h;
-        w2l[r >> 3][r & 7] = (_Float16)fmaf(w2v[r], sc2, -(float)h);
-      }
-    }
-  }
-  const int roff0 = SL::chunk_off(fr, fh);
-  auto roff = [&](int kb) { return roff0 ^ (kb << 5); };
-
-  // everything after the first-stage accumulators of a tile: activation, column sums, second stage, partial sums into the slot's
-  // reduction block; -> true (with the tile's two float4 items of this lane in o0 / o1) for the wave that completes the block
-  auto post = [&](const f32x16& acc, float s_row, float dom, int64_t tile, int slot, uint32_t round, float4& o0, float4& o1) -> bool {
-    float a1[16];
-    const float sc1 = s_row * cinvW;
-    float mx = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float v = fmaf(acc[r], sc1, bias16[r]);
-      if (p.relu) v = fmaxf(v, 0.f);
-      a1[r] = v;
-      mx = fmaxf(mx, fabsf(v));
-    }
-    const bool valid = tile * 32 + fr < p.N;
-    const float ws = (valid && dom != 0.f) ? 1.f : 0.f, wt = (valid && dom == 0.f) ? 1.f : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { cs_s[r] = fmaf(ws, a1[r], cs_s[r]); cs_t[r] = fmaf(wt, a1[r], cs_t[r]); }
-    if (fh == 0) { cnt_s += ws; cnt_t += wt; }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));       // the row's two lane halves share the scale
-    float sc2, inv2;
-    pow2_scales(mx, sc2, inv2);
-    h8 ah[2], al[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const _Float16 h = (_Float16)(a1[r] * sc2);
-      ah[r >> 3][r & 7] = h;
-      al[r >> 3][r & 7] = (_Float16)fmaf(a1[r], sc2, -(float)h);
-    }
-    f32x16 acc2;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2h[kb], al[kb], acc2, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2l[kb], ah[kb], acc2, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2h[kb], ah[kb], acc2, 0, 0, 0);
-    }
-    // accumulator register i of lane (fr, fh) is output 8*(i/4) + 4*fh + i%4 of row fr: lane half 0 holds outputs 0..3 and
-    // 8..11 (8, 9 are the gate products), lane half 1 outputs 4..7
-    const float s2 = inv2 * cinvW2;
-    float* r2 = &red[slot][cw][fr * R2];
-    if (fh == 0) {
-      *reinterpret_cast<float4*>(r2) = make_float4(acc2[0] * s2, acc2[1] * s2, acc2[2] * s2, acc2[3] * s2);
-      *reinterpret_cast<float4*>(r2 + 8) = make_float4(acc2[4] * s2, acc2[5] * s2, 0.f, 0.f);
-    } else {
-      *reinterpret_cast<float4*>(r2 + 4) = make_float4(acc2[0] * s2, acc2[1] * s2, acc2[2] * s2, acc2[3] * s2);
-    }
-    TS_MARK(4);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    uint32_t old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(&redcnt[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    old = __builtin_amdgcn_readfirstlane(old);
-    const bool last = old == (uint32_t)NA * (round + 1) - 1;
-    if (last) {                               // wave-uniform: this wave adds the NA slices of the tile
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-      o0 = *reinterpret_cast<const float4*>(&red[slot][0][lane * 4]);
-      o1 = lane < 32 ? *reinterpret_cast<const float4*>(&red[slot][0][(lane + 64) * 4]) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int w = 1; w < NA; ++w) {
-        const float4 u = *reinterpret_cast<const float4*>(&red[slot][w][lane * 4]);
-        o0.x += u.x; o0.y += u.y; o0.z += u.z; o0.w += u.w;
-        if (lane < 32) {
-          const float4 v = *reinterpret_cast<const float4*>(&red[slot][w][(lane + 64) * 4]);
-          o1.x += v.x; o1.y += v.y; o1.z += v.z; o1.w += v.w;
-        }
-      }
-    }
-    TS_MARK(5);
-    return last;
-  };
-  auto mfma_chain_plain = [&](const unsigned char* sb, f32x16& acc) {
-    constexpr int NB = KB16 / 2;
-    h8 fa[2][2][2];
-    auto fetch = [&](int b, int buf) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        fa[buf][t][0] = *reinterpret_cast<const h8*>(sb + roff(2 * b + t));
-        fa[buf][t][1] = *reinterpret_cast<const h8*>(sb + SL::PIECE + roff(2 * b + t));
-      }
-    };
-    fetch(0, 0); fetch(1, 1);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int kb = 2 * b + t;
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[kb], fa[b & 1][t][1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[kb], fa[b & 1][t][0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[kb], fa[b & 1][t][0], acc, 0, 0, 0);
-      }
-      if (b + 2 < NB) fetch(b + 2, b & 1);
-    }
-  };
-  // plain consumption (first / last iterations): wait, chain, post
-  auto consume = [&](int64_t i, int slot, uint32_t round, float4& o0, float4& o1) -> bool {
-    if (!consumer || i >= nlocal) return false;
-    const unsigned char* const sb = ring + slot * SL::BYTES;
-    lds_wait_ge(&ready[slot], (uint32_t)NW * (round + 1));
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    mfma_chain_plain(sb, acc);
-    const float* cf = reinterpret_cast<const float*>(sb + SL::COEF);
-    const float s_row = cf[64 + fr], dom = cf[96 + fr];
-    lds_arrive(&done[slot]);
-    return post(acc, s_row, dom, blockIdx.x + i * (int64_t)gridDim.x, slot, round, o0, o1);
-  };
-  // steady state: the staging steps of tile i + AHEAD ride behind the MFMAs of tile i
-  auto fused = [&](int64_t i, const u32x4 (&rv)[CPT], uint8_t mk, int sslot, uint32_t sround, int cslot, uint32_t cround,
-                   uint32_t pf_done, uint32_t pf_ready, float4& o0, float4& o1) -> bool {
-    TS_MARK(0);
-    lds_wait_ge2(&done[sslot], (uint32_t)NA * sround, pf_done, &ready[cslot], (uint32_t)NW * (cround + 1), pf_ready);
-    TS_MARK(1);
-    unsigned char* const wb = ring + sslot * SL::BYTES;
-    const unsigned char* const sb = ring + cslot * SL::BYTES;
-    StageState q;
-    stage_init(q, rv, mk);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    constexpr int NB = KB16 / 2;
-    h8 fa[2][2][2];
-    auto fetch = [&](int b, int buf) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        fa[buf][t][0] = *reinterpret_cast<const h8*>(sb + roff(2 * b + t));
-        fa[buf][t][1] = *reinterpret_cast<const h8*>(sb + SL::PIECE + roff(2 * b + t));
-      }
-    };
-    fetch(0, 0); fetch(1, 1);
-    const float* cf = reinterpret_cast<const float*>(sb + SL::COEF);
-    const float s_row = cf[64 + fr], dom = cf[96 + fr];
-    int step = 0;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int kb = 2 * b + t;
-#pragma unroll
-        for (int pr = 0; pr < 3; ++pr) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(pr == 1 ? wlo[kb] : whi[kb], pr == 0 ? fa[b & 1][t][1] : fa[b & 1][t][0], acc, 0, 0, 0);
-          if (step < STAGE_STEPS) stage_step(q, step, wb);
-          ++step;
-        }
-      }
-      if (b + 2 < NB) fetch(b + 2, b & 1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    lds_inc(&ready[sslot]);
-    lds_inc(&done[cslot]);
-    TS_MARK(3);
-    return post(acc, s_row, dom, blockIdx.x + i * (int64_t)gridDim.x, cslot, cround, o0, o1);
-  };
-  // the tile's 32 x 12 floats: item `lane` and item `lane + 64` (16 bytes each); empty descriptor unless this wave finished the tile
-  int64_t st_left = 0;
-  float* st_o = p.raw;
-  auto store_raw = [&](bool live, const float4& o0, const float4& o1) {
-    const int rows_here = (!live || st_left < 0) ? 0 : (st_left > 32 ? 32 : (int)st_left);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(st_o, (short)0, rows_here * R2 * 4, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), ro, lane * 16, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), ro, (lane + 64) * 16, 0, 0);
-    st_left -= tstep; st_o += tstep * R2;
-  };
-
-  // ---------------------------------------------------------------- pipeline (see transform_stream_kernel)
-  uint32_t pf_done = 0, pf_ready = 0;
-  int ss = 0, cs = 0;
-  uint32_t sr = 0, cr = 0;
-  auto bump = [](int& slot, uint32_t& round) { ++slot; if (slot == SLOTS) { slot = 0; ++round; } };
-  int64_t i_first = -(AHEAD + DEPTH);
-  asm volatile("" : "+s"(i_first));
-  st_left = p.N - ((int64_t)blockIdx.x + i_first * (int64_t)gridDim.x) * 32;
-  st_o = p.raw + ((int64_t)blockIdx.x + i_first * (int64_t)gridDim.x) * 32 * R2;
-  for (int64_t i0 = i_first; i0 < nlocal; i0 += DEPTH) {
-#pragma unroll
-    for (int u = 0; u < DEPTH; ++u) {
-      const int64_t i = i0 + u, s = i + AHEAD;
-      u32x4 rv[CPT];
-      uint8_t mk;
-#pragma unroll
-      for (int c = 0; c < CPT; ++c) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { unsigned t; asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(ra[u][c][e])); rv[c][e] = t; }
-      }
-      { unsigned tm; asm volatile("v_mov_b32 %0, %1" : "=v"(tm) : "v"((unsigned)rm[u])); mk = (uint8_t)tm; }
-      TS_MARK(0);
-      request(u);
-      TS_MARK(2);
-      float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
-      bool live = false;
-      const bool my_turn = (int)(i & 1) == team;                 // (wave-uniform)
-      if (my_turn && i >= 0 && s < nlocal) {
-        live = fused(i, rv, mk, ss, sr, cs, cr, pf_done, pf_ready, o0, o1);
-        bump(ss, sr);
-        bump(cs, cr);
-      } else {
-        if (s >= 0) {
-          stage(s, rv, mk, ss, sr);
-          bump(ss, sr);
-        }
-        if (i >= 0) {
-          if (my_turn) live = consume(i, cs, cr, o0, o1);
-          bump(cs, cr);
-        }
-      }
-      TS_MARK(6);
-      store_raw(live, o0, o1);
-      pf_done = lds_peek(&done[ss]);
-      pf_ready = lds_peek(&ready[cs]);
-      TS_MARK(7);
-    }
-  }
-#ifdef TS_STAMP
-  if (lane == 0 && p.sk_out[0][0] != nullptr) {
-    float* o = p.sk_out[0][0] + ((int64_t)blockIdx.x * NW + wave) * 8;
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) o[k2] = (float)st_acc[k2];
-  }
-#endif
-  // ---------------------------------------------------------------- per-domain column sums of the activation (+ node counts)
-  if (consumer && p.colsum != nullptr) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float a = cs_s[r], b = cs_t[r];
-#pragma unroll
-      for (int m = 16; m >= 1; m >>= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }     // over the 32 rows of a lane half
-      if (fr == 0) {
-        const int c = col_base + 8 * (r >> 2) + 4 * fh + (r & 3);
-        unsafeAtomicAdd(&p.colsum[c], (double)a);
-        unsafeAtomicAdd(&p.colsum[NC + c], (double)b);
-      }
-    }
-    if (cw == 0) {
-      float a = cnt_s, b = cnt_t;
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-      if (lane == 0) { unsafeAtomicAdd(&p.colsum[2 * NC], (double)a); unsafeAtomicAdd(&p.colsum[2 * NC + 1], (double)b); }
-    }
-  }
-}
-
 }  // namespace
 
-static bool stream2_supported(const GemmParams& p);
-
-bool bgnn_tf_stream_supported(const GemmParams& p, int mode) {
-  if (mode == 2) return stream2_supported(p);
-  if (mode != 0) return false;
+bool bgnn_tf_stream_supported(const GemmParams& p) {
   if (p.n_heads != 1 || p.Din > 128 || p.Din <= 64 || (p.Din & 3) || (p.ldh & 31)) return false;
   if (p.NC != 2 * p.ldh || (p.NC != 256 && p.NC != 128) || p.col_off != 0) return false;
   if (p.ldx * 4 * 32 > 0x7fffffff || p.row_stride * 4 * 36 > 0x7fffffff) return false;     // 32-bit offsets inside a tile
   return true;
-}
-
-static bool stream2_supported(const GemmParams& p) {
-  return p.NC == 128 && p.Din <= 128 && p.Din > 64 && (p.Din & 3) == 0 && p.mask && p.w2 && p.g2 && p.raw && p.ldx * 4 * 32 <= 0x7fffffff;
 }
 
 // Team mode's admission (GemmParams::team_*): a run the kernel should not take is emptied -- BGNN_TS_TEAMS=0 in the environment (read
@@ -1151,39 +692,9 @@ static void team_runs_admit(GemmParams& p, int64_t ntiles, int64_t nblocks) {
   }
 }
 
-int bgnn_tf_stream_launch(const GemmParams& p_in, int mode, hipStream_t st, int n_cu) {
+int bgnn_tf_stream_launch(const GemmParams& p_in, hipStream_t st, int n_cu) {
   GemmParams p = p_in;
-  if (mode == 2) {
-    if (!stream2_supported(p)) return BGNN_E_SHAPE;
-    const int64_t nt = (p.N + 31) / 32;
-    const dim3 g2((unsigned)(nt < n_cu ? nt : n_cu), 1u);
-#ifdef TS_STAMP
-    {
-      GemmParams q = p;
-      static float* dbuf2 = nullptr;
-      if (!dbuf2) (void)hipMalloc((void**)&dbuf2, sizeof(float) * 256 * 8 * 8);
-      q.sk_out[0][0] = dbuf2;
-      hipLaunchKernelGGL((transform_stream2_kernel<128, 8, 4, TS_SLOTS, TS_AHEAD, TS_DEPTH>), g2, dim3(512), 0, st, q);
-      static int calls2 = 0;
-      if (++calls2 % 12 == 0) {
-        (void)hipDeviceSynchronize();
-        static float host[256 * 8 * 8];
-        (void)hipMemcpy(host, dbuf2, sizeof(float) * g2.x * 8 * 8, hipMemcpyDeviceToHost);
-        double acc[8] = {0};
-        for (unsigned w = 0; w < g2.x * 8; ++w) for (int k = 0; k < 8; ++k) acc[k] += host[w * 8 + k];
-        const double d = (double)g2.x * 8 * ((double)nt / g2.x);
-        fprintf(stderr, "[ts2 stamp] cycles per tile and wave (mean): other %.0f  flags %.0f  request %.0f  chain(+stage, fused turn) %.0f  post %.0f  reduce/flush %.0f  pre-store %.0f  stores+peek %.0f\n",
-                acc[0] / d, acc[1] / d, acc[2] / d, acc[3] / d, acc[4] / d, acc[5] / d, acc[6] / d, acc[7] / d);
-      }
-      BGNN_LAUNCH_CHECK();
-      return 0;
-    }
-#endif
-    hipLaunchKernelGGL((transform_stream2_kernel<128, 8, 4, TS_SLOTS, TS_AHEAD, TS_DEPTH>), g2, dim3(512), 0, st, p);
-    BGNN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (!bgnn_tf_stream_supported(p, mode)) return BGNN_E_SHAPE;
+  if (!bgnn_tf_stream_supported(p)) return BGNN_E_SHAPE;
   const int64_t ntiles = (p.N + 31) / 32;
   const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu), 1u);
   team_runs_admit(p, ntiles, (int64_t)grid.x);
@@ -1192,8 +703,8 @@ int bgnn_tf_stream_launch(const GemmParams& p_in, int mode, hipStream_t st, int 
   static float* dbuf = nullptr;
   if (!dbuf) (void)hipMalloc((void**)&dbuf, sizeof(float) * 256 * 8 * 8);
   q.raw = dbuf;
-  if (p.NC == 256) hipLaunchKernelGGL((transform_stream_kernel<128, 8, 8, TS_SLOTS, TS_AHEAD, TS_DEPTH, 0>), grid, dim3(512), 0, st, q);
-  else hipLaunchKernelGGL((transform_stream_kernel<128, 8, 4, TS_SLOTS, TS_AHEAD, TS_DEPTH, 0>), grid, dim3(512), 0, st, q);
+  if (p.NC == 256) hipLaunchKernelGGL((transform_stream_kernel<128, 8, 8, TS_SLOTS, TS_AHEAD, TS_DEPTH>), grid, dim3(512), 0, st, q);
+  else hipLaunchKernelGGL((transform_stream_kernel<128, 8, 4, TS_SLOTS, TS_AHEAD, TS_DEPTH>), grid, dim3(512), 0, st, q);
   static int calls = 0;
   if (++calls % 12 == 0) {
     (void)hipDeviceSynchronize();
@@ -1208,8 +719,8 @@ int bgnn_tf_stream_launch(const GemmParams& p_in, int mode, hipStream_t st, int 
             acc[4] / (grid.x * 8) / nt, mx[4] / nt, acc[5] / (grid.x * 8) / nt, mx[5] / nt, acc[6] / (grid.x * 8) / nt, mx[6] / nt, acc[7] / (grid.x * 8) / nt, mx[7] / nt);
   }
 #else
-  if (p.NC == 256) hipLaunchKernelGGL((transform_stream_kernel<128, 8, 8, TS_SLOTS, TS_AHEAD, TS_DEPTH, 0>), grid, dim3(512), 0, st, p);
-  else hipLaunchKernelGGL((transform_stream_kernel<128, 8, 4, TS_SLOTS, TS_AHEAD, TS_DEPTH, 0>), grid, dim3(512), 0, st, p);
+  if (p.NC == 256) hipLaunchKernelGGL((transform_stream_kernel<128, 8, 8, TS_SLOTS, TS_AHEAD, TS_DEPTH>), grid, dim3(512), 0, st, p);
+  else hipLaunchKernelGGL((transform_stream_kernel<128, 8, 4, TS_SLOTS, TS_AHEAD, TS_DEPTH>), grid, dim3(512), 0, st, p);
 #endif
   BGNN_LAUNCH_CHECK();
   return 0;

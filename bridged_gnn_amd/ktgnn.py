@@ -586,7 +586,7 @@ class AdaptedConv(_PlistHooks, nn.Module):
         din_pad = xp.shape[1]
         if delta is None and sums is None:
             sums = ops.domain_sums(xp, mask_u8)
-        # with `sums` the kernel that forms W.delta also forms delta (bgnn_adaptedconv_transform_sums_f32)
+        # with `sums` the kernel that forms W.delta also forms delta (bgnn_adaptedconv_transform_f32, sums_opt)
         res = ops.adaptedconv_transform(xp, mask_u8, delta, self.packed(din_pad, partner),
                                         out=out if (out is None or partner is not None) else [out],
                                         sums=sums if delta is None else None, tail_single=tail_single,

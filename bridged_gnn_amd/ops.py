@@ -568,8 +568,8 @@ def single_table_runs(tile_need):
 
 
 def transform_team_runs(N, device, tile_need=None, tail_single=(0, 0)):
-    """The plan of the hidden transform's team mode (bgnn.h: bgnn_adaptedconv_transform_need2_f32): the runs of single-table tiles
-    -- out of the need mask, or the two tail groups -- that give every block of the stream kernel's launch (one per CU) at least
+    """The plan of the hidden transform's team mode (bgnn.h: bgnn_adaptedconv_transform_f32, team_runs_host_opt): the runs of
+    single-table tiles -- out of the need mask, or the two tail groups -- that give every block of the stream kernel's launch (one per CU) at least
     TEAM_MIN_TILES tiles.  [] = team mode stays off for this graph."""
     if tile_need is None and not (tail_single[0] or tail_single[1]):
         return []
@@ -618,11 +618,7 @@ def adaptedconv_transform(x, mask_u8, delta, packed, out=None, sums=None, tail_s
     if delta is None:
         if sums is None or sums.dtype != torch.float64 or sums.numel() != 2 * Din + 2:
             raise ValueError("adaptedconv_transform needs delta [Din] or the float64 domain sums [2*Din+2]")
-        fn, first, name = lib.bgnn_adaptedconv_transform_sums_f32, sums, "bgnn_adaptedconv_transform_sums_f32"
-    else:
-        fn, first, name = lib.bgnn_adaptedconv_transform_f32, delta, "bgnn_adaptedconv_transform_f32"
-    tail = (int(tail_single[0]), int(tail_single[1])) if delta is None else ()
-    if delta is not None and tuple(tail_single) != (0, 0):
+    elif tuple(tail_single) != (0, 0):
         raise ValueError("tail_single needs the sums form of the transform")
     if tile_need is not None:
         # `tile_need` (DstCSR.tile_need): rows of a table that the aggregation never reads may stay unwritten (sums form only)
@@ -630,18 +626,16 @@ def adaptedconv_transform(x, mask_u8, delta, packed, out=None, sums=None, tail_s
             raise ValueError("tile_need needs the sums form of the transform and no tail_single")
         if tile_need.dtype != torch.int32 or tile_need.numel() != (N + 31) // 32:
             raise ValueError("tile_need: one int32 per 32-row tile")
-        fn, name, tail = lib.bgnn_adaptedconv_transform_need_f32, "bgnn_adaptedconv_transform_need_f32", (L.ptr(tile_need),)
+    runs = []
     if delta is None and H == 1 and (tile_need is not None or tail_single[0] or tail_single[1]):
         c = getattr(tile_need, "_team_plan", None)                    # (the plan of this need mask, decided at its first launch)
         runs = c[1] if (c is not None and c[0] == (N, dev, tile_need._version)) else transform_team_runs(N, dev, tile_need, tail_single)
-        if runs:
-            flat = (ctypes.c_int64 * (3 * len(runs)))(*[v for r in runs for v in r])       # host memory, read during the call
-            fn, name = lib.bgnn_adaptedconv_transform_need2_f32, "bgnn_adaptedconv_transform_need2_f32"
-            tail = (int(tail_single[0]), int(tail_single[1]), L.ptr(tile_need) if tile_need is not None else None, flat, len(runs))
-    rc = fn(L.ptr(x), N, Din, x.stride(0), L.ptr(mask_u8), L.ptr(first), H, D, L.ptr(Wp), L.ptr(bp), L.ptr(gates), L.ptr(gconst),
-            L.ptr_rows(out[0][1]), L.ptr_rows(out[0][0]), L.ptr_rows(o1[1]), L.ptr_rows(o1[0]), ldh, row_stride, *tail,
-            L.ptr(small), L.stream())
-    L.check(rc, name)
+    flat = (ctypes.c_int64 * (3 * len(runs)))(*[v for r in runs for v in r]) if runs else None     # host memory, read during the call
+    rc = lib.bgnn_adaptedconv_transform_f32(
+        L.ptr(x), N, Din, x.stride(0), L.ptr(mask_u8), L.ptr(delta), None if delta is not None else L.ptr(sums), H, D, L.ptr(Wp), L.ptr(bp),
+        L.ptr(gates), L.ptr(gconst), L.ptr_rows(out[0][1]), L.ptr_rows(out[0][0]), L.ptr_rows(o1[1]), L.ptr_rows(o1[0]), ldh, row_stride,
+        int(tail_single[0]), int(tail_single[1]), L.ptr(tile_need), flat, len(runs), L.ptr(small), L.stream())
+    L.check(rc, "bgnn_adaptedconv_transform_f32")
     return out
 
 

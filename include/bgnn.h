@@ -40,8 +40,11 @@ extern "C" {
  * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
- * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone. */
-#define BGNN_VERSION 114
+ * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone.
+ * 115 is NOT call-compatible with 114: bgnn_adaptedconv_transform_f32 takes delta_opt AND sums_opt (exactly one non-NULL), the
+ * tail counts, the need mask and the team runs for every caller, and the _transform_sums_, _transform_need_ and
+ * _transform_need2_ entries that each took a prefix of that list are gone. */
+#define BGNN_VERSION 115
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
 #define BGNN_E_WORKSPACE (-3)   /* ws_bytes smaller than *_workspace_bytes()    */
@@ -92,7 +95,9 @@ int bgnn_build_dst_csr(const int64_t* edge_index, int64_t E, int64_t N, int rewr
  *   each output row holds ldh >= D floats (ldh % 4 == 0; columns D..ldh-1 come out as 0) and rows are
  *   row_stride >= ldh floats apart (row_stride % 4 == 0), so several convs' tables can be interleaved in one
  *   allocation (multi-GPU: one halo exchange then carries the rows of all of them).
- * small_ws: n_heads*(2*ldh+2) floats of scratch (W.delta and the gates' delta halves).       */
+ * small_ws: n_heads*(2*ldh+2) floats of scratch (W.delta and the gates' delta halves).
+ * The ONE transform entry takes delta or the domain sums, and optionally tail groups, a per-tile need mask and team
+ * runs: see its declaration below.                                                           */
 int bgnn_domain_sums_f64(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
                          double* sums_io /*[2*Din+2]*/, void* stream);
 /* Two-stage form of bgnn_domain_sums_f64 (same result up to fp64 summation order, and run-to-run identical): every CU
@@ -125,7 +130,7 @@ int bgnn_linear_narrow_transform_f32(const float* x, int64_t N, int32_t Din, int
                                      const float* bias, int32_t Dout, int relu, const uint8_t* mask,
                                      double* colsum, const float* Wp2, const float* gates2, float* raw, void* stream);
 /* The classifier stage's dense work in ONE pass over the hidden activation x = h (KTGNN.py:432-434; ABI 112): the narrow tables of
- * the `sk_heads` (1 or 2) convs that read h itself -- the transform of bgnn_adaptedconv_transform_sums_f32 with `sums_x` for the packed
+ * the `sk_heads` (1 or 2) convs that read h itself -- the transform of bgnn_adaptedconv_transform_f32 in its sums form with `sums_x` for the packed
  * operands sk_Wp / sk_bias / sk_gates (sk_heads * 2 * sk_ldh <= 24 packed columns) -- AND stage A of the fused pair above (W, bias,
  * Dout = 128, colsum, Wp2, gates2, raw).  Same results as the two separate launches; Din in (64, 128], Din % 4 == 0, else
  * BGNN_E_SHAPE.  small_ws: sk_heads * (2 * sk_ldh + 2) + 8 floats. */
@@ -228,52 +233,34 @@ int bgnn_transform_bwd_finish_f32(const float* dWall, const float* ex, const flo
  *   training path): one stream over X for all vectors. */
 int bgnn_rowdot_f32(const float* X, int64_t ldx, int64_t N, int32_t d, const float* V, int64_t ldv, int32_t nv,
                     float* out /*[N][nv]*/, void* stream);
+/* The transform of (a11) above.  Exactly one of delta_opt / sums_opt is non-NULL (both or neither: BGNN_E_NULL):
+ *   delta_opt  [Din] floats, 16-byte aligned: the domain-mean difference of bgnn_domain_delta_f32;
+ *   sums_opt   [2*Din+2] doubles (after any all-reduce): the tiny W.delta kernel forms delta with the arithmetic of
+ *              bgnn_domain_delta_f32 (bit-identical), one launch less per conv.
+ * n_tail_t2s / n_tail_s2t: the LAST n_tail_t2s + n_tail_s2t of the N rows (in that order) are rows whose consumer reads
+ *   only h_t2s / only h_s2t -- the resident input halo of a partitioned graph (dist.py): for them the other table MAY be
+ *   left unwritten (single-table launches inside the W-stationary kernel's envelope, both tables outside it).
+ * tile_need_opt: NULL, or one int32 per 32-row tile of x, bit 0 set = some row of the tile has its h_s2t row read by the
+ *   aggregation, bit 1 = its h_t2s row (a node's h_t2s row is gathered only by source-domain destinations and as the node's own
+ *   row if it is one, KTGNN.py:292-295; with s -> t bridge edges no target node feeds a source destination and half of the h_t2s
+ *   table is dead).  Rows of a table that no tile needs MAY be left unwritten.  Only the stream kernel (one head, 128 / 256 packed
+ *   columns, 64 < Din <= 128) honours the mask; other shapes write both tables.  Tail groups OR a need mask, not both
+ *   (BGNN_E_SHAPE).
+ * team_runs_host_opt: NULL, or n_team_runs <= 2 triples (first tile, one past the last tile, table) of int64 in HOST memory,
+ *   read during the call: runs of 32-row tiles in which EVERY tile needs the one table `table` (0 = h_s2t, 1 = h_t2s) -- by
+ *   tile_need_opt (value 1 << table) or by lying inside that table's tail group.  The caller vouches for that; it decides the runs
+ *   once per graph.  Inside a run the stream kernel's two 4-wave teams both hold the needed table's columns and take a block's
+ *   tiles in turn (csrc/bgnn_transform_stream.hip).  Outputs are bit for bit those of a call without runs.  A run that gives some
+ *   block of the launch fewer than 4 tiles, or a shape the stream kernel does not take at 256 packed columns, is ignored; so are
+ *   all runs with BGNN_TS_TEAMS=0 in the environment (read once). */
 int bgnn_adaptedconv_transform_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                   const uint8_t* mask, const float* delta,
+                                   const uint8_t* mask, const float* delta_opt, const double* sums_opt,
                                    int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
                                    const float* gates, const float* gate_const_opt,
                                    float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                   int64_t ldh, int64_t row_stride, float* small_ws, void* stream);
-/* Same transform taking the domain sums ([2*Din+2] doubles, after any all-reduce) instead of delta: the tiny
- * W.delta kernel forms delta with the arithmetic of bgnn_domain_delta_f32 (bit-identical), one launch less per conv.
- * n_tail_t2s / n_tail_s2t: the LAST n_tail_t2s + n_tail_s2t of the N rows (in that order) are rows whose consumer reads
- * only h_t2s / only h_s2t -- the resident input halo of a partitioned graph (dist.py): for them the other table MAY be
- * left unwritten (single-table launches inside the W-stationary kernel's envelope, both tables outside it). */
-int bgnn_adaptedconv_transform_sums_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                        const uint8_t* mask, const double* sums,
-                                        int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                        const float* gates, const float* gate_const_opt,
-                                        float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                        int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
-                                        float* small_ws, void* stream);
-/* The sums form with a per-tile need mask (ABI 111).  tile_need_opt: NULL, or one int32 per 32-row tile of x, bit 0 set = some row
- * of the tile has its h_s2t row read by the aggregation, bit 1 = its h_t2s row (a node's h_t2s row is gathered only by source-
- * domain destinations and as the node's own row if it is one, KTGNN.py:292-295; with s -> t bridge edges no target node feeds a
- * source destination and half of the h_t2s table is dead).  Rows of a table that no tile needs MAY be left unwritten.  Only the
- * stream kernel (one head, 128 / 256 packed columns, 64 < Din <= 128) honours the mask; other shapes write both tables. */
-int bgnn_adaptedconv_transform_need_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                        const uint8_t* mask, const double* sums,
-                                        int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                        const float* gates, const float* gate_const_opt,
-                                        float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                        int64_t ldh, int64_t row_stride, const int32_t* tile_need_opt,
-                                        float* small_ws, void* stream);
-/* The sums form with tail groups OR a need mask (not both), plus up to two "team runs" (additive entry: the revision does not
- * move).  team_runs_host_opt: NULL, or n_team_runs <= 2 triples (first tile, one past the last tile, table) of int64 in HOST memory,
- * read during the call: runs of 32-row tiles in which EVERY tile needs the one table `table` (0 = h_s2t, 1 = h_t2s) -- by
- * tile_need_opt (value 1 << table) or by lying inside that table's tail group.  The caller vouches for that; it decides the runs once
- * per graph.  Inside a run the stream kernel's two 4-wave teams both hold the needed table's columns and take a block's tiles in
- * turn (csrc/bgnn_transform_stream.hip).  Outputs are bit for bit those of the entries above.  A run that gives some block of
- * the launch fewer than 4 tiles, or a shape the stream kernel does not take at 256 packed columns, is ignored; so are all runs
- * with BGNN_TS_TEAMS=0 in the environment (read once). */
-int bgnn_adaptedconv_transform_need2_f32(const float* x, int64_t N, int32_t Din, int64_t ldx,
-                                         const uint8_t* mask, const double* sums,
-                                         int32_t n_heads, int32_t D, const float* Wp, const float* bias_p,
-                                         const float* gates, const float* gate_const_opt,
-                                         float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1,
-                                         int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
-                                         const int32_t* tile_need_opt, const int64_t* team_runs_host_opt, int32_t n_team_runs,
-                                         float* small_ws, void* stream);
+                                   int64_t ldh, int64_t row_stride, int64_t n_tail_t2s, int64_t n_tail_s2t,
+                                   const int32_t* tile_need_opt, const int64_t* team_runs_host_opt, int32_t n_team_runs,
+                                   float* small_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a11-a13) fused GATv2 logits + per-destination softmax + weighted neighbour sum.

@@ -326,7 +326,7 @@ def test_library_exports_the_new_symbols_and_refuses_shapes_outside_the_envelope
     for n in ("bgnn_gatv2_aggregate_workspace_bytes", "bgnn_gatv2_aggregate_f32", "bgnn_gatv2_aggregate_bwd_f32"):
         assert hasattr(raw, n) and n in _lib.SIGNATURES
     lib = _lib.lib()
-    assert lib.bgnn_version() == 114
+    assert lib.bgnn_version() == 115
     assert lib.bgnn_gatv2_aggregate_workspace_bytes(100, 10, 2, 8) >= 2 * 100 * 2 * 4 + 10 * 2 * 4 + 2 * 8 * 4
     buf = np.zeros(64, np.float32)
     P = ctypes.c_void_p(buf.ctypes.data)

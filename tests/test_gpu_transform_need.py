@@ -1,4 +1,4 @@
-"""GPU: the need-mask transform (bgnn_adaptedconv_transform_need_f32, `ops.adaptedconv_transform(..., tile_need=...)`) at its own
+"""GPU: the need-mask transform (bgnn_adaptedconv_transform_f32 with tile_need_opt, `ops.adaptedconv_transform(..., tile_need=...)`) at its own
 interface: a table's rows in a tile whose need bit is set are bit-equal to the unmasked call, rows of a tile whose bit is clear
 are either untouched or exactly the unmasked value, guard rows stay untouched, and the unmasked call meets the default bar
 against fp64 (the restatement of tests/test_gpu_classifier_stage.py, itself checked against the C oracle there)."""
@@ -81,3 +81,49 @@ def test_need_mask_outside_the_stream_envelope_writes_both_tables(din, D, n):
         for t in range(2):
             assert torch.equal(got[t].view(torch.int32), full[t].view(torch.int32)), f"need {v}, table {t}"
             assert untouched(got[t][n:])
+
+
+def test_transform_entry_contract():
+    """The one C entry at its own interface (N = 33, Din = 64, D = 32): the argument checks that sit in front of any launch --
+    both or neither of delta_opt / sums_opt, a misaligned delta_opt, a need mask together with a tail, three team runs -- and one
+    valid call per form whose tables equal those of `ops.adaptedconv_transform` bit for bit."""
+    import ctypes
+
+    from bridged_gnn_amd import _lib as L
+    from bridged_gnn_amd import ops
+    E_NULL, E_SHAPE, E_ALIGN = -1, -2, -4
+    n, din, D = 33, 64, 32
+    x, m, head, sums, packed, g = _setup(din, D, n, seed=115)
+    Wp, bp, gates, _, ldh, gconst = packed
+    x, m8, sums = x.to(DEV), m.to(DEV, torch.uint8), sums.to(DEV)
+    delta = ops.domain_delta(sums, din)
+    odd = torch.zeros(din + 4, dtype=torch.float32, device=DEV)[1:din + 1]          # 4 bytes past a 16-byte boundary
+    need = torch.full(((n + 31) // 32,), 3, dtype=torch.int32, device=DEV)
+    runs = (ctypes.c_int64 * 9)(0, 1, 0, 1, 2, 1, 0, 0, 0)
+    small = torch.empty(2 * ldh + 2 + 8, dtype=torch.float32, device=DEV)
+    lib = L.lib()
+
+    def call(delta_t, sums_t, tails=(0, 0), need_t=None, runs_p=None, n_runs=0):
+        h_t2s, h_s2t = sentinel(n + GUARD, ldh), sentinel(n + GUARD, ldh)
+        rc = lib.bgnn_adaptedconv_transform_f32(
+            L.ptr(x), n, din, x.stride(0), L.ptr(m8), None if delta_t is None else ctypes.c_void_p(delta_t.data_ptr()), L.ptr(sums_t),
+            1, D, L.ptr(Wp), L.ptr(bp), L.ptr(gates), L.ptr(gconst), L.ptr_rows(h_s2t), L.ptr_rows(h_t2s), None, None, ldh, ldh,
+            tails[0], tails[1], L.ptr(need_t), runs_p, n_runs, L.ptr(small), L.stream())
+        torch.cuda.synchronize()
+        return rc, h_t2s, h_s2t
+
+    for what, want, kw in (("both delta_opt and sums_opt", E_NULL, dict(delta_t=delta, sums_t=sums)),
+                           ("neither delta_opt nor sums_opt", E_NULL, dict(delta_t=None, sums_t=None)),
+                           ("misaligned delta_opt", E_ALIGN, dict(delta_t=odd, sums_t=None)),
+                           ("tile_need_opt with a tail", E_SHAPE, dict(delta_t=None, sums_t=sums, tails=(0, 1), need_t=need)),
+                           ("n_team_runs = 3", E_SHAPE, dict(delta_t=None, sums_t=sums, runs_p=runs, n_runs=3))):
+        rc, h_t2s, h_s2t = call(**kw)
+        assert rc == want, f"{what}: returned {rc}, expected {want}"
+        assert untouched(h_t2s) and untouched(h_s2t), f"{what}: a table was written"
+    for what, kw, okw in (("delta form", dict(delta_t=delta, sums_t=None), dict(delta=delta)),
+                          ("sums form", dict(delta_t=None, sums_t=sums), dict(delta=None, sums=sums))):
+        rc, h_t2s, h_s2t = call(**kw)
+        assert rc == 0, f"{what}: returned {rc}"
+        (o_t2s, o_s2t), = ops.adaptedconv_transform(x, m8, okw.pop("delta"), packed, **okw)
+        assert torch.equal(h_t2s[:n], o_t2s) and torch.equal(h_s2t[:n], o_s2t), f"{what}: tables differ from ops.adaptedconv_transform"
+        assert untouched(h_t2s[n:]) and untouched(h_s2t[n:]), f"{what}: guard rows written"
