@@ -24,4 +24,7 @@ def __getattr__(name):
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)
+    if name in ("PartitionedGAT", "GatPartition"):     # the GAT baseline on a node partition, likewise
+        from . import dist_gat
+        return getattr(dist_gat, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -192,9 +192,10 @@ struct RowParams {
   uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_dev;
   float* g; int64_t ldg;
   float* r;                                        // [n_rows, H]
+  const int64_t* row_id;                           // ROW_ID: dropout row of row i (a rank's rows of a partition); NULL: row i itself
 };
 
-template <int LF, int EPI>
+template <int LF, int EPI, bool ROW_ID = false>
 static __global__ __launch_bounds__(256) void attn_bwd_rows_kernel(RowParams p) {
   constexpr int RPB = 256 / LF;
   const int q = threadIdx.x / LF;
@@ -214,7 +215,7 @@ static __global__ __launch_bounds__(256) void attn_bwd_rows_kernel(RowParams p) 
     load4(p.gy + i * p.ldgy + hoff, k0, p.C, vec, valid, dy);
     if (p.bias != nullptr) load4(p.bias + hoff, k0, p.C, vec, true, b);
     if (EPI == EPI_ELU) {
-      const uint64_t e = (uint64_t)i * (uint64_t)(p.H * p.C) + (uint64_t)(hoff + k0);
+      const uint64_t e = (uint64_t)(ROW_ID ? (valid ? p.row_id[i] : 0) : i) * (uint64_t)(p.H * p.C) + (uint64_t)(hoff + k0);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         // the mask is redrawn, never read off y: ELU is 0 at a pre-activation of exactly 0, kept or not
@@ -314,18 +315,20 @@ int dispatch_bwd_rows(int epilogue, const BwdRowsParams& p, hipStream_t st) {
   });
 }
 
-template <int LF, int EPI>
+template <int LF, int EPI, bool ROW_ID = false>
 int launch_rows(const RowParams& p, hipStream_t st) {
   constexpr int RPB = 256 / LF;
   int64_t grid = (p.n_rows * p.H + RPB - 1) / RPB;
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((attn_bwd_rows_kernel<LF, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((attn_bwd_rows_kernel<LF, EPI, ROW_ID>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
 
 inline int dispatch_rows(int epilogue, const RowParams& p, hipStream_t st) {
+  if (epilogue == EPI_ELU && p.row_id != nullptr && p.thr != 0u)   // the ids matter only where the mask is redrawn
+    return lf_ladder((p.C + 3) / 4, [&](auto LF, auto, auto) { return launch_rows<LF, EPI_ELU, true>(p, st); });
   return epi_switch(epilogue, [&](auto EPI) {
     return lf_ladder((p.C + 3) / 4, [&](auto LF, auto, auto) { return launch_rows<LF, EPI>(p, st); });
   });

@@ -1112,6 +1112,23 @@ def _seed_args(seed, seed_dev):
     return int(seed) & 0xFFFFFFFFFFFFFFFF, (L.ptr(seed_dev) if seed_dev is not None else None)
 
 
+def _gat_ids_paired(row_ids, edge_base, what):
+    """both ids or neither: checked before anything else, a half-given pair is a caller's mistake on any device"""
+    if (row_ids is None) != (edge_base is None):
+        raise ValueError(f"{what}: row_ids and edge_base are given together (a rank's rows need the global positions of both masks)")
+
+
+def _gat_ids(row_ids, edge_base, n_rows, dev, what):
+    """the id pair of the `_rows` entry points: int64, contiguous, [n_rows], on the table's device -> given?"""
+    if row_ids is None:
+        return False
+    for t, name in ((row_ids, "row_ids"), (edge_base, "edge_base")):
+        _gat_need(t, name, (n_rows,), torch.int64)
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} must be on the table's device {dev} (got {t.device})")
+    return True
+
+
 def gat_scores(tbl, att_src, att_dst, H, C):
     """s_src[n,h] = <tbl[n,h,:], att_src[h,:]>, s_dst likewise (models/backbones.py:404-438 -> GATConv's alpha_src / alpha_dst;
     bgnn.h: bgnn_gat_scores_f32) -> two float32 [N, H] in one read of tbl [N, >= pad4(H*C)].  att_*: float32 with H*C elements."""
@@ -1133,14 +1150,19 @@ def gat_scores(tbl, att_src, att_dst, H, C):
 
 
 def gat_aggregate(tbl, s_src, s_dst, rowptr, col, n_rows, H, C, bias=None, negative_slope=0.2, p_att=0.0, seed_att=0,
-                  seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_pre=False, return_alpha=False):
+                  seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_pre=False, return_alpha=False, row_ids=None,
+                  edge_base=None):
     """GAT attention aggregation (models/backbones.py:404-438, bgnn.h: bgnn_gat_aggregate_f32) over a CSR that holds one self loop per
     row (`build_dst_csr(rewrite_self_loops=True)`): out[i,h,:] = epi(sum_t a~[t,h] * tbl[col[t],h,:] + bias[h,:]) with
     a~ = softmax_t(leaky_relu(s_src[col[t],h] + s_dst[i,h])) * m[t,h], m the attention-dropout mask at p_att (element t*H + h of the
     counter hash, seed_att + seed_att_dev).  epilogue: None, "elu" (then dropout at p_drop, seed + seed_dev, element
     i*(H*C) + column) or "log_softmax" (H == 1).  bias: float32 [>= H*C], 16-byte aligned, or None.
     -> (out [n_rows, pad4(H*C)], state [n_rows, H, 2] = (max, denominator), pre | None, alpha | None): pre (want_pre) is the conv
-    output before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order."""
+    output before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order.
+    row_ids, edge_base: int64 [n_rows] each, given together (a rank's rows of a partition, bgnn_gat_aggregate_rows_f32): the GLOBAL
+    id of every output row and the position of its first edge in the whole graph's CSR; the masks are then hashed at
+    row_ids[i]*(H*C) + column and (edge_base[i] + (t - rowptr[i]))*H + h, those of the whole-graph call.  None: row i, edge t."""
+    _gat_ids_paired(row_ids, edge_base, "gat_aggregate")
     H, C = _gat_check(tbl, H, C, "gat_aggregate")
     n_rows, E = int(n_rows), int(col.shape[0])
     dev = tbl.device
@@ -1152,6 +1174,7 @@ def gat_aggregate(tbl, s_src, s_dst, rowptr, col, n_rows, H, C, bias=None, negat
     _gat_need(s_dst, "s_dst", (n_rows, H))
     _gat_need(rowptr, "rowptr", (n_rows + 1,), torch.int32)
     _gat_need(col, "col", (E,), torch.int32)
+    ids = _gat_ids(row_ids, edge_base, n_rows, dev, "gat_aggregate")
     _gat_need_seed_word(seed_att_dev, "seed_att_dev")
     _gat_need_seed_word(seed_dev, "seed_dev")
     if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
@@ -1166,52 +1189,71 @@ def gat_aggregate(tbl, s_src, s_dst, rowptr, col, n_rows, H, C, bias=None, negat
     pre_arg = pre if (pre is not None and pre is not out) else None
     sa, sad = _seed_args(seed_att, seed_att_dev)
     sf, sfd = _seed_args(seed, seed_dev)
-    rc = L.lib().bgnn_gat_aggregate_f32(
-        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows,
-        H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(state), L.ptr(alpha),
-        None, 0, L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_gat_aggregate_f32")
+    head = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E,
+            n_rows, H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd)
+    tail = (L.ptr(state), L.ptr(alpha), None, 0, L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0,
+            L.ptr_rows(out), out.stride(0), L.stream())
+    if ids:
+        rc = L.lib().bgnn_gat_aggregate_rows_f32(*head, L.ptr(row_ids), L.ptr(edge_base), *tail)
+        L.check(rc, "bgnn_gat_aggregate_rows_f32")
+    else:
+        rc = L.lib().bgnn_gat_aggregate_f32(*head, *tail)
+        L.check(rc, "bgnn_gat_aggregate_f32")
     return out, state, pre, (alpha if return_alpha else None)
 
 
 def gat_aggregate_bwd(tbl, s_src, s_dst, state, alpha, pre, grad_y, rowptr, col, t_rowptr, t_eid, t_dst, H, C, bias=None,
                       negative_slope=0.2, p_att=0.0, seed_att=0, seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None,
-                      want_bias=True):
+                      want_bias=True, n_rows=None, row_ids=None, edge_base=None):
     """Backward of `gat_aggregate` (bgnn.h: bgnn_gat_aggregate_bwd_f32) from what the forward returned (state, alpha with
     return_alpha, pre with want_pre) and grad_y [N, >= pad4(H*C)] -> (grad_tbl [N, pad4(H*C)] = the gather part of dL/dtbl,
     ds_src [N, H], ds_dst [N, H], grad_bias [H*C] | None).  The caller adds ds_src (x) att_src + ds_dst (x) att_dst to grad_tbl and
-    forms the att gradients.  (t_rowptr, t_eid, t_dst) = `DstCSR.transposed()`.  Three launches, no atomics: bit-identical runs."""
+    forms the att gradients.  (t_rowptr, t_eid, t_dst) = `DstCSR.transposed()`.  Three launches, no atomics: bit-identical runs.
+    n_rows: the destination rows when the table holds more sources than that (a rank's extended graph: N = tbl rows = n_ext
+    sources, the first n_rows of them the owned rows).  Then s_dst, state, pre, grad_y and rowptr ([n_rows + 1]) are over n_rows,
+    s_src and t_rowptr ([N + 1]) over N, and the results are grad_tbl [N, .], ds_src [N, H], ds_dst [n_rows, H].  None: N.
+    row_ids, edge_base: as in `gat_aggregate` (bgnn_gat_aggregate_bwd_rows_f32): both masks are redrawn at the global positions."""
+    _gat_ids_paired(row_ids, edge_base, "gat_aggregate_bwd")
     H, C = _gat_check(tbl, H, C, "gat_aggregate_bwd")
     N, E = int(tbl.shape[0]), int(col.shape[0])
+    R = N if n_rows is None else int(n_rows)
+    if not 0 <= R <= N:
+        raise ValueError(f"gat_aggregate_bwd: n_rows = {R} must lie in [0, {N}] (the table's rows are the sources)")
     dev = tbl.device
     W = pad4(H * C)
-    for t, what in ((s_src, "s_src"), (s_dst, "s_dst")):
-        _gat_need(t, what, (N, H))
-    _gat_need(state, "state", (N, H, 2))
+    _gat_need(s_src, "s_src", (N, H))
+    _gat_need(s_dst, "s_dst", (R, H))
+    _gat_need(state, "state", (R, H, 2))
     _gat_need(alpha, "alpha", (E, H))
-    _gat_need_rows(pre, "pre", N, W)
-    _gat_need_rows(grad_y, "grad_y", N, W)
-    for t, what, n in ((rowptr, "rowptr", N + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
+    _gat_need_rows(pre, "pre", R, W)
+    _gat_need_rows(grad_y, "grad_y", R, W)
+    for t, what, n in ((rowptr, "rowptr", R + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
         _gat_need(t, what, (n,), torch.int32)
+    ids = _gat_ids(row_ids, edge_base, R, dev, "gat_aggregate_bwd")
     if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
         raise ValueError("bias must be float32 [>= H*C]")
     _gat_need_seed_word(seed_att_dev, "seed_att_dev")
     _gat_need_seed_word(seed_dev, "seed_dev")
     lib = L.lib()
-    g = torch.empty(N, W, dtype=torch.float32, device=dev)
+    g = torch.empty(R, W, dtype=torch.float32, device=dev)
     grad_tbl = torch.empty(N, W, dtype=torch.float32, device=dev)
     ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-    ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-    wsb = int(lib.bgnn_gat_aggregate_workspace_bytes(E, N, H))
+    ds_dst = torch.empty(R, H, dtype=torch.float32, device=dev)
+    wsb = int(lib.bgnn_gat_aggregate_workspace_bytes(E, R, H))
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
     sa, sad = _seed_args(seed_att, seed_att_dev)
     sf, sfd = _seed_args(seed, seed_dev)
-    rc = lib.bgnn_gat_aggregate_bwd_f32(
-        L.ptr_rows(tbl), tbl.stride(0), N, L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(state), L.ptr(alpha), L.ptr_rows(pre),
-        pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E,
-        N, H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws), ws.numel(),
-        L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(ds_src), L.ptr(ds_dst), L.stream())
-    L.check(rc, "bgnn_gat_aggregate_bwd_f32")
+    head = (L.ptr_rows(tbl), tbl.stride(0), N, L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(state), L.ptr(alpha), L.ptr_rows(pre),
+            pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst),
+            E, R, H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws),
+            ws.numel())
+    tail = (L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(ds_src), L.ptr(ds_dst), L.stream())
+    if ids:
+        rc = lib.bgnn_gat_aggregate_bwd_rows_f32(*head, L.ptr(row_ids), L.ptr(edge_base), *tail)
+        L.check(rc, "bgnn_gat_aggregate_bwd_rows_f32")
+    else:
+        rc = lib.bgnn_gat_aggregate_bwd_f32(*head, *tail)
+        L.check(rc, "bgnn_gat_aggregate_bwd_f32")
     return grad_tbl, ds_src, ds_dst, (column_sums(g)[:H * C] if want_bias else None)
 
 

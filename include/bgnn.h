@@ -37,7 +37,8 @@ extern "C" {
  * bgnn_gcn_aggregate_rows_f32, and for the GAT baseline's bgnn_gat_scores_f32, bgnn_gat_aggregate_f32, bgnn_gat_aggregate_bwd_f32 and
  * their workspace size (added after 114 without changing it), and for the GATv2 baseline's bgnn_gatv2_aggregate_f32,
  * bgnn_gatv2_aggregate_bwd_f32 and their workspace size (likewise), and for bgnn_adaptedconv_aggregate_queued_f32 with
- * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue).
+ * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue), and for partitioned
+ * GAT's bgnn_gat_aggregate_rows_f32 and bgnn_gat_aggregate_bwd_rows_f32 (added after 115 without changing it).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
  * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone.
@@ -582,7 +583,11 @@ int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, co
  * t_eid = the edge's position in the by-destination order, t_dst = its destination: `DstCSR.transposed()`) forms
  * grad_tbl[j,h,:] = sum a~ * g[i,h,:] and ds_src[j,h] = sum dz.  The caller finishes: grad_bias = column sums of g,
  * grad_tbl += ds_src (x) att_src + ds_dst (x) att_dst, grad_att_src[h,:] = sum_n ds_src[n,h] * tbl[n,h,:] (att_dst likewise).
- * n_src == n_rows here (self loops make every node both); deterministic bits.  A row's edge range is cut to [0, n_edges] and ids are
+ * Rows and sources are counted separately: n_rows destination rows (rowptr [n_rows+1]; s_dst, state, pre, grad_y, g and ds_dst are
+ * over n_rows, and so is the workspace: bgnn_gat_aggregate_workspace_bytes(n_edges, n_rows, H)) and n_src >= n_rows source rows
+ * (tbl, s_src, grad_tbl and ds_src are over n_src, t_rowptr is [n_src+1]); every id in col is < n_src, every id in t_dst < n_rows.
+ * On a whole graph n_src == n_rows (self loops make every node both); a rank's extended graph of a partition has its halo slots
+ * as further sources without in-edges.  Deterministic bits.  A row's edge range is cut to [0, n_edges] and ids are
  * checked against their tables: a malformed CSR gives a wrong sum, never a stray access.  The entry points are defined in
  * csrc/bgnn_gat.hip next to their kernels. */
 int bgnn_gat_scores_f32(const float* tbl, int64_t ldt, int64_t n, int32_t H, int32_t C, const float* att_src,
@@ -602,6 +607,30 @@ int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, con
                                const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
                                const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
                                float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, void* stream);
+/* bgnn_gat_aggregate_rows_f32 / bgnn_gat_aggregate_bwd_rows_f32: the two entries above for a block of rows of a larger graph (a
+ * rank's rows of a destination-node partition: tbl and s_src cover the rank's own rows followed by its halo rows, n_src = n_ext in
+ * the backward).  Both masks are then drawn where the whole-graph call draws them: row_id_opt [n_rows] (int64) is every row's
+ * GLOBAL id, the feature-dropout element index becomes row_id[i]*(H*C) + h*C + c; edge_base_opt [n_rows] (int64) is the position
+ * of the row's first edge in the WHOLE graph's by-destination CSR, the attention-dropout element index of edge t of row i becomes
+ * (edge_base[i] + (t - rowptr[i])) * H + h -- a rank's rows must keep the whole graph's edge order inside a row.  The backward
+ * redraws both masks from the same ids.  The ids feed the hash only and never form an address.  With both pointers NULL (or no
+ * dropout) these are bgnn_gat_aggregate_f32 / bgnn_gat_aggregate_bwd_f32, bit for bit and kernel for kernel. */
+int bgnn_gat_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s_src, const float* s_dst,
+                                const float* bias_opt, const int32_t* rowptr, const int32_t* col, int64_t n_edges,
+                                int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                                const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
+                                float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes, float* pre_out_opt, int64_t ldp,
+                                float* out, int64_t ldo, void* stream);
+int bgnn_gat_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
+                                    const float* bias_opt, const float* state, const float* alpha, const float* pre, int64_t ldp,
+                                    const float* grad_y, int64_t ldgy, const int32_t* rowptr, const int32_t* col,
+                                    const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges,
+                                    int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                                    const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                    const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id_opt,
+                                    const int64_t* edge_base_opt, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
+                                    float* ds_src, float* ds_dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GATv2 attention conv (the `gnn='GATv2'` baseline of main_graph_knowledge_transfer.py:329-330):
