@@ -27,4 +27,7 @@ def __getattr__(name):
     if name in ("PartitionedGAT", "GatPartition"):     # the GAT baseline on a node partition, likewise
         from . import dist_gat
         return getattr(dist_gat, name)
+    if name == "PartitionedGATv2":                     # the GATv2 baseline on the same partition
+        from . import dist_gatv2
+        return dist_gatv2.PartitionedGATv2
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

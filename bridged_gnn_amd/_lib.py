@@ -126,6 +126,11 @@ SIGNATURES = {
     "bgnn_gatv2_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32,
                                              _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ, _P, _I64, _P, _I64,
                                              _P, _P]),
+    "bgnn_gatv2_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,
+                                              _INT, _F32, C.c_uint64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "bgnn_gatv2_aggregate_bwd_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64,
+                                                  _I32, _I32, _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ, _P, _P,
+                                                  _P, _I64, _P, _I64, _P, _P]),
     "bgnn_step2_loss_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_step2_loss_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, C.c_double, _P, _P, _SZ, _P]),
     "bgnn_step2_loss_bwd_f32": (_INT, [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),

@@ -31,6 +31,14 @@
 //             walks head by head), is reduced over the block in a fixed order and written to the block's partial row.
 //   datt      adds the blocks' partial rows in a fixed order (a block per column).
 //   by-src    over (t_rowptr, t_eid, t_dst): gathers g_i and xr_i, dXL[j,h,:] = sum_u coef * g_i + de * att (.) leaky'(xl_j + xr_i).
+// Rows of a larger graph (bgnn_gatv2_aggregate_rows_f32 / bgnn_gatv2_aggregate_bwd_rows_f32, a rank's rows of a node partition): both
+// masks are functions of a position, and a rank's local positions are not the whole graph's.  The IDS forward hashes the feature
+// mask at row_id[i] * (H*C) + column and the attention mask at (edge_base[i] + (t - rowptr[i])) * H + h: the row's GLOBAL id and the
+// GLOBAL position of its first edge, both read once per virtual row; the ids feed the hash only, never an address.  The backward
+// takes n_rows destination rows and n_src >= n_rows source rows (a rank's extended graph: its halo slots are sources without
+// in-edges): the ROWS by-destination pass checks neighbour ids against n_src and redraws the attention mask at the global
+// position, the ROWS by-source pass walks n_src sources and leaves the x_r half of the rows n_rows .. n_src as 0; the shared row
+// pass takes row_id.  The plain entries launch the instantiations without the flags.
 // Ids outside their table are never dereferenced and a row's edge range is cut to the edge arrays: a malformed CSR (ids or rowptr)
 // gives a wrong sum, not a stray read or write.
 #include "bgnn_conv_common.h"
@@ -67,9 +75,11 @@ struct FwdParams {
   float* alpha;                                                  // [E', H] post-dropout coefficients, or NULL
   float* pre; int64_t ldp;                                       // the conv output before the epilogue, or NULL
   float* out; int64_t ldo;
+  const int64_t* row_id;                                         // IDS: dropout row of row i (element index row_id[i] * (H*C) + column)
+  const int64_t* edge_base;                                      // IDS: position of the row's first edge in the whole graph's CSR
 };
 
-template <int LF, int EP, int U, int EPI>
+template <int LF, int EP, int U, int EPI, bool IDS = false>
 __global__ __launch_bounds__(256) void gatv2_fwd_kernel(FwdParams p) {
   constexpr int GL = LF * EP;
   constexpr int GPW = 64 / GL;
@@ -98,6 +108,8 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(FwdParams p) {
     const int64_t hoff = (int64_t)h * p.C;
     int32_t beg = 0, end = 0;
     if (valid) { beg = p.rowptr[i]; end = p.rowptr[i + 1]; }
+    int64_t eshift = 0, drow = 0;                               // IDS: hashed position of edge e = e + eshift (raw rowptr[i]); dropout row
+    if (IDS && valid) { eshift = p.edge_base[i] - (int64_t)beg; drow = p.row_id[i]; }
     clamp_row(beg, end, p.n_edges);
     const int32_t niter = (end - beg + EP * U - 1) / (EP * U);  // uniform inside the group
     float xr[4], att[4];
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(FwdParams p) {
         if (!ok[u]) continue;
         const int32_t e = e0 + u * EP;
         const float ev = lg_e[u];
-        const uint64_t el = (uint64_t)e * (uint64_t)p.H + (uint64_t)h;
+        const uint64_t el = (IDS ? (uint64_t)((int64_t)e + eshift) : (uint64_t)e) * (uint64_t)p.H + (uint64_t)h;
         const float mk = p.athr == 0u ? 1.f : (drop_bits(el, aseed) >= p.athr ? p.akeep : 0.f);
         if (p.alpha != nullptr && k0 == 0) p.alpha[(int64_t)e * p.H + h] = ev;     // parked: the sweep below turns it into a~
         float w;
@@ -183,7 +195,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(FwdParams p) {
         float a = 0.f;
         if (j >= 0 && (int64_t)j < p.n_tbl) {
           a = expf(p.alpha[(int64_t)e * p.H + h] - mx) / den;
-          const uint64_t el = (uint64_t)e * (uint64_t)p.H + (uint64_t)h;
+          const uint64_t el = (IDS ? (uint64_t)((int64_t)e + eshift) : (uint64_t)e) * (uint64_t)p.H + (uint64_t)h;
           if (p.athr != 0u) a = drop_bits(el, aseed) >= p.athr ? a * p.akeep : 0.f;
         }
         p.alpha[(int64_t)e * p.H + h] = a;
@@ -208,7 +220,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(FwdParams p) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] = o[c] > 0.f ? o[c] : expm1f(o[c]);
       if (p.thr != 0u)
-        drop4(o, (uint64_t)i * (uint64_t)(p.H * p.C) + (uint64_t)(hoff + k0), vec, seed, p.thr, p.keep_scale);
+        drop4(o, (uint64_t)(IDS ? drow : i) * (uint64_t)(p.H * p.C) + (uint64_t)(hoff + k0), vec, seed, p.thr, p.keep_scale);
     } else if (EPI == EPI_LOGSOFTMAX) {
       log_softmax4<LF>(o, k0, p.C);   // H == 1: the whole row (C <= 4*LF) sits in the LF lanes of the group
     }
@@ -233,9 +245,11 @@ struct DstParams {
   float* de; float* coef;                          // [E', H] each
   float* grad_tbl; int64_t ldgt;                   // dXR goes to columns [xr_off, xr_off + H*C)
   float* part;                                     // [gridDim.x, H*C] partial rows of datt
+  int64_t n_src;                                   // ROWS: rows of tbl (the sources), >= n_rows
+  const int64_t* edge_base;                        // ROWS: as FwdParams, or NULL (edge t is hashed at t)
 };
 
-template <int LF, int EP, int U>
+template <int LF, int EP, int U, bool ROWS = false>
 __global__ __launch_bounds__(256) void gatv2_bwd_dst_kernel(DstParams p) {
   constexpr int GL = LF * EP;
   constexpr int GPW = 64 / GL;
@@ -275,6 +289,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_dst_kernel(DstParams p) {
         beg = p.rowptr[i]; end = p.rowptr[i + 1];
         mx = p.state[2 * v]; den = p.state[2 * v + 1]; rr = p.r[v];
       }
+      int64_t eshift = 0;                                       // ROWS: hashed position of edge e = e + eshift (raw rowptr[i])
+      if (ROWS && valid && p.edge_base != nullptr) eshift = p.edge_base[i] - (int64_t)beg;
       clamp_row(beg, end, p.n_edges);
       const int32_t niter = (end - beg + EP * U - 1) / (EP * U);  // uniform inside the group
       float dxr[4] = {0.f, 0.f, 0.f, 0.f};
@@ -290,7 +306,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_dst_kernel(DstParams p) {
         bool ok[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          ok[u] = nid[u] >= 0 && (int64_t)nid[u] < p.n_rows;
+          ok[u] = nid[u] >= 0 && (int64_t)nid[u] < (ROWS ? p.n_src : p.n_rows);
           float x[4];
           load4(p.tbl + (int64_t)(ok[u] ? nid[u] : 0) * p.ldt + hoff, k0, p.C, vec, ok[u], x);
           lg_e[u] = logit_part(x, xr, att, p.slope, m[u]);
@@ -317,7 +333,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_dst_kernel(DstParams p) {
             continue;
           }
           const float alpha = den > 0.f ? expf(lg_e[u] - mx) / den : 0.f;
-          const uint64_t el = (uint64_t)e * (uint64_t)p.H + (uint64_t)h;
+          const uint64_t el = (ROWS ? (uint64_t)((int64_t)e + eshift) : (uint64_t)e) * (uint64_t)p.H + (uint64_t)h;
           const float mk = p.athr == 0u ? 1.f : (drop_bits(el, aseed) >= p.athr ? p.akeep : 0.f);
           const float dev = alpha * (mk * dot[u] - rr);
           if (k0 == 0) {
@@ -385,9 +401,10 @@ struct SrcParams {
   float slope;
   const float* de; const float* coef;              // [E', H] each, by-destination order
   float* grad_tbl; int64_t ldgt;                   // dXL goes to columns [0, H*C)
+  int64_t n_src;                                   // ROWS: the sources walked, >= n_rows (g and x_r are read of rows < n_rows only)
 };
 
-template <int LF, int EP, int U>
+template <int LF, int EP, int U, bool ROWS = false>
 __global__ __launch_bounds__(256) void gatv2_bwd_src_kernel(SrcParams p) {
   constexpr int GL = LF * EP;
   constexpr int GPW = 64 / GL;
@@ -400,7 +417,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_src_kernel(SrcParams p) {
   const int k0 = (lg % LF) * 4;
   const bool vec = (p.C & 3) == 0;
 
-  const int64_t nv = p.n_rows * p.H;
+  const int64_t nv = (ROWS ? p.n_src : p.n_rows) * p.H;
   const int64_t ntiles = (nv + RPB - 1) / RPB;
   const bgnn::XcdRange tr = bgnn::xcd_pos_range(ntiles);
   for (int64_t pos = tr.begin; pos < tr.end; pos += tr.step) {
@@ -462,49 +479,57 @@ __global__ __launch_bounds__(256) void gatv2_bwd_src_kernel(SrcParams p) {
       store4(p.grad_tbl + j * p.ldgt + hoff, k0, p.C, vec, acc);
       if (h == p.H - 1 && lg == 0)
         for (int q = 0; q < p.npad; ++q) p.grad_tbl[j * p.ldgt + (int64_t)p.H * p.C + q] = 0.f;
+      if (ROWS && j >= p.n_rows) {                                // a source that is no destination row: its dXR half leaves as 0
+        const float z[4] = {0.f, 0.f, 0.f, 0.f};
+        store4(p.grad_tbl + j * p.ldgt + p.xr_off + hoff, k0, p.C, vec, z);
+        if (h == p.H - 1 && lg == 0)
+          for (int q = 0; q < p.npad; ++q) p.grad_tbl[j * p.ldgt + p.xr_off + (int64_t)p.H * p.C + q] = 0.f;
+      }
     }
   }
 }
 
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------
-template <int LF, int EP, int U, int EPI>
+template <int LF, int EP, int U, int EPI, bool IDS>
 int launch_fwd(const FwdParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
   static int cap = 0;
   const int64_t ntiles = (p.n_rows * p.H + RPB - 1) / RPB;
-  const int grid = persistent_grid(gatv2_fwd_kernel<LF, EP, U, EPI>, ntiles, &cap);
-  hipLaunchKernelGGL((gatv2_fwd_kernel<LF, EP, U, EPI>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  const int grid = persistent_grid(gatv2_fwd_kernel<LF, EP, U, EPI, IDS>, ntiles, &cap);
+  hipLaunchKernelGGL((gatv2_fwd_kernel<LF, EP, U, EPI, IDS>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
 
+template <bool IDS>
 int dispatch_fwd(int epilogue, const FwdParams& p, hipStream_t st) {
   // four neighbour rows in flight on every rung (the ladder's U is not taken): each carries its logit beside its four columns
   return epi_switch(epilogue, [&](auto EPI) {
-    return lf_ladder((p.C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_fwd<LF, EP, 4, EPI>(p, st); });
+    return lf_ladder((p.C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_fwd<LF, EP, 4, EPI, IDS>(p, st); });
   });
 }
 
-template <int LF, int EP, int U>
+template <int LF, int EP, int U, bool ROWS>
 int launch_dst(DstParams p, hipStream_t st, int* grid_out) {
   constexpr int RPB = 4 * (64 / (LF * EP));
   static int cap = 0;
   const int64_t ntiles = (p.n_rows + RPB - 1) / RPB;
-  int grid = persistent_grid(gatv2_bwd_dst_kernel<LF, EP, U>, ntiles, &cap);
+  int grid = persistent_grid(gatv2_bwd_dst_kernel<LF, EP, U, ROWS>, ntiles, &cap);
   if (grid > DATT_BLOCKS) grid = DATT_BLOCKS;                   // a multiple of 8 as well
   *grid_out = grid;
-  hipLaunchKernelGGL((gatv2_bwd_dst_kernel<LF, EP, U>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL((gatv2_bwd_dst_kernel<LF, EP, U, ROWS>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
 
-template <int LF, int EP, int U>
+template <int LF, int EP, int U, bool ROWS>
 int launch_src(const SrcParams& p, hipStream_t st) {
   constexpr int RPB = 4 * (64 / (LF * EP));
   static int cap = 0;
-  const int64_t ntiles = (p.n_rows * p.H + RPB - 1) / RPB;
-  const int grid = persistent_grid(gatv2_bwd_src_kernel<LF, EP, U>, ntiles, &cap);
-  hipLaunchKernelGGL((gatv2_bwd_src_kernel<LF, EP, U>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  const int64_t ntiles = ((ROWS ? p.n_src : p.n_rows) * p.H + RPB - 1) / RPB;
+  const int grid = persistent_grid(gatv2_bwd_src_kernel<LF, EP, U, ROWS>, ntiles, &cap);
+  hipLaunchKernelGGL((gatv2_bwd_src_kernel<LF, EP, U, ROWS>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
@@ -515,20 +540,14 @@ size_t rows_bytes(int64_t n_rows, int32_t H) { return bgnn_align_up((size_t)n_ro
 // the one table [rows, >= 2 * pad4(H*C)] with XL and XR: 16-byte aligned base, leading dimension a multiple of 4
 bool cat_ok(const float* t, int64_t ld, int32_t HC) { return bgnn_aligned16(t) && (ld & 3) == 0 && ld >= 2 * (((int64_t)HC + 3) / 4 * 4); }
 
-}  // namespace
-
-extern "C" size_t bgnn_gatv2_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H, int32_t C) {
-  if (n_edges < 0 || n_rows < 0 || !shape_ok(H, C)) return 0;
-  return 2 * coef_bytes(n_edges, H) + rows_bytes(n_rows, H) + part_bytes(H, C) + 16;
-}
-
-extern "C" int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
-                                        const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H,
-                                        int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                        const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                        const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, float* pre_out_opt,
-                                        int64_t ldp, float* out, int64_t ldo, void* stream) {
+// the ids matter only where a mask is drawn: without dropout the plain instantiations run
+int gatv2_aggregate(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt, const int32_t* rowptr,
+                    const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
+                    uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                    const uint64_t* seed_dev_opt, const int64_t* row_id, const int64_t* edge_base, float* state, float* alpha_out_opt,
+                    float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, hipStream_t st) {
   if (!tbl || !att || !rowptr || !col || !state || !out) return BGNN_E_NULL;
+  if ((row_id == nullptr) != (edge_base == nullptr)) return BGNN_E_NULL;      // the forward hashes both: given together
   if (n_rows < 0 || n_tbl < n_rows || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
   if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
   if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
@@ -545,19 +564,22 @@ extern "C" int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n
   drop_consts(p_drop, p.thr, p.keep_scale);
   p.seed = seed; p.seed_dev = seed_dev_opt;
   p.state = state; p.alpha = alpha_out_opt; p.pre = pre_out_opt; p.ldp = ldp; p.out = out; p.ldo = ldo;
-  return dispatch_fwd(epilogue, p, (hipStream_t)stream);
+  p.row_id = row_id; p.edge_base = edge_base;
+  if (row_id != nullptr && (p.athr != 0u || (epilogue == EPI_ELU && p.thr != 0u))) return dispatch_fwd<true>(epilogue, p, st);
+  return dispatch_fwd<false>(epilogue, p, st);
 }
 
-extern "C" int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att, const float* bias_opt, const float* state,
-                                            const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr,
-                                            const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                            int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
-                                            uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop,
-                                            uint64_t seed, const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g,
-                                            int64_t ldg, float* grad_tbl, int64_t ldgt, float* grad_att, void* stream) {
+int gatv2_aggregate_bwd(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt, const float* state,
+                        const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr, const int32_t* col,
+                        const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H,
+                        int32_t C, float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue,
+                        float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id,
+                        const int64_t* edge_base, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt, float* grad_att,
+                        hipStream_t st) {
   if (!tbl || !att || !state || !pre || !grad_y || !rowptr || !col || !t_rowptr || !t_eid || !t_dst || !ws || !g || !grad_tbl || !grad_att)
     return BGNN_E_NULL;
-  if (n_rows < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
+  if ((row_id == nullptr) != (edge_base == nullptr)) return BGNN_E_NULL;
+  if (n_rows < 0 || n_src < n_rows || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
   if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
   if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
   const int32_t HC = H * C;
@@ -569,15 +591,19 @@ extern "C" int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const
   float* coef = de + coef_bytes(n_edges, H) / sizeof(float);
   float* r = coef + coef_bytes(n_edges, H) / sizeof(float);
   float* part = r + rows_bytes(n_rows, H) / sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
   const int32_t P = (HC + 3) / 4 * 4, npad = P - HC;
-  if (n_rows == 0) return (int)hipMemsetAsync(grad_att, 0, (size_t)HC * sizeof(float), st);
+  if (n_rows == 0) {                                              // no destination row, so no edge: every gradient is 0
+    if (const hipError_t e = hipMemsetAsync(grad_att, 0, (size_t)HC * sizeof(float), st)) return (int)e;
+    if (n_src == 0) return 0;
+    return (int)hipMemset2DAsync(grad_tbl, (size_t)ldgt * sizeof(float), 0, (size_t)(2 * P) * sizeof(float), (size_t)n_src, st);
+  }
+  const bool ext = n_src != n_rows;
   {
     RowParams q{};
     q.pre = pre; q.ldp = ldp; q.gy = grad_y; q.ldgy = ldgy; q.bias = bias_opt; q.n_rows = n_rows; q.H = H; q.C = C; q.npad = npad;
     drop_consts(p_drop, q.thr, q.keep_scale);
     q.seed = seed; q.seed_dev = seed_dev_opt;
-    q.g = g; q.ldg = ldg; q.r = r;
+    q.g = g; q.ldg = ldg; q.r = r; q.row_id = row_id;
     if (const int rc = dispatch_rows(epilogue, q, st)) return rc;
   }
   {
@@ -587,14 +613,75 @@ extern "C" int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const
     att_drop_consts(p_att, d.athr, d.akeep);
     d.aseed = seed_att; d.aseed_dev = seed_att_dev_opt;
     d.de = de; d.coef = coef; d.grad_tbl = grad_tbl; d.ldgt = ldgt; d.part = part;
+    d.n_src = n_src; d.edge_base = d.athr != 0u ? edge_base : nullptr;
     int grid = 0;
-    if (const int rc = lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_dst<LF, EP, 4>(d, st, &grid); })) return rc;
+    const int rc = (ext || d.edge_base != nullptr)
+                       ? lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_dst<LF, EP, 4, true>(d, st, &grid); })
+                       : lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_dst<LF, EP, 4, false>(d, st, &grid); });
+    if (rc != 0) return rc;
     hipLaunchKernelGGL(gatv2_datt_sum_kernel, dim3((unsigned)HC), dim3(256), 0, st, part, grid, (int)HC, grad_att);
     BGNN_LAUNCH_CHECK();
   }
   SrcParams s{};
   s.tbl = tbl; s.ldt = ldt; s.xr_off = P; s.att = att; s.g = g; s.ldg = ldg; s.t_rowptr = t_rowptr; s.t_eid = t_eid; s.t_dst = t_dst;
   s.n_edges = n_edges; s.n_rows = n_rows; s.H = H; s.C = C; s.npad = npad; s.slope = negative_slope; s.de = de; s.coef = coef;
-  s.grad_tbl = grad_tbl; s.ldgt = ldgt;
-  return lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_src<LF, EP, 4>(s, st); });
+  s.grad_tbl = grad_tbl; s.ldgt = ldgt; s.n_src = n_src;
+  if (ext) return lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_src<LF, EP, 4, true>(s, st); });
+  return lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_src<LF, EP, 4, false>(s, st); });
+}
+
+}  // namespace
+
+extern "C" size_t bgnn_gatv2_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H, int32_t C) {
+  if (n_edges < 0 || n_rows < 0 || !shape_ok(H, C)) return 0;
+  return 2 * coef_bytes(n_edges, H) + rows_bytes(n_rows, H) + part_bytes(H, C) + 16;
+}
+
+extern "C" int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
+                                        const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H,
+                                        int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                                        const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                        const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, float* pre_out_opt,
+                                        int64_t ldp, float* out, int64_t ldo, void* stream) {
+  return gatv2_aggregate(tbl, ldt, n_tbl, att, bias_opt, rowptr, col, n_edges, n_rows, H, C, negative_slope, p_att, seed_att,
+                         seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, nullptr, nullptr, state, alpha_out_opt, pre_out_opt, ldp,
+                         out, ldo, (hipStream_t)stream);
+}
+
+extern "C" int bgnn_gatv2_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
+                                             const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H,
+                                             int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                                             const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                             const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
+                                             float* state, float* alpha_out_opt, float* pre_out_opt, int64_t ldp, float* out,
+                                             int64_t ldo, void* stream) {
+  return gatv2_aggregate(tbl, ldt, n_tbl, att, bias_opt, rowptr, col, n_edges, n_rows, H, C, negative_slope, p_att, seed_att,
+                         seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, row_id_opt, edge_base_opt, state, alpha_out_opt,
+                         pre_out_opt, ldp, out, ldo, (hipStream_t)stream);
+}
+
+extern "C" int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att, const float* bias_opt, const float* state,
+                                            const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr,
+                                            const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
+                                            int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
+                                            uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop,
+                                            uint64_t seed, const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g,
+                                            int64_t ldg, float* grad_tbl, int64_t ldgt, float* grad_att, void* stream) {
+  return gatv2_aggregate_bwd(tbl, ldt, n_rows, att, bias_opt, state, pre, ldp, grad_y, ldgy, rowptr, col, t_rowptr, t_eid, t_dst, n_edges,
+                             n_rows, H, C, negative_slope, p_att, seed_att, seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, ws,
+                             ws_bytes, nullptr, nullptr, g, ldg, grad_tbl, ldgt, grad_att, (hipStream_t)stream);
+}
+
+extern "C" int bgnn_gatv2_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt,
+                                                 const float* state, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
+                                                 const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr,
+                                                 const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H,
+                                                 int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                                                 const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                                 const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id_opt,
+                                                 const int64_t* edge_base_opt, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
+                                                 float* grad_att, void* stream) {
+  return gatv2_aggregate_bwd(tbl, ldt, n_src, att, bias_opt, state, pre, ldp, grad_y, ldgy, rowptr, col, t_rowptr, t_eid, t_dst, n_edges,
+                             n_rows, H, C, negative_slope, p_att, seed_att, seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, ws,
+                             ws_bytes, row_id_opt, edge_base_opt, g, ldg, grad_tbl, ldgt, grad_att, (hipStream_t)stream);
 }

@@ -1276,7 +1276,7 @@ def _gatv2_check(tbl, att, H, C, what):
 
 
 def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slope=0.2, p_att=0.0, seed_att=0, seed_att_dev=None,
-                    epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_pre=False, return_alpha=False):
+                    epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_pre=False, return_alpha=False, row_ids=None, edge_base=None):
     """GATv2 attention conv in one pass (models/backbones.py:302-358, bgnn.h: bgnn_gatv2_aggregate_f32) over a CSR that holds one self
     loop per row (`build_dst_csr(rewrite_self_loops=True)`).  tbl [N, >= 2P], P = pad4(H*C): x_l at columns [0, H*C), x_r at
     [P, P + H*C).  out[i,h,:] = epi(sum_t a~[t,h] * x_l[col[t],h,:] + bias[h,:]), a~ = softmax_t(<att[h], leaky_relu(x_l[col[t],h] +
@@ -1284,9 +1284,16 @@ def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slo
     epilogue: None, "elu" (then dropout at p_drop, seed + seed_dev, element i*(H*C) + column) or "log_softmax" (H == 1).  bias:
     float32 [>= H*C], 16-byte aligned, or None.
     -> (out [n_rows, P], state [n_rows, H, 2] = (max, denominator), pre | None, alpha | None): pre (want_pre) is the conv output
-    before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order."""
-    H, C, a = _gatv2_check(tbl, att, H, C, "gatv2_aggregate")
+    before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order.
+    row_ids, edge_base: int64 [n_rows] each, given together (a rank's rows of a partition, bgnn_gatv2_aggregate_rows_f32): the GLOBAL
+    id of every output row and the position of its first edge in the whole graph's CSR; the masks are then hashed at
+    row_ids[i]*(H*C) + column and (edge_base[i] + (t - rowptr[i]))*H + h, those of the whole-graph call.  None: row i, edge t."""
+    _gat_ids_paired(row_ids, edge_base, "gatv2_aggregate")
     n_rows, E = int(n_rows), int(col.shape[0])
+    if row_ids is not None:                                # dtype and length: a caller's mistake on any device, as the pairing
+        _gat_need(row_ids, "row_ids", (n_rows,), torch.int64)
+        _gat_need(edge_base, "edge_base", (n_rows,), torch.int64)
+    H, C, a = _gatv2_check(tbl, att, H, C, "gatv2_aggregate")
     dev = tbl.device
     if epilogue == "log_softmax" and H != 1:
         raise RuntimeError("gatv2_aggregate: unsupported shape: the log_softmax epilogue needs heads == 1")
@@ -1296,6 +1303,7 @@ def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slo
         raise ValueError("the table must hold a row for every destination row")
     _gat_need(rowptr, "rowptr", (n_rows + 1,), torch.int32)
     _gat_need(col, "col", (E,), torch.int32)
+    ids = _gat_ids(row_ids, edge_base, n_rows, dev, "gatv2_aggregate")
     _gat_need_seed_word(seed_att_dev, "seed_att_dev")
     _gat_need_seed_word(seed_dev, "seed_dev")
     if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
@@ -1310,47 +1318,71 @@ def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slo
     pre_arg = pre if (pre is not None and pre is not out) else None
     sa, sad = _seed_args(seed_att, seed_att_dev)
     sf, sfd = _seed_args(seed, seed_dev)
-    rc = L.lib().bgnn_gatv2_aggregate_f32(
-        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(a), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows, H, C,
-        float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(state), L.ptr(alpha),
-        L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_gatv2_aggregate_f32")
+    head = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(a), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows, H, C,
+            float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd)
+    tail = (L.ptr(state), L.ptr(alpha), L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out),
+            out.stride(0), L.stream())
+    if ids:
+        rc = L.lib().bgnn_gatv2_aggregate_rows_f32(*head, L.ptr(row_ids), L.ptr(edge_base), *tail)
+        L.check(rc, "bgnn_gatv2_aggregate_rows_f32")
+    else:
+        rc = L.lib().bgnn_gatv2_aggregate_f32(*head, *tail)
+        L.check(rc, "bgnn_gatv2_aggregate_f32")
     return out, state, pre, alpha
 
 
 def gatv2_aggregate_bwd(tbl, att, state, pre, grad_y, rowptr, col, t_rowptr, t_eid, t_dst, H, C, bias=None, negative_slope=0.2,
-                        p_att=0.0, seed_att=0, seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_bias=True):
+                        p_att=0.0, seed_att=0, seed_att_dev=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, want_bias=True,
+                        n_rows=None, row_ids=None, edge_base=None):
     """Backward of `gatv2_aggregate` (bgnn.h: bgnn_gatv2_aggregate_bwd_f32) from the forward's table, (state, pre with want_pre) and
     grad_y [N, >= pad4(H*C)] -> (grad_tbl [N, 2P] = the whole dL/dtbl: dx_l at columns [0, H*C), dx_r at [P, P + H*C), pad columns 0;
     grad_att [H*C]; grad_bias [H*C] | None).  (t_rowptr, t_eid, t_dst) = `DstCSR.transposed()`.  The coefficients are rebuilt from
-    the state and both dropout masks redrawn from their seeds.  Four launches, no atomics: bit-identical runs."""
-    H, C, a = _gatv2_check(tbl, att, H, C, "gatv2_aggregate_bwd")
+    the state and both dropout masks redrawn from their seeds.  Four launches, no atomics: bit-identical runs.
+    n_rows: the destination rows when the table holds more sources than that (a rank's extended graph: N = tbl rows = n_ext
+    sources, the first n_rows of them the owned rows; bgnn_gatv2_aggregate_bwd_rows_f32).  Then state, pre, grad_y and rowptr
+    ([n_rows + 1]) are over n_rows, t_rowptr ([N + 1]) over N, and grad_tbl is [N, 2P] with the dx_r half of the rows n_rows .. N
+    exactly 0; grad_att sums this call's edges.  None: N.
+    row_ids, edge_base: as in `gatv2_aggregate`: both masks are redrawn at the global positions."""
+    _gat_ids_paired(row_ids, edge_base, "gatv2_aggregate_bwd")
     N, E = int(tbl.shape[0]), int(col.shape[0])
+    R = N if n_rows is None else int(n_rows)
+    if not 0 <= R <= N:
+        raise ValueError(f"gatv2_aggregate_bwd: n_rows = {R} must lie in [0, {N}] (the table's rows are the sources)")
+    if row_ids is not None:                                # as in `gatv2_aggregate`
+        _gat_need(row_ids, "row_ids", (R,), torch.int64)
+        _gat_need(edge_base, "edge_base", (R,), torch.int64)
+    H, C, a = _gatv2_check(tbl, att, H, C, "gatv2_aggregate_bwd")
     dev = tbl.device
     W = pad4(H * C)
-    _gat_need(state, "state", (N, H, 2))
-    _gat_need_rows(pre, "pre", N, W)
-    _gat_need_rows(grad_y, "grad_y", N, W)
-    for t, what, n in ((rowptr, "rowptr", N + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
+    _gat_need(state, "state", (R, H, 2))
+    _gat_need_rows(pre, "pre", R, W)
+    _gat_need_rows(grad_y, "grad_y", R, W)
+    for t, what, n in ((rowptr, "rowptr", R + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
         _gat_need(t, what, (n,), torch.int32)
+    ids = _gat_ids(row_ids, edge_base, R, dev, "gatv2_aggregate_bwd")
     if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
         raise ValueError("bias must be float32 [>= H*C]")
     _gat_need_seed_word(seed_att_dev, "seed_att_dev")
     _gat_need_seed_word(seed_dev, "seed_dev")
     lib = L.lib()
-    g = torch.empty(N, W, dtype=torch.float32, device=dev)
+    g = torch.empty(R, W, dtype=torch.float32, device=dev)
     grad_tbl = torch.empty(N, 2 * W, dtype=torch.float32, device=dev)
     grad_att = torch.empty(H * C, dtype=torch.float32, device=dev)
-    wsb = int(lib.bgnn_gatv2_aggregate_workspace_bytes(E, N, H, C))
+    wsb = int(lib.bgnn_gatv2_aggregate_workspace_bytes(E, R, H, C))
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
     sa, sad = _seed_args(seed_att, seed_att_dev)
     sf, sfd = _seed_args(seed, seed_dev)
-    rc = lib.bgnn_gatv2_aggregate_bwd_f32(
-        L.ptr_rows(tbl), tbl.stride(0), L.ptr(a), L.ptr(bias), L.ptr(state), L.ptr_rows(pre), pre.stride(0), L.ptr_rows(grad_y),
-        grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E, N, H, C, float(negative_slope),
-        float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws), ws.numel(), L.ptr_rows(g), g.stride(0),
-        L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(grad_att), L.stream())
-    L.check(rc, "bgnn_gatv2_aggregate_bwd_f32")
+    mid = (L.ptr(a), L.ptr(bias), L.ptr(state), L.ptr_rows(pre), pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr),
+           L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E, R, H, C, float(negative_slope), float(p_att), sa, sad,
+           GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws), ws.numel())
+    tail = (L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(grad_att), L.stream())
+    if ids or R != N:
+        rc = lib.bgnn_gatv2_aggregate_bwd_rows_f32(L.ptr_rows(tbl), tbl.stride(0), N, *mid, L.ptr(row_ids) if ids else None,
+                                                   L.ptr(edge_base) if ids else None, *tail)
+        L.check(rc, "bgnn_gatv2_aggregate_bwd_rows_f32")
+    else:
+        rc = lib.bgnn_gatv2_aggregate_bwd_f32(L.ptr_rows(tbl), tbl.stride(0), *mid, *tail)
+        L.check(rc, "bgnn_gatv2_aggregate_bwd_f32")
     return grad_tbl, grad_att, (column_sums(g)[:H * C] if want_bias else None)
 
 

@@ -38,7 +38,8 @@ extern "C" {
  * their workspace size (added after 114 without changing it), and for the GATv2 baseline's bgnn_gatv2_aggregate_f32,
  * bgnn_gatv2_aggregate_bwd_f32 and their workspace size (likewise), and for bgnn_adaptedconv_aggregate_queued_f32 with
  * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue), and for partitioned
- * GAT's bgnn_gat_aggregate_rows_f32 and bgnn_gat_aggregate_bwd_rows_f32 (added after 115 without changing it).
+ * GAT's bgnn_gat_aggregate_rows_f32 and bgnn_gat_aggregate_bwd_rows_f32 (added after 115 without changing it), and for partitioned
+ * GATv2's bgnn_gatv2_aggregate_rows_f32 and bgnn_gatv2_aggregate_bwd_rows_f32 (likewise).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
  * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone.
@@ -650,8 +651,8 @@ int bgnn_gat_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src
  * denominator >= 1); alpha_out_opt [n_edges, H]: the coefficients a~ in CSR order (NULL: not formed; the pass parks the logits
  * there and a sweep over the row's own words finishes them, no second gather); pre_out_opt [n_rows, ldp]: the conv output
  * before the epilogue (NULL: not written); out [n_rows, ldo]; pad columns H*C .. P of out and pre_out leave as 0.
- * bgnn_gatv2_aggregate_bwd_f32: the atomic-free backward from (tbl, att, state, pre) and grad_y; n_rows rows are both sources
- * and destinations.  A row pass writes g [n_rows, ldg] and r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]> as GAT's does; a pass
+ * bgnn_gatv2_aggregate_bwd_f32: the atomic-free backward from (tbl, att, state, pre) and grad_y; here n_rows rows are both sources
+ * and destinations (n_src == n_rows; bgnn_gatv2_aggregate_bwd_rows_f32 below counts them separately).  A row pass writes g [n_rows, ldg] and r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]> as GAT's does; a pass
  * over the by-destination CSR regathers x_l[j], rebuilds e with the forward's own operations, alpha = exp(e - max) / den,
  * da = mask * <g[i,h,:], x_l[j,h,:]>, de = alpha * (da - r); de and a~ go to ws, grad_tbl[i, P + h*C + c] = sum_t de * att[h,c] *
  * leaky'(m_c), and grad_att[h,c] = sum over all edges of de * leaky(m_c): per block partial rows added in a fixed order by a small
@@ -674,6 +675,35 @@ int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att
                                  uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
                                  const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
                                  float* grad_tbl, int64_t ldgt, float* grad_att, void* stream);
+/* bgnn_gatv2_aggregate_rows_f32 / bgnn_gatv2_aggregate_bwd_rows_f32: the two entries above for a block of rows of a larger graph (a
+ * rank's rows of a destination-node partition: tbl covers the rank's own rows followed by its halo rows).  Both masks are then drawn
+ * where the whole-graph call draws them: row_id_opt [n_rows] (int64) is every row's GLOBAL id, the feature-dropout element index
+ * becomes row_id[i]*(H*C) + h*C + c; edge_base_opt [n_rows] (int64) is the position of the row's first edge in the WHOLE graph's
+ * by-destination CSR, the attention-dropout element index of edge t of row i becomes (edge_base[i] + (t - rowptr[i])) * H + h -- a
+ * rank's rows must keep the whole graph's edge order inside a row.  The two pointers are given together (else BGNN_E_NULL); the
+ * ids feed the hash only and never form an address.  The backward redraws both masks from the same ids and counts rows and sources
+ * separately: n_rows destination rows (rowptr [n_rows+1]; state, pre, grad_y and g are over n_rows, and so is the workspace:
+ * bgnn_gatv2_aggregate_workspace_bytes(n_edges, n_rows, H, C)) and n_src >= n_rows source rows (else BGNN_E_SHAPE; tbl and grad_tbl
+ * are over n_src, t_rowptr is [n_src+1]); every id in col is < n_src, every id in t_dst < n_rows.  The by-destination pass
+ * regathers x_l[j] for j < n_src; the by-source pass walks n_src sources and reads x_r and g of rows < n_rows only.  The x_r half of
+ * grad_tbl (columns [P, 2P)) is written for rows < n_rows and is 0 for the rows n_rows .. n_src (a halo slot has no in-edges, its
+ * x_r is never read); pad columns are 0; grad_att is the sum over this call's edges.  No float atomics: two identical calls are
+ * bitwise equal.  With both pointers NULL (or no dropout) and n_src == n_rows these are bgnn_gatv2_aggregate_f32 /
+ * bgnn_gatv2_aggregate_bwd_f32, bit for bit and kernel for kernel. */
+int bgnn_gatv2_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
+                                  const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
+                                  float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
+                                  int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                  const int64_t* row_id_opt, const int64_t* edge_base_opt, float* state, float* alpha_out_opt,
+                                  float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
+int bgnn_gatv2_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt,
+                                      const float* state, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
+                                      const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid,
+                                      const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
+                                      float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
+                                      int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, void* ws,
+                                      size_t ws_bytes, const int64_t* row_id_opt, const int64_t* edge_base_opt, float* g, int64_t ldg,
+                                      float* grad_tbl, int64_t ldgt, float* grad_att, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.
