@@ -81,9 +81,7 @@ SIGNATURES = {
     "bgnn_coalesce_workspace_bytes": (_SZ, [_I64]),
     "bgnn_coalesce_i64": (_INT, [_P, _I64, _I64, _P, _P, _SZ, _P]),
     "bgnn_sage_mean_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _INT, _INT, _F32, C.c_uint64, _P,
-                                             _P, _I64, _P]),
-    "bgnn_sage_mean_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _I32, _INT, _INT, _F32, C.c_uint64, _P,
-                                                  _P, _P, _I64, _P]),
+                                             _P, _P, _I64, _P]),
     "bgnn_rows_segment_add_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _I64, _I32, _INT, _P, _I64, _I64, _P]),
     "bgnn_pair_mlp_workspace_bytes": (_SZ, [_I64]),
     "bgnn_pair_mlp_stats_f32": (_INT, [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _F32, _P, _P, _P, _P, _SZ, _P]),
@@ -103,34 +101,22 @@ SIGNATURES = {
                                                  _P, _SZ, _P]),
     "bgnn_gcn_aggregate_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_gcn_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P,
-                                       _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _I64, _P]),
-    "bgnn_gcn_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P,
-                                            _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _I64, _P]),
+                                       _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _I64, _P]),
     "bgnn_gcn_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I32, _INT, _F32,
                                            _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _I64, _P, _I64, _P]),
     "bgnn_gat_scores_f32": (_INT, [_P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgnn_gat_aggregate_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
     "bgnn_gat_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,
-                                       _INT, _F32, C.c_uint64, _P, _P, _P, _P, _SZ, _P, _I64, _P, _I64, _P]),
+                                       _INT, _F32, C.c_uint64, _P, _P, _P, _P, _P, _P, _SZ, _P, _I64, _P, _I64, _P]),
     "bgnn_gat_aggregate_bwd_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64,
                                            _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ,
-                                           _P, _I64, _P, _I64, _P, _P, _P]),
-    "bgnn_gat_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,
-                                            _INT, _F32, C.c_uint64, _P, _P, _P, _P, _P, _P, _SZ, _P, _I64, _P, _I64, _P]),
-    "bgnn_gat_aggregate_bwd_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64,
-                                                _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ,
-                                                _P, _P, _P, _I64, _P, _I64, _P, _P, _P]),
+                                           _P, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "bgnn_gatv2_aggregate_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
     "bgnn_gatv2_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,
-                                         _INT, _F32, C.c_uint64, _P, _P, _P, _P, _I64, _P, _I64, _P]),
-    "bgnn_gatv2_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32,
-                                             _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ, _P, _I64, _P, _I64,
-                                             _P, _P]),
-    "bgnn_gatv2_aggregate_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,
-                                              _INT, _F32, C.c_uint64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
-    "bgnn_gatv2_aggregate_bwd_rows_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64,
-                                                  _I32, _I32, _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ, _P, _P,
-                                                  _P, _I64, _P, _I64, _P, _P]),
+                                         _INT, _F32, C.c_uint64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "bgnn_gatv2_aggregate_bwd_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64,
+                                             _I32, _I32, _F32, _F32, C.c_uint64, _P, _INT, _F32, C.c_uint64, _P, _P, _SZ, _P, _P,
+                                             _P, _I64, _P, _I64, _P, _P]),
     "bgnn_step2_loss_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_step2_loss_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, C.c_double, _P, _P, _SZ, _P]),
     "bgnn_step2_loss_bwd_f32": (_INT, [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
@@ -174,7 +160,7 @@ def _sidecar_hash():
 
 
 # the ABI revision this binding was written for (include/bgnn.h: BGNN_VERSION); checked against the loaded library
-ABI_VERSION = 115
+ABI_VERSION = 116
 
 
 def _make():

@@ -24,11 +24,11 @@
 //             dz goes to a [E', H] workspace; its row sum ds_dst[i,h] is formed from the row's own per-side sums (see there).
 //   gather    by-source (t_rowptr, t_eid, t_dst): the aggregate kernel with coefficient index t_eid[u]:
 //             dT[j,h,:] = sum_u coef[t_eid[u],h] * g[t_dst[u],h,:] and ds_src[j,h] = sum_u dz[t_eid[u],h].
-// Rows of a larger graph (bgnn_gat_aggregate_rows_f32 / bgnn_gat_aggregate_bwd_rows_f32, a rank's rows of a node partition): both
+// Rows of a larger graph (row_id_opt / edge_base_opt of the two entries, a rank's rows of a node partition): both
 // masks are functions of a position, and a rank's local positions are not the whole graph's.  The ROW_ID / EDGE_ID kernels hash
 // the feature mask at row_id[i] * (H*C) + column and the attention mask at (edge_base[i] + (t - rowptr[i])) * H + h: the row's
 // GLOBAL id and the GLOBAL position of its first edge, both read once per virtual row.  The ids feed the hash only, never an address.
-// The plain entries launch the instantiations without the flags.  The backward takes n_rows destination rows and n_src >= n_rows
+// Without ids (or without dropout) the entries launch the instantiations without the flags.  The backward takes n_rows destination rows and n_src >= n_rows
 // source rows (a rank's extended graph: its halo slots are sources without in-edges); see bgnn.h for which operand is over which.
 // Ids outside their table are never dereferenced and a row's edge range is cut to the edge arrays: a malformed CSR (ids or rowptr)
 // gives a wrong sum, not a stray read or write.
@@ -427,95 +427,6 @@ int dispatch_edge(const EdgeParams& p, hipStream_t st) {
   return lf_ladder((p.C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_edge<LF, EP, 4, EDGE_ID>(p, st); });
 }
 
-// the ids matter only where a mask is drawn: without dropout the plain instantiations run
-int gat_aggregate(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s_src, const float* s_dst, const float* bias_opt,
-                  const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
-                  float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop,
-                  uint64_t seed, const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes,
-                  const int64_t* row_id, const int64_t* edge_base, float* pre_out_opt, int64_t ldp, float* out, int64_t ldo,
-                  hipStream_t st) {
-  if (!tbl || !s_src || !s_dst || !rowptr || !col || !state || !out) return BGNN_E_NULL;
-  if (!alpha_out_opt && !ws_opt) return BGNN_E_NULL;
-  if (n_rows < 0 || n_tbl < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
-  if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
-  if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
-  const int32_t HC = H * C;
-  if (!tbl_ok(tbl, ldt, HC) || !tbl_ok(out, ldo, HC) || (pre_out_opt && !tbl_ok(pre_out_opt, ldp, HC))) return BGNN_E_ALIGN;
-  if (bias_opt && !bgnn_aligned16(bias_opt)) return BGNN_E_ALIGN;
-  float* coef = alpha_out_opt;
-  if (!coef) {
-    if (ws_bytes < coef_bytes(n_edges, H) + 16) return BGNN_E_WORKSPACE;
-    coef = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws_opt), 16));
-  }
-  if (n_rows == 0) return 0;
-  {
-    AlphaParams a{};
-    a.s_src = s_src; a.n_src = n_tbl; a.s_dst = s_dst; a.rowptr = rowptr; a.col = col; a.n_rows = n_rows; a.n_edges = n_edges; a.H = H;
-    a.slope = negative_slope;
-    att_drop_consts(p_att, a.thr, a.keep_scale);
-    a.seed = seed_att; a.seed_dev = seed_att_dev_opt;
-    a.state = state; a.coef = coef; a.edge_base = edge_base;
-    const int rc = (edge_base != nullptr && a.thr != 0u) ? launch_alpha<true>(a, st) : launch_alpha<false>(a, st);
-    if (rc != 0) return rc;
-  }
-  AggParams p{};
-  p.tbl = tbl; p.ldt = ldt; p.n_tbl = n_tbl; p.bias = bias_opt; p.rowptr = rowptr; p.col = col; p.eid = nullptr; p.n_edges = n_edges;
-  p.coef = coef; p.n_rows = n_rows; p.H = H; p.C = C; p.npad = (HC + 3) / 4 * 4 - HC;
-  p.out = out; p.ldo = ldo; p.pre = pre_out_opt; p.ldp = ldp;
-  drop_consts(p_drop, p.thr, p.keep_scale);
-  p.seed = seed; p.seed_dev = seed_dev_opt; p.row_id = row_id;
-  if (epilogue == EPI_ELU && row_id != nullptr && p.thr != 0u) return dispatch_agg<EPI_ELU, false, true>(p, st);
-  return epi_switch(epilogue, [&](auto EPI) { return dispatch_agg<EPI, false>(p, st); });
-}
-
-int gat_aggregate_bwd(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst, const float* bias_opt,
-                      const float* state, const float* alpha, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
-                      const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                      int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                      const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                      void* ws, size_t ws_bytes, const int64_t* row_id, const int64_t* edge_base, float* g, int64_t ldg,
-                      float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, hipStream_t st) {
-  if (!tbl || !s_src || !s_dst || !state || !alpha || !pre || !grad_y || !rowptr || !col || !t_rowptr || !t_eid || !t_dst || !ws ||
-      !g || !grad_tbl || !ds_src || !ds_dst)
-    return BGNN_E_NULL;
-  if (n_rows < 0 || n_src < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
-  if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
-  if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
-  const int32_t HC = H * C;
-  if (!tbl_ok(tbl, ldt, HC) || !tbl_ok(pre, ldp, HC) || !tbl_ok(grad_y, ldgy, HC) || !tbl_ok(g, ldg, HC) || !tbl_ok(grad_tbl, ldgt, HC))
-    return BGNN_E_ALIGN;
-  if (bias_opt && !bgnn_aligned16(bias_opt)) return BGNN_E_ALIGN;
-  if (ws_bytes < bgnn_gat_aggregate_workspace_bytes(n_edges, n_rows, H)) return BGNN_E_WORKSPACE;
-  float* dz = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws), 16));
-  float* r = dz + coef_bytes(n_edges, H) / sizeof(float);
-  const int32_t npad = (HC + 3) / 4 * 4 - HC;
-  if (n_rows > 0) {
-    RowParams p{};
-    p.pre = pre; p.ldp = ldp; p.gy = grad_y; p.ldgy = ldgy; p.bias = bias_opt; p.n_rows = n_rows; p.H = H; p.C = C; p.npad = npad;
-    drop_consts(p_drop, p.thr, p.keep_scale);
-    p.seed = seed; p.seed_dev = seed_dev_opt;
-    p.g = g; p.ldg = ldg; p.r = r; p.row_id = row_id;
-    int rc = dispatch_rows(epilogue, p, st);
-    if (rc != 0) return rc;
-    EdgeParams e{};
-    e.tbl = tbl; e.ldt = ldt; e.n_tbl = n_src; e.g = g; e.ldg = ldg; e.s_src = s_src; e.s_dst = s_dst; e.state = state; e.r = r;
-    e.rowptr = rowptr; e.col = col; e.n_rows = n_rows; e.n_edges = n_edges; e.H = H; e.C = C; e.slope = negative_slope;
-    att_drop_consts(p_att, e.thr, e.keep_scale);
-    e.seed = seed_att; e.seed_dev = seed_att_dev_opt;
-    e.dz = dz; e.ds_dst = ds_dst; e.edge_base = edge_base;
-    rc = (edge_base != nullptr && e.thr != 0u) ? dispatch_edge<true>(e, st) : dispatch_edge<false>(e, st);
-    if (rc != 0) return rc;
-  }
-  if (n_src == 0) return 0;
-  // the forward walk over the by-source view: its n_src rows gather rows of g (n_rows of them: every id in t_dst is a row < n_rows)
-  // with the forward's coefficients; a source without out-edges here (no halo slot is one) leaves as a zero row
-  AggParams p{};
-  p.tbl = g; p.ldt = ldg; p.n_tbl = n_rows; p.bias = nullptr; p.rowptr = t_rowptr; p.col = t_dst; p.eid = t_eid; p.n_edges = n_edges;
-  p.coef = alpha; p.dz = dz; p.dsum = ds_src; p.n_rows = n_src; p.H = H; p.C = C; p.npad = npad;
-  p.out = grad_tbl; p.ldo = ldgt; p.pre = nullptr;
-  return dispatch_agg<EPI_NONE, true>(p, st);
-}
-
 }  // namespace
 
 extern "C" int bgnn_gat_scores_f32(const float* tbl, int64_t ldt, int64_t n, int32_t H, int32_t C, const float* att_src,
@@ -536,27 +447,47 @@ extern "C" size_t bgnn_gat_aggregate_workspace_bytes(int64_t n_edges, int64_t n_
   return coef_bytes(n_edges, H) + bgnn_align_up((size_t)n_rows * (size_t)H * sizeof(float), 16) + 16;
 }
 
+// the ids matter only where a mask is drawn: without dropout the plain instantiations run
 extern "C" int bgnn_gat_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s_src, const float* s_dst,
                                       const float* bias_opt, const int32_t* rowptr, const int32_t* col, int64_t n_edges,
                                       int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
                                       const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                      const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes,
-                                      float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream) {
-  return gat_aggregate(tbl, ldt, n_tbl, s_src, s_dst, bias_opt, rowptr, col, n_edges, n_rows, H, C, negative_slope, p_att, seed_att,
-                       seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, state, alpha_out_opt, ws_opt, ws_bytes, nullptr, nullptr,
-                       pre_out_opt, ldp, out, ldo, (hipStream_t)stream);
-}
-
-extern "C" int bgnn_gat_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s_src, const float* s_dst,
-                                           const float* bias_opt, const int32_t* rowptr, const int32_t* col, int64_t n_edges,
-                                           int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                           const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                           const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
-                                           float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes, float* pre_out_opt,
-                                           int64_t ldp, float* out, int64_t ldo, void* stream) {
-  return gat_aggregate(tbl, ldt, n_tbl, s_src, s_dst, bias_opt, rowptr, col, n_edges, n_rows, H, C, negative_slope, p_att, seed_att,
-                       seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, state, alpha_out_opt, ws_opt, ws_bytes, row_id_opt,
-                       edge_base_opt, pre_out_opt, ldp, out, ldo, (hipStream_t)stream);
+                                      const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
+                                      float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes, float* pre_out_opt,
+                                      int64_t ldp, float* out, int64_t ldo, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!tbl || !s_src || !s_dst || !rowptr || !col || !state || !out) return BGNN_E_NULL;
+  if (!alpha_out_opt && !ws_opt) return BGNN_E_NULL;
+  if (n_rows < 0 || n_tbl < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
+  if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
+  const int32_t HC = H * C;
+  if (!tbl_ok(tbl, ldt, HC) || !tbl_ok(out, ldo, HC) || (pre_out_opt && !tbl_ok(pre_out_opt, ldp, HC))) return BGNN_E_ALIGN;
+  if (bias_opt && !bgnn_aligned16(bias_opt)) return BGNN_E_ALIGN;
+  float* coef = alpha_out_opt;
+  if (!coef) {
+    if (ws_bytes < coef_bytes(n_edges, H) + 16) return BGNN_E_WORKSPACE;
+    coef = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws_opt), 16));
+  }
+  if (n_rows == 0) return 0;
+  {
+    AlphaParams a{};
+    a.s_src = s_src; a.n_src = n_tbl; a.s_dst = s_dst; a.rowptr = rowptr; a.col = col; a.n_rows = n_rows; a.n_edges = n_edges; a.H = H;
+    a.slope = negative_slope;
+    att_drop_consts(p_att, a.thr, a.keep_scale);
+    a.seed = seed_att; a.seed_dev = seed_att_dev_opt;
+    a.state = state; a.coef = coef; a.edge_base = edge_base_opt;
+    const int rc = (edge_base_opt != nullptr && a.thr != 0u) ? launch_alpha<true>(a, st) : launch_alpha<false>(a, st);
+    if (rc != 0) return rc;
+  }
+  AggParams p{};
+  p.tbl = tbl; p.ldt = ldt; p.n_tbl = n_tbl; p.bias = bias_opt; p.rowptr = rowptr; p.col = col; p.eid = nullptr; p.n_edges = n_edges;
+  p.coef = coef; p.n_rows = n_rows; p.H = H; p.C = C; p.npad = (HC + 3) / 4 * 4 - HC;
+  p.out = out; p.ldo = ldo; p.pre = pre_out_opt; p.ldp = ldp;
+  drop_consts(p_drop, p.thr, p.keep_scale);
+  p.seed = seed; p.seed_dev = seed_dev_opt; p.row_id = row_id_opt;
+  if (epilogue == EPI_ELU && row_id_opt != nullptr && p.thr != 0u) return dispatch_agg<EPI_ELU, false, true>(p, st);
+  return epi_switch(epilogue, [&](auto EPI) { return dispatch_agg<EPI, false>(p, st); });
 }
 
 extern "C" int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
@@ -565,24 +496,47 @@ extern "C" int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t
                                           const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges,
                                           int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
                                           const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                          const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
-                                          float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, void* stream) {
-  return gat_aggregate_bwd(tbl, ldt, n_src, s_src, s_dst, bias_opt, state, alpha, pre, ldp, grad_y, ldgy, rowptr, col, t_rowptr, t_eid,
-                           t_dst, n_edges, n_rows, H, C, negative_slope, p_att, seed_att, seed_att_dev_opt, epilogue, p_drop, seed,
-                           seed_dev_opt, ws, ws_bytes, nullptr, nullptr, g, ldg, grad_tbl, ldgt, ds_src, ds_dst, (hipStream_t)stream);
-}
-
-extern "C" int bgnn_gat_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
-                                               const float* bias_opt, const float* state, const float* alpha, const float* pre,
-                                               int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr,
-                                               const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                               int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
-                                               uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop,
-                                               uint64_t seed, const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes,
-                                               const int64_t* row_id_opt, const int64_t* edge_base_opt, float* g, int64_t ldg,
-                                               float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, void* stream) {
-  return gat_aggregate_bwd(tbl, ldt, n_src, s_src, s_dst, bias_opt, state, alpha, pre, ldp, grad_y, ldgy, rowptr, col, t_rowptr, t_eid,
-                           t_dst, n_edges, n_rows, H, C, negative_slope, p_att, seed_att, seed_att_dev_opt, epilogue, p_drop, seed,
-                           seed_dev_opt, ws, ws_bytes, row_id_opt, edge_base_opt, g, ldg, grad_tbl, ldgt, ds_src, ds_dst,
-                           (hipStream_t)stream);
+                                          const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id_opt,
+                                          const int64_t* edge_base_opt, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
+                                          float* ds_src, float* ds_dst, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!tbl || !s_src || !s_dst || !state || !alpha || !pre || !grad_y || !rowptr || !col || !t_rowptr || !t_eid || !t_dst || !ws ||
+      !g || !grad_tbl || !ds_src || !ds_dst)
+    return BGNN_E_NULL;
+  if (n_rows < 0 || n_src < 0 || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
+  if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
+  const int32_t HC = H * C;
+  if (!tbl_ok(tbl, ldt, HC) || !tbl_ok(pre, ldp, HC) || !tbl_ok(grad_y, ldgy, HC) || !tbl_ok(g, ldg, HC) || !tbl_ok(grad_tbl, ldgt, HC))
+    return BGNN_E_ALIGN;
+  if (bias_opt && !bgnn_aligned16(bias_opt)) return BGNN_E_ALIGN;
+  if (ws_bytes < bgnn_gat_aggregate_workspace_bytes(n_edges, n_rows, H)) return BGNN_E_WORKSPACE;
+  float* dz = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws), 16));
+  float* r = dz + coef_bytes(n_edges, H) / sizeof(float);
+  const int32_t npad = (HC + 3) / 4 * 4 - HC;
+  if (n_rows > 0) {
+    RowParams p{};
+    p.pre = pre; p.ldp = ldp; p.gy = grad_y; p.ldgy = ldgy; p.bias = bias_opt; p.n_rows = n_rows; p.H = H; p.C = C; p.npad = npad;
+    drop_consts(p_drop, p.thr, p.keep_scale);
+    p.seed = seed; p.seed_dev = seed_dev_opt;
+    p.g = g; p.ldg = ldg; p.r = r; p.row_id = row_id_opt;
+    int rc = dispatch_rows(epilogue, p, st);
+    if (rc != 0) return rc;
+    EdgeParams e{};
+    e.tbl = tbl; e.ldt = ldt; e.n_tbl = n_src; e.g = g; e.ldg = ldg; e.s_src = s_src; e.s_dst = s_dst; e.state = state; e.r = r;
+    e.rowptr = rowptr; e.col = col; e.n_rows = n_rows; e.n_edges = n_edges; e.H = H; e.C = C; e.slope = negative_slope;
+    att_drop_consts(p_att, e.thr, e.keep_scale);
+    e.seed = seed_att; e.seed_dev = seed_att_dev_opt;
+    e.dz = dz; e.ds_dst = ds_dst; e.edge_base = edge_base_opt;
+    rc = (edge_base_opt != nullptr && e.thr != 0u) ? dispatch_edge<true>(e, st) : dispatch_edge<false>(e, st);
+    if (rc != 0) return rc;
+  }
+  if (n_src == 0) return 0;
+  // the forward walk over the by-source view: its n_src rows gather rows of g (n_rows of them: every id in t_dst is a row < n_rows)
+  // with the forward's coefficients; a source without out-edges here (no halo slot is one) leaves as a zero row
+  AggParams p{};
+  p.tbl = g; p.ldt = ldg; p.n_tbl = n_rows; p.bias = nullptr; p.rowptr = t_rowptr; p.col = t_dst; p.eid = t_eid; p.n_edges = n_edges;
+  p.coef = alpha; p.dz = dz; p.dsum = ds_src; p.n_rows = n_src; p.H = H; p.C = C; p.npad = npad;
+  p.out = grad_tbl; p.ldo = ldgt; p.pre = nullptr;
+  return dispatch_agg<EPI_NONE, true>(p, st);
 }

@@ -31,7 +31,7 @@
 //             walks head by head), is reduced over the block in a fixed order and written to the block's partial row.
 //   datt      adds the blocks' partial rows in a fixed order (a block per column).
 //   by-src    over (t_rowptr, t_eid, t_dst): gathers g_i and xr_i, dXL[j,h,:] = sum_u coef * g_i + de * att (.) leaky'(xl_j + xr_i).
-// Rows of a larger graph (bgnn_gatv2_aggregate_rows_f32 / bgnn_gatv2_aggregate_bwd_rows_f32, a rank's rows of a node partition): both
+// Rows of a larger graph (row_id_opt / edge_base_opt of the two entries, a rank's rows of a node partition): both
 // masks are functions of a position, and a rank's local positions are not the whole graph's.  The IDS forward hashes the feature
 // mask at row_id[i] * (H*C) + column and the attention mask at (edge_base[i] + (t - rowptr[i])) * H + h: the row's GLOBAL id and the
 // GLOBAL position of its first edge, both read once per virtual row; the ids feed the hash only, never an address.  The backward
@@ -540,14 +540,24 @@ size_t rows_bytes(int64_t n_rows, int32_t H) { return bgnn_align_up((size_t)n_ro
 // the one table [rows, >= 2 * pad4(H*C)] with XL and XR: 16-byte aligned base, leading dimension a multiple of 4
 bool cat_ok(const float* t, int64_t ld, int32_t HC) { return bgnn_aligned16(t) && (ld & 3) == 0 && ld >= 2 * (((int64_t)HC + 3) / 4 * 4); }
 
+}  // namespace
+
+extern "C" size_t bgnn_gatv2_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H, int32_t C) {
+  if (n_edges < 0 || n_rows < 0 || !shape_ok(H, C)) return 0;
+  return 2 * coef_bytes(n_edges, H) + rows_bytes(n_rows, H) + part_bytes(H, C) + 16;
+}
+
 // the ids matter only where a mask is drawn: without dropout the plain instantiations run
-int gatv2_aggregate(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt, const int32_t* rowptr,
-                    const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
-                    uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                    const uint64_t* seed_dev_opt, const int64_t* row_id, const int64_t* edge_base, float* state, float* alpha_out_opt,
-                    float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, hipStream_t st) {
+extern "C" int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
+                                        const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H,
+                                        int32_t C, float negative_slope, float p_att, uint64_t seed_att,
+                                        const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
+                                        const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
+                                        float* state, float* alpha_out_opt, float* pre_out_opt, int64_t ldp, float* out, int64_t ldo,
+                                        void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   if (!tbl || !att || !rowptr || !col || !state || !out) return BGNN_E_NULL;
-  if ((row_id == nullptr) != (edge_base == nullptr)) return BGNN_E_NULL;      // the forward hashes both: given together
+  if ((row_id_opt == nullptr) != (edge_base_opt == nullptr)) return BGNN_E_NULL;  // the forward hashes both: given together
   if (n_rows < 0 || n_tbl < n_rows || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
   if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
   if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
@@ -564,21 +574,23 @@ int gatv2_aggregate(const float* tbl, int64_t ldt, int64_t n_tbl, const float* a
   drop_consts(p_drop, p.thr, p.keep_scale);
   p.seed = seed; p.seed_dev = seed_dev_opt;
   p.state = state; p.alpha = alpha_out_opt; p.pre = pre_out_opt; p.ldp = ldp; p.out = out; p.ldo = ldo;
-  p.row_id = row_id; p.edge_base = edge_base;
-  if (row_id != nullptr && (p.athr != 0u || (epilogue == EPI_ELU && p.thr != 0u))) return dispatch_fwd<true>(epilogue, p, st);
+  p.row_id = row_id_opt; p.edge_base = edge_base_opt;
+  if (row_id_opt != nullptr && (p.athr != 0u || (epilogue == EPI_ELU && p.thr != 0u))) return dispatch_fwd<true>(epilogue, p, st);
   return dispatch_fwd<false>(epilogue, p, st);
 }
 
-int gatv2_aggregate_bwd(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt, const float* state,
-                        const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr, const int32_t* col,
-                        const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H,
-                        int32_t C, float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue,
-                        float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id,
-                        const int64_t* edge_base, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt, float* grad_att,
-                        hipStream_t st) {
+extern "C" int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt,
+                                            const float* state, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
+                                            const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid,
+                                            const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
+                                            float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
+                                            int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, void* ws,
+                                            size_t ws_bytes, const int64_t* row_id_opt, const int64_t* edge_base_opt, float* g,
+                                            int64_t ldg, float* grad_tbl, int64_t ldgt, float* grad_att, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   if (!tbl || !att || !state || !pre || !grad_y || !rowptr || !col || !t_rowptr || !t_eid || !t_dst || !ws || !g || !grad_tbl || !grad_att)
     return BGNN_E_NULL;
-  if ((row_id == nullptr) != (edge_base == nullptr)) return BGNN_E_NULL;
+  if ((row_id_opt == nullptr) != (edge_base_opt == nullptr)) return BGNN_E_NULL;
   if (n_rows < 0 || n_src < n_rows || n_edges < 0 || !shape_ok(H, C) || !(p_att >= 0.f && p_att < 1.f)) return BGNN_E_SHAPE;
   if (const int rc = epi_check(epilogue, p_drop, C)) return rc;
   if (epilogue == EPI_LOGSOFTMAX && H != 1) return BGNN_E_SHAPE;
@@ -603,7 +615,7 @@ int gatv2_aggregate_bwd(const float* tbl, int64_t ldt, int64_t n_src, const floa
     q.pre = pre; q.ldp = ldp; q.gy = grad_y; q.ldgy = ldgy; q.bias = bias_opt; q.n_rows = n_rows; q.H = H; q.C = C; q.npad = npad;
     drop_consts(p_drop, q.thr, q.keep_scale);
     q.seed = seed; q.seed_dev = seed_dev_opt;
-    q.g = g; q.ldg = ldg; q.r = r; q.row_id = row_id;
+    q.g = g; q.ldg = ldg; q.r = r; q.row_id = row_id_opt;
     if (const int rc = dispatch_rows(epilogue, q, st)) return rc;
   }
   {
@@ -613,7 +625,7 @@ int gatv2_aggregate_bwd(const float* tbl, int64_t ldt, int64_t n_src, const floa
     att_drop_consts(p_att, d.athr, d.akeep);
     d.aseed = seed_att; d.aseed_dev = seed_att_dev_opt;
     d.de = de; d.coef = coef; d.grad_tbl = grad_tbl; d.ldgt = ldgt; d.part = part;
-    d.n_src = n_src; d.edge_base = d.athr != 0u ? edge_base : nullptr;
+    d.n_src = n_src; d.edge_base = d.athr != 0u ? edge_base_opt : nullptr;
     int grid = 0;
     const int rc = (ext || d.edge_base != nullptr)
                        ? lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_dst<LF, EP, 4, true>(d, st, &grid); })
@@ -628,60 +640,4 @@ int gatv2_aggregate_bwd(const float* tbl, int64_t ldt, int64_t n_src, const floa
   s.grad_tbl = grad_tbl; s.ldgt = ldgt; s.n_src = n_src;
   if (ext) return lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_src<LF, EP, 4, true>(s, st); });
   return lf_ladder((C + 3) / 4, [&](auto LF, auto EP, auto) { return launch_src<LF, EP, 4, false>(s, st); });
-}
-
-}  // namespace
-
-extern "C" size_t bgnn_gatv2_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H, int32_t C) {
-  if (n_edges < 0 || n_rows < 0 || !shape_ok(H, C)) return 0;
-  return 2 * coef_bytes(n_edges, H) + rows_bytes(n_rows, H) + part_bytes(H, C) + 16;
-}
-
-extern "C" int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
-                                        const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H,
-                                        int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                        const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                        const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, float* pre_out_opt,
-                                        int64_t ldp, float* out, int64_t ldo, void* stream) {
-  return gatv2_aggregate(tbl, ldt, n_tbl, att, bias_opt, rowptr, col, n_edges, n_rows, H, C, negative_slope, p_att, seed_att,
-                         seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, nullptr, nullptr, state, alpha_out_opt, pre_out_opt, ldp,
-                         out, ldo, (hipStream_t)stream);
-}
-
-extern "C" int bgnn_gatv2_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
-                                             const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H,
-                                             int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                             const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                             const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
-                                             float* state, float* alpha_out_opt, float* pre_out_opt, int64_t ldp, float* out,
-                                             int64_t ldo, void* stream) {
-  return gatv2_aggregate(tbl, ldt, n_tbl, att, bias_opt, rowptr, col, n_edges, n_rows, H, C, negative_slope, p_att, seed_att,
-                         seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, row_id_opt, edge_base_opt, state, alpha_out_opt,
-                         pre_out_opt, ldp, out, ldo, (hipStream_t)stream);
-}
-
-extern "C" int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att, const float* bias_opt, const float* state,
-                                            const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr,
-                                            const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                            int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
-                                            uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop,
-                                            uint64_t seed, const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g,
-                                            int64_t ldg, float* grad_tbl, int64_t ldgt, float* grad_att, void* stream) {
-  return gatv2_aggregate_bwd(tbl, ldt, n_rows, att, bias_opt, state, pre, ldp, grad_y, ldgy, rowptr, col, t_rowptr, t_eid, t_dst, n_edges,
-                             n_rows, H, C, negative_slope, p_att, seed_att, seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, ws,
-                             ws_bytes, nullptr, nullptr, g, ldg, grad_tbl, ldgt, grad_att, (hipStream_t)stream);
-}
-
-extern "C" int bgnn_gatv2_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt,
-                                                 const float* state, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
-                                                 const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr,
-                                                 const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H,
-                                                 int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                                 const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                                 const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id_opt,
-                                                 const int64_t* edge_base_opt, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
-                                                 float* grad_att, void* stream) {
-  return gatv2_aggregate_bwd(tbl, ldt, n_src, att, bias_opt, state, pre, ldp, grad_y, ldgy, rowptr, col, t_rowptr, t_eid, t_dst, n_edges,
-                             n_rows, H, C, negative_slope, p_att, seed_att, seed_att_dev_opt, epilogue, p_drop, seed, seed_dev_opt, ws,
-                             ws_bytes, row_id_opt, edge_base_opt, g, ldg, grad_tbl, ldgt, grad_att, (hipStream_t)stream);
 }

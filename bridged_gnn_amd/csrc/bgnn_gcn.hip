@@ -19,9 +19,10 @@
 // in segment order, scales by dinv_i, adds the bias and applies the epilogue.  One group per segment: a hub is spread over
 // the whole grid, its bits do not depend on which block took which segment.
 //
-// Rows of a larger graph (bgnn_gcn_aggregate_rows_f32, a rank's rows of a node partition): ROW_ID kernels draw the dropout mask
-// of output row io for row_id[io], its GLOBAL row, in the row kernel and in a hub's FINISH group alike; the id is loaded once per
-// row after the gather loop.  Without ids (or without dropout) the kernels launched are the ones without the template flag.
+// Rows of a larger graph (row_id_opt of bgnn_gcn_aggregate_f32, a rank's rows of a node partition): ROW_ID kernels draw the
+// dropout mask of output row io for row_id[io], its GLOBAL row, in the row kernel and in a hub's FINISH group alike; the id is
+// loaded once per row after the gather loop.  Without ids (or without dropout) the kernels launched are the ones without the
+// template flag.
 #include "bgnn_conv_common.h"
 
 namespace {
@@ -168,56 +169,6 @@ int dispatch_epi(int epilogue, const GcnParams& p, hipStream_t st) {
 
 int64_t part_ld(int32_t D) { return D < SLICE ? ((int64_t)D + 3) / 4 * 4 : SLICE; }
 
-int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias, const int32_t* rowptr, const int32_t* col,
-             const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D, int epilogue, float p_drop, uint64_t seed,
-             const uint64_t* seed_dev, int32_t hub_threshold, const int32_t* hub_rows, int64_t n_hubs, const int32_t* hub_seg_ptr,
-             const int32_t* seg_bounds, int64_t n_seg, void* ws, size_t ws_bytes, float* out, int64_t ldo, hipStream_t st,
-             const int64_t* row_id = nullptr) {
-  if (!tbl || !rowptr || !col || !dinv || !out) return BGNN_E_NULL;
-  if (n_rows < 0 || n_tbl < 0 || D <= 0 || n_dinv < n_rows || n_dinv < n_tbl) return BGNN_E_SHAPE;
-  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
-  if (!ld_ok(ldt, D) || !ld_ok(ldo, D)) return BGNN_E_ALIGN;
-  if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (bias && !bgnn_aligned16(bias))) return BGNN_E_ALIGN;
-  const bool hubs = n_hubs > 0;
-  if (n_hubs < 0 || n_seg < 0) return BGNN_E_SHAPE;
-  float* part = nullptr;
-  if (hubs) {
-    if (hub_threshold < 1 || n_seg < n_hubs) return BGNN_E_SHAPE;
-    if (!hub_rows || !hub_seg_ptr || !seg_bounds || !ws) return BGNN_E_NULL;
-    if (ws_bytes < (size_t)n_seg * (size_t)part_ld(D) * sizeof(float) + 16) return BGNN_E_WORKSPACE;
-    part = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws), 16));
-  }
-  if (n_rows == 0) return 0;
-  for (int32_t c0 = 0; c0 < D; c0 += SLICE) {
-    GcnParams p{};
-    p.tbl = tbl + c0; p.ldt = ldt; p.n_tbl = n_tbl;
-    p.bias = bias ? bias + c0 : nullptr;
-    p.rowptr = rowptr; p.col = col; p.dinv = dinv; p.n_dinv = n_dinv; p.n_rows = n_rows;
-    p.D = D - c0 < SLICE ? D - c0 : SLICE;
-    p.hub_threshold = hubs ? hub_threshold : 0;
-    p.n_out = n_rows;
-    p.out = out + c0; p.ldo = ldo;
-    drop_consts(p_drop, p.thr, p.keep_scale);
-    p.seed = seed; p.seed_dev = seed_dev; p.d_full = D; p.c0 = c0;
-    p.row_id = row_id;                       // [n_rows]: the row kernel reads row_id[i], a hub's finish group row_id[hub_rows[h]]
-    int rc = dispatch_epi<MODE_ROWS>(epilogue, p, st);
-    if (rc != 0) return rc;
-    if (hubs) {
-      GcnParams s = p;                       // partial rows of the segments (the slice's columns, densely packed)
-      s.bias = nullptr; s.rowptr = seg_bounds; s.n_rows = n_seg; s.hub_threshold = 0;
-      s.out = part; s.ldo = part_ld(D); s.thr = 0u;
-      rc = dispatch_agg<EPI_NONE, MODE_SEGMENT>(s, st);
-      if (rc != 0) return rc;
-      GcnParams f = p;                       // a hub's partial rows in segment order, then the row's scale, bias and epilogue
-      f.tbl = part; f.ldt = part_ld(D); f.n_tbl = n_seg;
-      f.rowptr = hub_seg_ptr; f.col = nullptr; f.n_rows = n_hubs; f.hub_threshold = 0; f.hub_rows = hub_rows;
-      rc = dispatch_epi<MODE_FINISH>(epilogue, f, st);
-      if (rc != 0) return rc;
-    }
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" size_t bgnn_gcn_aggregate_workspace_bytes(int64_t n_seg, int32_t D) {
@@ -230,22 +181,52 @@ extern "C" int bgnn_gcn_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_t
                                       int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
                                       int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
                                       const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
-                                      void* ws_opt, size_t ws_bytes, float* out, int64_t ldo, void* stream) {
-  return agg_impl(tbl, ldt, n_tbl, bias_opt, rowptr, col, dinv, n_dinv, n_rows, D, epilogue, p_drop, seed, seed_dev_opt,
-                  hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, out, ldo,
-                  (hipStream_t)stream);
-}
-
-extern "C" int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias_opt, const int32_t* rowptr,
-                                           const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D,
-                                           int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                           int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
-                                           const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
-                                           void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo,
-                                           void* stream) {
-  return agg_impl(tbl, ldt, n_tbl, bias_opt, rowptr, col, dinv, n_dinv, n_rows, D, epilogue, p_drop, seed, seed_dev_opt,
-                  hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, out, ldo,
-                  (hipStream_t)stream, row_id_opt);
+                                      void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo,
+                                      void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!tbl || !rowptr || !col || !dinv || !out) return BGNN_E_NULL;
+  if (n_rows < 0 || n_tbl < 0 || D <= 0 || n_dinv < n_rows || n_dinv < n_tbl) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
+  if (!ld_ok(ldt, D) || !ld_ok(ldo, D)) return BGNN_E_ALIGN;
+  if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (bias_opt && !bgnn_aligned16(bias_opt))) return BGNN_E_ALIGN;
+  const bool hubs = n_hubs > 0;
+  if (n_hubs < 0 || n_seg < 0) return BGNN_E_SHAPE;
+  float* part = nullptr;
+  if (hubs) {
+    if (hub_threshold < 1 || n_seg < n_hubs) return BGNN_E_SHAPE;
+    if (!hub_rows_opt || !hub_seg_ptr_opt || !seg_bounds_opt || !ws_opt) return BGNN_E_NULL;
+    if (ws_bytes < (size_t)n_seg * (size_t)part_ld(D) * sizeof(float) + 16) return BGNN_E_WORKSPACE;
+    part = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws_opt), 16));
+  }
+  if (n_rows == 0) return 0;
+  for (int32_t c0 = 0; c0 < D; c0 += SLICE) {
+    GcnParams p{};
+    p.tbl = tbl + c0; p.ldt = ldt; p.n_tbl = n_tbl;
+    p.bias = bias_opt ? bias_opt + c0 : nullptr;
+    p.rowptr = rowptr; p.col = col; p.dinv = dinv; p.n_dinv = n_dinv; p.n_rows = n_rows;
+    p.D = D - c0 < SLICE ? D - c0 : SLICE;
+    p.hub_threshold = hubs ? hub_threshold : 0;
+    p.n_out = n_rows;
+    p.out = out + c0; p.ldo = ldo;
+    drop_consts(p_drop, p.thr, p.keep_scale);
+    p.seed = seed; p.seed_dev = seed_dev_opt; p.d_full = D; p.c0 = c0;
+    p.row_id = row_id_opt;                   // [n_rows]: the row kernel reads row_id[i], a hub's finish group row_id[hub_rows[h]]
+    int rc = dispatch_epi<MODE_ROWS>(epilogue, p, st);
+    if (rc != 0) return rc;
+    if (hubs) {
+      GcnParams s = p;                       // partial rows of the segments (the slice's columns, densely packed)
+      s.bias = nullptr; s.rowptr = seg_bounds_opt; s.n_rows = n_seg; s.hub_threshold = 0;
+      s.out = part; s.ldo = part_ld(D); s.thr = 0u;
+      rc = dispatch_agg<EPI_NONE, MODE_SEGMENT>(s, st);
+      if (rc != 0) return rc;
+      GcnParams f = p;                       // a hub's partial rows in segment order, then the row's scale, bias and epilogue
+      f.tbl = part; f.ldt = part_ld(D); f.n_tbl = n_seg;
+      f.rowptr = hub_seg_ptr_opt; f.col = nullptr; f.n_rows = n_hubs; f.hub_threshold = 0; f.hub_rows = hub_rows_opt;
+      rc = dispatch_epi<MODE_FINISH>(epilogue, f, st);
+      if (rc != 0) return rc;
+    }
+  }
+  return 0;
 }
 
 extern "C" int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows,
@@ -273,6 +254,7 @@ extern "C" int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const flo
     if (rc != 0) return rc;
   }
   // the forward walk over the by-source view (every id in t_col is a destination row < n_rows)
-  return agg_impl(g, ldg, n_rows, nullptr, t_rowptr, t_col, dinv, n_dinv, n_src, D, EPI_NONE, 0.f, 0, nullptr, hub_threshold,
-                  hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, grad_tbl, ldgt, st);
+  return bgnn_gcn_aggregate_f32(g, ldg, n_rows, nullptr, t_rowptr, t_col, dinv, n_dinv, n_src, D, EPI_NONE, 0.f, 0, nullptr,
+                                hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes,
+                                nullptr, grad_tbl, ldgt, stream);
 }

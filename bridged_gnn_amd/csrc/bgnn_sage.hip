@@ -137,50 +137,36 @@ int dispatch_agg(const SageParams& p, hipStream_t st) {
                    [&](auto LF, auto EP, auto U) { return launch_agg<LF, EP, U, EPI, ROW_ID, OUT_ROW>(p, st); });
 }
 
-int agg_impl(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root, int64_t ldr, const int32_t* rowptr,
-             const int32_t* col, int64_t n_rows, int32_t D, int mean, int epilogue, float p_drop, uint64_t seed,
-             const uint64_t* seed_dev, float* out, int64_t ldo, hipStream_t st, const int64_t* row_id = nullptr) {
-  if (!tbl || !rowptr || !col || !out) return BGNN_E_NULL;
-  if (n_rows < 0 || n_tbl < 0 || D <= 0) return BGNN_E_SHAPE;
-  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
-  if (!ld_ok(ldt, D) || !ld_ok(ldo, D) || (root && !(ldr == 0 || ld_ok(ldr, D)))) return BGNN_E_ALIGN;
-  if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (root && !bgnn_aligned16(root))) return BGNN_E_ALIGN;
-  if (n_rows == 0) return 0;
-  for (int32_t c0 = 0; c0 < D; c0 += SLICE) {
-    SageParams p{};
-    p.tbl = tbl + c0; p.ldt = ldt; p.n_tbl = n_tbl;
-    p.root = root ? root + c0 : nullptr; p.ldr = ldr;
-    p.rowptr = rowptr; p.col = col; p.n_rows = n_rows;
-    p.D = D - c0 < SLICE ? D - c0 : SLICE;
-    p.mean = mean;
-    p.out = out + c0; p.ldo = ldo;
-    drop_consts(p_drop, p.thr, p.keep_scale);
-    p.seed = seed; p.seed_dev = seed_dev; p.d_full = D; p.c0 = c0;
-    p.row_id = row_id;
-    // the row id only feeds the dropout hash: without dropout (or without ids) the plain kernel runs
-    int rc = epilogue == EPI_RELU ? (row_id != nullptr && p.thr != 0u ? dispatch_agg<EPI_RELU, true>(p, st) : dispatch_agg<EPI_RELU>(p, st))
-           : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX>(p, st) : dispatch_agg<EPI_NONE>(p, st);
-    if (rc != 0) return rc;
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int bgnn_sage_mean_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
                                             const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
                                             int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                            float* out, int64_t ldo, void* stream) {
-  return agg_impl(tbl, ldt, n_tbl, root_opt, ldr, rowptr, col, n_rows, D, mean, epilogue, p_drop, seed, seed_dev_opt, out, ldo,
-                  (hipStream_t)stream);
-}
-
-extern "C" int bgnn_sage_mean_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
-                                                 const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
-                                                 int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                                 const int64_t* row_id_opt, float* out, int64_t ldo, void* stream) {
-  return agg_impl(tbl, ldt, n_tbl, root_opt, ldr, rowptr, col, n_rows, D, mean, epilogue, p_drop, seed, seed_dev_opt, out, ldo,
-                  (hipStream_t)stream, row_id_opt);
+                                            const int64_t* row_id_opt, float* out, int64_t ldo, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!tbl || !rowptr || !col || !out) return BGNN_E_NULL;
+  if (n_rows < 0 || n_tbl < 0 || D <= 0) return BGNN_E_SHAPE;
+  if (const int rc = epi_check(epilogue, p_drop, D)) return rc;
+  if (!ld_ok(ldt, D) || !ld_ok(ldo, D) || (root_opt && !(ldr == 0 || ld_ok(ldr, D)))) return BGNN_E_ALIGN;
+  if (!bgnn_aligned16(tbl) || !bgnn_aligned16(out) || (root_opt && !bgnn_aligned16(root_opt))) return BGNN_E_ALIGN;
+  if (n_rows == 0) return 0;
+  for (int32_t c0 = 0; c0 < D; c0 += SLICE) {
+    SageParams p{};
+    p.tbl = tbl + c0; p.ldt = ldt; p.n_tbl = n_tbl;
+    p.root = root_opt ? root_opt + c0 : nullptr; p.ldr = ldr;
+    p.rowptr = rowptr; p.col = col; p.n_rows = n_rows;
+    p.D = D - c0 < SLICE ? D - c0 : SLICE;
+    p.mean = mean;
+    p.out = out + c0; p.ldo = ldo;
+    drop_consts(p_drop, p.thr, p.keep_scale);
+    p.seed = seed; p.seed_dev = seed_dev_opt; p.d_full = D; p.c0 = c0;
+    p.row_id = row_id_opt;
+    // the row id only feeds the dropout hash: without dropout (or without ids) the plain kernel runs
+    int rc = epilogue == EPI_RELU ? (row_id_opt != nullptr && p.thr != 0u ? dispatch_agg<EPI_RELU, true>(p, st) : dispatch_agg<EPI_RELU>(p, st))
+           : epilogue == EPI_LOGSOFTMAX ? dispatch_agg<EPI_LOGSOFTMAX>(p, st) : dispatch_agg<EPI_NONE>(p, st);
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 extern "C" int bgnn_rows_segment_add_f32(const float* src, int64_t lds, int64_t n_src, const int32_t* seg_ptr,
@@ -239,5 +225,6 @@ extern "C" int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, con
     if (rc != 0) return rc;
   }
   // pass B: plain sum of the scratch rows over the by-source view (every id in t_col is a destination row < n_rows)
-  return agg_impl(s, lds, n_rows, nullptr, 0, t_rowptr, t_col, n_src, D, 0, EPI_NONE, 0.f, 0, nullptr, grad_tbl, ldgt, st);
+  return bgnn_sage_mean_aggregate_f32(s, lds, n_rows, nullptr, 0, t_rowptr, t_col, n_src, D, 0, EPI_NONE, 0.f, 0, nullptr, nullptr,
+                                      grad_tbl, ldgt, stream);
 }

@@ -18,7 +18,8 @@ transform-first as on one GPU (T = x W^T, [., H*C]), so what crosses ranks is OU
   * dropout: the seeds are drawn exactly as `GATConv.run` draws them (`ktgnn.dropout_seed`: per conv the attention seed, then
     the epilogue's) and the kernels hash the whole graph's positions: the feature mask at (GLOBAL row id) * (H*C) + column
     (`row_ids`), the attention mask at (GLOBAL edge position) * H + head (`edge_base`: where the row's first edge sits in the
-    whole graph's by-destination CSR), in the forward and where the backward redraws them; every rank draws the single-GPU masks;
+    whole graph's by-destination CSR), in the forward and where the backward redraws them; every rank draws the single-GPU masks
+    (`row_id_opt` / `edge_base_opt` of the one entry each, bgnn_gat_aggregate_f32 and bgnn_gat_aggregate_bwd_f32, ABI 116);
   * the loss is a sum over the owned rows with the GLOBAL normaliser (`nll_loss`); parameter gradients are summed in ONE
     bucketed all-reduce (`sync_grads`).
 `get_emb` is supported (conv 0 alone: no exchange).  The host pieces (`GatPartition`, `_GatTables`) carry nothing of GAT's
@@ -74,8 +75,7 @@ def _conv_forward(ps, x, wp, att_src, att_dst, bp, resident, cfg, seeds, keep):
     part, g = ps.part, ps.tables
     T = _aligned_rows(_transform(x, wp), H * C)
     if not resident:
-        send = ops.gather_rows(T, g.send_rows) if part.send_rows.shape[0] else T.new_zeros(0, T.shape[1])
-        halo = ps.comm.all_to_all(send, part.send_splits, part.recv_splits)
+        halo = ps.halo_rows(T)
         if part.n_halo:
             T = torch.cat((T, halo))
     s_src, s_dst = ops.gat_scores(T, att_src, att_dst, H, C)
@@ -132,9 +132,7 @@ class _PartGatLayerFn(torch.autograd.Function):
         dTv[:nl].addcmul_(ds_dst.unsqueeze(-1), a_d)
         if not resident:
             # reverse exchange: the halo rows' dT go back to their owners, who add them into their own rows
-            back = ps.comm.all_to_all(dT[nl:], part.recv_splits, part.send_splits)
-            if back.shape[0]:
-                ops.rows_segment_add(back, g.seg_ptr, g.seg_idx, g.seg_row, dT[:nl], D=W, accumulate=True)
+            ps.return_halo(dT[nl:], dT[:nl], W)
             dT = dT[:nl]
         dW = _gram_dw(dT, x)
         gx = _dx(dT, wp) if (ctx.needs_input_grad[0] and not resident) else None

@@ -16,7 +16,8 @@ columns [0, P) and x_r at [P, 2P), P = pad4(H*C).  A halo slot is only ever a SO
     sums that add up under `sync_grads` (the `bns.*` parameters, registered and never applied, have no gradient on any rank and
     are left out of the bucket on every rank alike);
   * dropout: the seeds are drawn exactly as `GATv2Conv.run` draws them (`ktgnn.dropout_seed`: per conv the attention seed, then
-    the epilogue's) and the kernels hash the whole graph's positions (`row_ids`, `edge_base`), in the forward and where the
+    the epilogue's) and the kernels hash the whole graph's positions (`row_ids`, `edge_base`: `row_id_opt` / `edge_base_opt` of
+    the one entry each, bgnn_gatv2_aggregate_f32 and bgnn_gatv2_aggregate_bwd_f32, ABI 116), in the forward and where the
     backward redraws them; every rank draws the single-GPU masks;
   * the loss is a sum over the owned rows with the GLOBAL normaliser (`nll_loss`).
 There is no `get_emb` (the model has none) and no graphed run."""
@@ -45,8 +46,7 @@ def _conv_forward(ps, x, wcat, bcat, att, bp, resident, cfg, seeds, keep):
     P = ops.pad4(H * C)
     T = _aligned_rows(_transform_cat(x, wcat, bcat), 2 * P)
     if not resident:
-        send = ops.gather_rows(T[:, :P], g.send_rows) if part.send_rows.shape[0] else T.new_zeros(0, P)
-        halo = ps.comm.all_to_all(send, part.send_splits, part.recv_splits)
+        halo = ps.halo_rows(T[:, :P])
         if part.n_halo:
             ext = T.new_zeros(part.n_ext, T.shape[1])          # a halo slot's x_r half is never read: 0
             ext[:part.n_local] = T
@@ -96,9 +96,7 @@ class _PartGatv2LayerFn(torch.autograd.Function):
                                                edge_base=g.edge_base if masked else None)
         if not resident:
             # reverse exchange: the x_l half of the halo rows' dT goes back to the owners, who add it into their own rows
-            back = ps.comm.all_to_all(dT[nl:, :P], part.recv_splits, part.send_splits)
-            if back.shape[0]:
-                ops.rows_segment_add(back, g.seg_ptr, g.seg_idx, g.seg_row, dT[:nl, :P], D=P, accumulate=True)
+            ps.return_halo(dT[nl:, :P], dT[:nl, :P], P)
             dT = dT[:nl]
         dW = _gram_dw(dT, x)
         db = ops.column_sums(dT)

@@ -17,8 +17,9 @@ OUTPUT-width: pad4(D) floats per row.
   * hub rows: a destination of >= `ops.GCN_HUB_THRESHOLD` in-edges is a hub on its owner's rank; a hub SOURCE may be a halo slot
     (a node feeding many rows of another rank), so the by-source hub tables cover the extended numbering;
   * dropout: the seeds are drawn exactly as `GCNConv.run` draws them (`ktgnn.dropout_seed`: host generator, one draw per dropout
-    conv per forward) and the kernel hashes (seed, GLOBAL row id * D + column) (`row_ids`), in the row kernel and in a hub's finish
-    pass alike, so every rank draws the masks of the single-GPU step;
+    conv per forward) and the kernel hashes (seed, GLOBAL row id * D + column) (`row_ids`: `row_id_opt` of the one entry
+    bgnn_gcn_aggregate_f32, ABI 116), in the row kernel and in a hub's finish pass alike, so every rank draws the masks of the
+    single-GPU step;
   * the loss is a sum over the owned rows with the GLOBAL normaliser (`nll_loss`); parameter gradients are summed in ONE
     bucketed all-reduce (`sync_grads`).
 `get_emb` / `get_logits` walk the same in-neighbours as `forward` (see gcn.py) and are supported.  Out of scope (raise):
@@ -64,8 +65,7 @@ def _conv_forward(ps, x, wp, bp, D, resident, epilogue, p_drop, seed, seed_dev=N
     part, g = ps.part, ps.tables
     T = _transform(x, wp)
     if not resident:
-        send = ops.gather_rows(T, g.send_rows) if part.send_rows.shape[0] else T.new_zeros(0, T.shape[1])
-        halo = ps.comm.all_to_all(send, part.send_splits, part.recv_splits)
+        halo = ps.halo_rows(T)
         if part.n_halo:
             T = torch.cat((T, halo))
     return ops.gcn_aggregate(T, g.rowptr_local, g.col, g.dinv, part.n_local, D, bias=bp, epilogue=epilogue, p_drop=p_drop,
@@ -103,9 +103,7 @@ class _PartGcnLayerFn(torch.autograd.Function):
                                        want_bias=has_b, hubs=g.t_hubs)
         if not resident:
             # reverse exchange: the halo rows' dT go back to their owners, who add them into their own rows
-            back = ps.comm.all_to_all(dT[nl:], part.recv_splits, part.send_splits)
-            if back.shape[0]:
-                ops.rows_segment_add(back, g.seg_ptr, g.seg_idx, g.seg_row, dT[:nl], D=Dp, accumulate=True)
+            ps.return_halo(dT[nl:], dT[:nl], Dp)
             dT = dT[:nl]
         dW = _gram_dw(dT, x)
         gx = _dx(dT, wp) if (ctx.needs_input_grad[0] and not resident) else None

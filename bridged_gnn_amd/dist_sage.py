@@ -12,7 +12,8 @@ ranks is OUTPUT-width: pad4(D) floats per row.
     backward sends the halo part of dT_l back (the reverse exchange) and the owner folds it into its own dT_l rows with
     `ops.rows_segment_add` (a row sent to k ranks gets k rows back; no atomics, deterministic);
   * dropout: the seeds are drawn exactly as `SAGEConv.run` draws them (host generator, one draw per dropout conv per forward) and
-    the kernel hashes (seed, GLOBAL row id * D + column) (`row_ids`), so every rank draws the masks of the single-GPU step;
+    the kernel hashes (seed, GLOBAL row id * D + column) (`row_ids`: `row_id_opt` of the one entry bgnn_sage_mean_aggregate_f32,
+    ABI 116), so every rank draws the masks of the single-GPU step;
   * the loss is a sum over the owned rows with the GLOBAL normaliser (`nll_loss`): the ranks' shares add up to the reference's
     F.nll_loss; parameter gradients are summed in ONE bucketed all-reduce (`sync_grads`).
 Out of scope (raise): get_emb / get_logits (out-neighbour averaging needs a source partition), normalize=True, log_softmax at
@@ -101,8 +102,7 @@ def _conv_forward(ps, x, wcat, bcat, D, resident, epilogue, p_drop, seed):
     if resident:
         tl = T[:, :Dp]
     else:
-        send = ops.gather_rows(T[:, :Dp], g.send_rows) if part.send_rows.shape[0] else T.new_zeros(0, Dp)
-        halo = ps.comm.all_to_all(send, part.send_splits, part.recv_splits)
+        halo = ps.halo_rows(T[:, :Dp])
         tl = torch.cat((T[:, :Dp], halo)) if part.n_halo else T[:, :Dp]
     y = ops.sage_mean_aggregate(tl, g.rowptr_local, g.col, nl, D, root=T[:nl, Dp:], mean=True, epilogue=epilogue,
                                 p_drop=p_drop, seed=seed, row_ids=g.owned_global if p_drop > 0 else None)
@@ -142,9 +142,7 @@ class _PartSageLayerFn(torch.autograd.Function):
                                     grad_tbl=dT[:, :Dp], grad_root=dT[:nl, Dp:])
         if not resident:
             # reverse exchange: the halo rows' dT_l go back to their owners, who add them into their own rows
-            back = ps.comm.all_to_all(dT[nl:, :Dp], part.recv_splits, part.send_splits)
-            if back.shape[0]:
-                ops.rows_segment_add(back, g.seg_ptr, g.seg_idx, g.seg_row, dT[:nl, :Dp], D=Dp, accumulate=True)
+            ps.return_halo(dT[nl:, :Dp], dT[:nl, :Dp], Dp)
             dT = dT[:nl]
         dW = _gram_dw(dT, x)
         gw_l = dW[:D]
@@ -155,8 +153,8 @@ class _PartSageLayerFn(torch.autograd.Function):
 
 
 class _RankModel:
-    """what the partitioned baselines share: the resident input halo, the loss share and the gradient all-reduce.  A subclass sets
-    model, part, tables (send_rows), comm and `_x_ext = None`."""
+    """what the partitioned baselines share: the resident input halo, a conv's halo exchange and its return, the loss share and
+    the gradient all-reduce.  A subclass sets model, part, tables (send_rows, seg_ptr, seg_idx, seg_row), comm and `_x_ext = None`."""
 
     def _input_ext(self, x_local):
         """[x own rows ; x halo rows] for the current version of the input features: the halo is fetched on first use and again
@@ -176,6 +174,20 @@ class _RankModel:
     def invalidate_input_cache(self):
         """forget the resident input halo (after a write to x that does not advance its version)"""
         self._x_ext = None
+
+    def halo_rows(self, X):
+        """the rows of X [n_local, W] (a row-strided view) that this rank's halo slots stand for, [n_halo, W]: ONE all_to_all"""
+        part = self.part
+        send = ops.gather_rows(X, self.tables.send_rows) if part.send_rows.shape[0] else X.new_zeros(0, X.shape[1])
+        return self.comm.all_to_all(send, part.send_splits, part.recv_splits)
+
+    def return_halo(self, dT_halo, dT_own, W):
+        """the reverse exchange: the halo slots' gradient rows go back to their owners (ONE all_to_all), who add what they get
+        into dT_own over W columns (a row sent to k ranks gets k rows back; no atomics, deterministic)"""
+        part, g = self.part, self.tables
+        back = self.comm.all_to_all(dT_halo, part.recv_splits, part.send_splits)
+        if back.shape[0]:
+            ops.rows_segment_add(back, g.seg_ptr, g.seg_idx, g.seg_row, dT_own, D=W, accumulate=True)
 
     def nll_loss(self, out, y_local, train_mask_local):
         """this rank's share of F.nll_loss(logp[train_mask], y[train_mask]): the owned training rows' terms over the GLOBAL count"""

@@ -959,6 +959,10 @@ def coalesce(edge_index, num_nodes=None):
 SAGE_EPILOGUES = {None: 0, "none": 0, "relu": 1, "log_softmax": 2}
 
 
+def _seed_args(seed, seed_dev):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(seed_dev)
+
+
 def sage_mean_aggregate(tbl, rowptr, col, n_rows, D, root=None, mean=True, epilogue=None, p_drop=0.0, seed=0, seed_dev=None,
                         out=None, row_ids=None):
     """GraphSAGE aggregation (models/backbones.py:440-498, bgnn.h: bgnn_sage_mean_aggregate_f32) ->
@@ -967,21 +971,18 @@ def sage_mean_aggregate(tbl, rowptr, col, n_rows, D, root=None, mean=True, epilo
     a DstCSR (in-neighbours) or its `transposed()` (t_rowptr, t_dst: out-neighbours).  epilogue: None, "relu" (then dropout at
     p_drop with the (seed, element index) hash of `bn_relu_dropout`) or "log_softmax" (D <= 128).
     row_ids: int64 [n_rows], the GLOBAL row id of every output row (a rank's rows of a partition): the dropout element index is
-    then row_ids[i] * D + column, the masks of the whole-graph call (bgnn_sage_mean_aggregate_rows_f32); None = row i itself."""
+    then row_ids[i] * D + column, the masks of the whole-graph call; None = row i itself."""
     n_rows, D = int(n_rows), int(D)
     if out is None:
         out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
     ldr = 0 if root is None else (root.stride(0) if root.shape[0] > 1 else 0)
-    args = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr_rows(root), ldr, L.ptr(rowptr), L.ptr(col), n_rows, D,
-            1 if mean else 0, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            L.ptr(seed_dev) if seed_dev is not None else None)
-    if row_ids is None:
-        rc = L.lib().bgnn_sage_mean_aggregate_f32(*args, L.ptr_rows(out), out.stride(0), L.stream())
-        L.check(rc, "bgnn_sage_mean_aggregate_f32")
-        return out
-    assert row_ids.dtype == torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n_rows and row_ids.is_contiguous()
-    rc = L.lib().bgnn_sage_mean_aggregate_rows_f32(*args, L.ptr(row_ids), L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_sage_mean_aggregate_rows_f32")
+    if row_ids is not None:
+        assert row_ids.dtype == torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n_rows and row_ids.is_contiguous()
+    rc = L.lib().bgnn_sage_mean_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr_rows(root), ldr, L.ptr(rowptr), L.ptr(col), n_rows, D,
+        1 if mean else 0, SAGE_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev), L.ptr(row_ids), L.ptr_rows(out),
+        out.stride(0), L.stream())
+    L.check(rc, "bgnn_sage_mean_aggregate_f32")
     return out
 
 
@@ -1033,7 +1034,7 @@ def gcn_aggregate(tbl, rowptr, col, dinv, n_rows, D, bias=None, epilogue=None, p
     hubs: None (every row is walked by one lane group) or (threshold, hub_rows, hub_seg_ptr, seg_bounds) from
     `DstCSR.hub_tables(threshold, segment)` of the SAME view: those rows are summed segment by segment across the grid.
     row_ids: int64 [n_rows], the GLOBAL row id of every output row (a rank's rows of a partition): the dropout element index is
-    then row_ids[i] * D + column, the masks of the whole-graph call (bgnn_gcn_aggregate_rows_f32); None = row i itself."""
+    then row_ids[i] * D + column, the masks of the whole-graph call; None = row i itself."""
     n_rows, D = int(n_rows), int(D)
     if out is None:
         out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
@@ -1042,16 +1043,13 @@ def gcn_aggregate(tbl, rowptr, col, dinv, n_rows, D, bias=None, epilogue=None, p
     if dinv.dtype != torch.float32 or dinv.dim() != 1:
         raise ValueError("dinv must be float32 [N]")
     hub_args, ws = _gcn_hub_args(hubs, D, tbl.device)
-    args = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(bias), L.ptr(rowptr), L.ptr(col), L.ptr(dinv),
-            int(dinv.shape[0]), n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            L.ptr(seed_dev) if seed_dev is not None else None, *hub_args)
-    if row_ids is None:
-        rc = L.lib().bgnn_gcn_aggregate_f32(*args, L.ptr_rows(out), out.stride(0), L.stream())
-        L.check(rc, "bgnn_gcn_aggregate_f32")
-        return out
-    assert row_ids.dtype == torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n_rows and row_ids.is_contiguous()
-    rc = L.lib().bgnn_gcn_aggregate_rows_f32(*args, L.ptr(row_ids), L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_gcn_aggregate_rows_f32")
+    if row_ids is not None:
+        assert row_ids.dtype == torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n_rows and row_ids.is_contiguous()
+    rc = L.lib().bgnn_gcn_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(bias), L.ptr(rowptr), L.ptr(col), L.ptr(dinv), int(dinv.shape[0]),
+        n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev), *hub_args, L.ptr(row_ids), L.ptr_rows(out),
+        out.stride(0), L.stream())
+    L.check(rc, "bgnn_gcn_aggregate_f32")
     return out
 
 
@@ -1103,13 +1101,36 @@ def _gat_need_rows(t, what, rows, width):
         raise ValueError(f"{what} must be float32 [{rows}, >= {width}] with unit column stride (got {t.dtype} {tuple(t.shape)})")
 
 
-def _gat_need_seed_word(w, what):
-    if w is not None and (w.dtype != torch.int64 or w.numel() != 1):
-        raise ValueError(f"{what} must be an int64 device tensor of one element")
+def _gat_need_bias(bias, HC):
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < HC):
+        raise ValueError("bias must be float32 [>= H*C]")
 
 
-def _seed_args(seed, seed_dev):
-    return int(seed) & 0xFFFFFFFFFFFFFFFF, (L.ptr(seed_dev) if seed_dev is not None else None)
+def _gat_need_seed_words(seed_att_dev, seed_dev):
+    for w, what in ((seed_att_dev, "seed_att_dev"), (seed_dev, "seed_dev")):
+        if w is not None and (w.dtype != torch.int64 or w.numel() != 1):
+            raise ValueError(f"{what} must be an int64 device tensor of one element")
+
+
+def _gat_need_probs(p_att, p_drop):
+    if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
+        raise ValueError("p_att and p_drop must lie in [0, 1)")
+
+
+def _gat_need_csrs(rowptr, col, t_rowptr, t_eid, t_dst, R, N, E):
+    """the backwards' two views of the edges: by destination over R rows, by source over N"""
+    for t, what, n in ((rowptr, "rowptr", R + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
+        _gat_need(t, what, (n,), torch.int32)
+
+
+def _gat_fwd_outputs(n_rows, H, W, epilogue, want_pre, dev):
+    """-> (out, state, pre | None, pre_arg): without an epilogue `pre` IS out, and the entry is handed no second buffer"""
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    state = torch.empty(n_rows, H, 2, dtype=torch.float32, device=dev)
+    pre = None
+    if want_pre:
+        pre = out if GAT_EPILOGUES[epilogue] == 0 else torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    return out, state, pre, (pre if (pre is not None and pre is not out) else None)
 
 
 def _gat_ids_paired(row_ids, edge_base, what):
@@ -1119,14 +1140,13 @@ def _gat_ids_paired(row_ids, edge_base, what):
 
 
 def _gat_ids(row_ids, edge_base, n_rows, dev, what):
-    """the id pair of the `_rows` entry points: int64, contiguous, [n_rows], on the table's device -> given?"""
+    """the id pair, when given: int64, contiguous, [n_rows], on the table's device"""
     if row_ids is None:
-        return False
+        return
     for t, name in ((row_ids, "row_ids"), (edge_base, "edge_base")):
         _gat_need(t, name, (n_rows,), torch.int64)
         if t.device != dev:
             raise ValueError(f"{what}: {name} must be on the table's device {dev} (got {t.device})")
-    return True
 
 
 def gat_scores(tbl, att_src, att_dst, H, C):
@@ -1159,7 +1179,7 @@ def gat_aggregate(tbl, s_src, s_dst, rowptr, col, n_rows, H, C, bias=None, negat
     i*(H*C) + column) or "log_softmax" (H == 1).  bias: float32 [>= H*C], 16-byte aligned, or None.
     -> (out [n_rows, pad4(H*C)], state [n_rows, H, 2] = (max, denominator), pre | None, alpha | None): pre (want_pre) is the conv
     output before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order.
-    row_ids, edge_base: int64 [n_rows] each, given together (a rank's rows of a partition, bgnn_gat_aggregate_rows_f32): the GLOBAL
+    row_ids, edge_base: int64 [n_rows] each, given together (a rank's rows of a partition): the GLOBAL
     id of every output row and the position of its first edge in the whole graph's CSR; the masks are then hashed at
     row_ids[i]*(H*C) + column and (edge_base[i] + (t - rowptr[i]))*H + h, those of the whole-graph call.  None: row i, edge t."""
     _gat_ids_paired(row_ids, edge_base, "gat_aggregate")
@@ -1168,37 +1188,22 @@ def gat_aggregate(tbl, s_src, s_dst, rowptr, col, n_rows, H, C, bias=None, negat
     dev = tbl.device
     if epilogue == "log_softmax" and H != 1:
         raise RuntimeError("gat_aggregate: unsupported shape: the log_softmax epilogue needs heads == 1")
-    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
-        raise ValueError("bias must be float32 [>= H*C]")
+    _gat_need_bias(bias, H * C)
     _gat_need(s_src, "s_src", (int(tbl.shape[0]), H))
     _gat_need(s_dst, "s_dst", (n_rows, H))
     _gat_need(rowptr, "rowptr", (n_rows + 1,), torch.int32)
     _gat_need(col, "col", (E,), torch.int32)
-    ids = _gat_ids(row_ids, edge_base, n_rows, dev, "gat_aggregate")
-    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
-    _gat_need_seed_word(seed_dev, "seed_dev")
-    if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
-        raise ValueError("p_att and p_drop must lie in [0, 1)")
-    W = pad4(H * C)
-    out = torch.empty(n_rows, W, dtype=torch.float32, device=dev)
-    state = torch.empty(n_rows, H, 2, dtype=torch.float32, device=dev)
+    _gat_ids(row_ids, edge_base, n_rows, dev, "gat_aggregate")
+    _gat_need_seed_words(seed_att_dev, seed_dev)
+    _gat_need_probs(p_att, p_drop)
+    out, state, pre, pre_arg = _gat_fwd_outputs(n_rows, H, pad4(H * C), epilogue, want_pre, dev)
     alpha = torch.empty(E, H, dtype=torch.float32, device=dev)       # always formed: the gather pass streams it
-    pre = None
-    if want_pre:
-        pre = out if GAT_EPILOGUES[epilogue] == 0 else torch.empty(n_rows, W, dtype=torch.float32, device=dev)
-    pre_arg = pre if (pre is not None and pre is not out) else None
-    sa, sad = _seed_args(seed_att, seed_att_dev)
-    sf, sfd = _seed_args(seed, seed_dev)
-    head = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E,
-            n_rows, H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd)
-    tail = (L.ptr(state), L.ptr(alpha), None, 0, L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0,
-            L.ptr_rows(out), out.stride(0), L.stream())
-    if ids:
-        rc = L.lib().bgnn_gat_aggregate_rows_f32(*head, L.ptr(row_ids), L.ptr(edge_base), *tail)
-        L.check(rc, "bgnn_gat_aggregate_rows_f32")
-    else:
-        rc = L.lib().bgnn_gat_aggregate_f32(*head, *tail)
-        L.check(rc, "bgnn_gat_aggregate_f32")
+    rc = L.lib().bgnn_gat_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E,
+        n_rows, H, C, float(negative_slope), float(p_att), *_seed_args(seed_att, seed_att_dev), GAT_EPILOGUES[epilogue],
+        float(p_drop), *_seed_args(seed, seed_dev), L.ptr(row_ids), L.ptr(edge_base), L.ptr(state), L.ptr(alpha), None, 0,
+        L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gat_aggregate_f32")
     return out, state, pre, (alpha if return_alpha else None)
 
 
@@ -1212,7 +1217,7 @@ def gat_aggregate_bwd(tbl, s_src, s_dst, state, alpha, pre, grad_y, rowptr, col,
     n_rows: the destination rows when the table holds more sources than that (a rank's extended graph: N = tbl rows = n_ext
     sources, the first n_rows of them the owned rows).  Then s_dst, state, pre, grad_y and rowptr ([n_rows + 1]) are over n_rows,
     s_src and t_rowptr ([N + 1]) over N, and the results are grad_tbl [N, .], ds_src [N, H], ds_dst [n_rows, H].  None: N.
-    row_ids, edge_base: as in `gat_aggregate` (bgnn_gat_aggregate_bwd_rows_f32): both masks are redrawn at the global positions."""
+    row_ids, edge_base: as in `gat_aggregate`: both masks are redrawn at the global positions."""
     _gat_ids_paired(row_ids, edge_base, "gat_aggregate_bwd")
     H, C = _gat_check(tbl, H, C, "gat_aggregate_bwd")
     N, E = int(tbl.shape[0]), int(col.shape[0])
@@ -1227,13 +1232,10 @@ def gat_aggregate_bwd(tbl, s_src, s_dst, state, alpha, pre, grad_y, rowptr, col,
     _gat_need(alpha, "alpha", (E, H))
     _gat_need_rows(pre, "pre", R, W)
     _gat_need_rows(grad_y, "grad_y", R, W)
-    for t, what, n in ((rowptr, "rowptr", R + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
-        _gat_need(t, what, (n,), torch.int32)
-    ids = _gat_ids(row_ids, edge_base, R, dev, "gat_aggregate_bwd")
-    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
-        raise ValueError("bias must be float32 [>= H*C]")
-    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
-    _gat_need_seed_word(seed_dev, "seed_dev")
+    _gat_need_csrs(rowptr, col, t_rowptr, t_eid, t_dst, R, N, E)
+    _gat_ids(row_ids, edge_base, R, dev, "gat_aggregate_bwd")
+    _gat_need_bias(bias, H * C)
+    _gat_need_seed_words(seed_att_dev, seed_dev)
     lib = L.lib()
     g = torch.empty(R, W, dtype=torch.float32, device=dev)
     grad_tbl = torch.empty(N, W, dtype=torch.float32, device=dev)
@@ -1241,19 +1243,13 @@ def gat_aggregate_bwd(tbl, s_src, s_dst, state, alpha, pre, grad_y, rowptr, col,
     ds_dst = torch.empty(R, H, dtype=torch.float32, device=dev)
     wsb = int(lib.bgnn_gat_aggregate_workspace_bytes(E, R, H))
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    sa, sad = _seed_args(seed_att, seed_att_dev)
-    sf, sfd = _seed_args(seed, seed_dev)
-    head = (L.ptr_rows(tbl), tbl.stride(0), N, L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(state), L.ptr(alpha), L.ptr_rows(pre),
-            pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst),
-            E, R, H, C, float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws),
-            ws.numel())
-    tail = (L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(ds_src), L.ptr(ds_dst), L.stream())
-    if ids:
-        rc = lib.bgnn_gat_aggregate_bwd_rows_f32(*head, L.ptr(row_ids), L.ptr(edge_base), *tail)
-        L.check(rc, "bgnn_gat_aggregate_bwd_rows_f32")
-    else:
-        rc = lib.bgnn_gat_aggregate_bwd_f32(*head, *tail)
-        L.check(rc, "bgnn_gat_aggregate_bwd_f32")
+    rc = lib.bgnn_gat_aggregate_bwd_f32(
+        L.ptr_rows(tbl), tbl.stride(0), N, L.ptr(s_src), L.ptr(s_dst), L.ptr(bias), L.ptr(state), L.ptr(alpha), L.ptr_rows(pre),
+        pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst),
+        E, R, H, C, float(negative_slope), float(p_att), *_seed_args(seed_att, seed_att_dev), GAT_EPILOGUES[epilogue], float(p_drop),
+        *_seed_args(seed, seed_dev), L.ptr(ws), ws.numel(), L.ptr(row_ids), L.ptr(edge_base), L.ptr_rows(g), g.stride(0),
+        L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(ds_src), L.ptr(ds_dst), L.stream())
+    L.check(rc, "bgnn_gat_aggregate_bwd_f32")
     return grad_tbl, ds_src, ds_dst, (column_sums(g)[:H * C] if want_bias else None)
 
 
@@ -1285,7 +1281,7 @@ def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slo
     float32 [>= H*C], 16-byte aligned, or None.
     -> (out [n_rows, P], state [n_rows, H, 2] = (max, denominator), pre | None, alpha | None): pre (want_pre) is the conv output
     before the epilogue, alpha (return_alpha) the post-dropout coefficients [E', H] in CSR order.
-    row_ids, edge_base: int64 [n_rows] each, given together (a rank's rows of a partition, bgnn_gatv2_aggregate_rows_f32): the GLOBAL
+    row_ids, edge_base: int64 [n_rows] each, given together (a rank's rows of a partition): the GLOBAL
     id of every output row and the position of its first edge in the whole graph's CSR; the masks are then hashed at
     row_ids[i]*(H*C) + column and (edge_base[i] + (t - rowptr[i]))*H + h, those of the whole-graph call.  None: row i, edge t."""
     _gat_ids_paired(row_ids, edge_base, "gatv2_aggregate")
@@ -1297,37 +1293,22 @@ def gatv2_aggregate(tbl, att, rowptr, col, n_rows, H, C, bias=None, negative_slo
     dev = tbl.device
     if epilogue == "log_softmax" and H != 1:
         raise RuntimeError("gatv2_aggregate: unsupported shape: the log_softmax epilogue needs heads == 1")
-    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
-        raise ValueError("bias must be float32 [>= H*C]")
+    _gat_need_bias(bias, H * C)
     if int(tbl.shape[0]) < n_rows:
         raise ValueError("the table must hold a row for every destination row")
     _gat_need(rowptr, "rowptr", (n_rows + 1,), torch.int32)
     _gat_need(col, "col", (E,), torch.int32)
-    ids = _gat_ids(row_ids, edge_base, n_rows, dev, "gatv2_aggregate")
-    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
-    _gat_need_seed_word(seed_dev, "seed_dev")
-    if not (0.0 <= float(p_att) < 1.0 and 0.0 <= float(p_drop) < 1.0):
-        raise ValueError("p_att and p_drop must lie in [0, 1)")
-    W = pad4(H * C)
-    out = torch.empty(n_rows, W, dtype=torch.float32, device=dev)
-    state = torch.empty(n_rows, H, 2, dtype=torch.float32, device=dev)
+    _gat_ids(row_ids, edge_base, n_rows, dev, "gatv2_aggregate")
+    _gat_need_seed_words(seed_att_dev, seed_dev)
+    _gat_need_probs(p_att, p_drop)
+    out, state, pre, pre_arg = _gat_fwd_outputs(n_rows, H, pad4(H * C), epilogue, want_pre, dev)
     alpha = torch.empty(E, H, dtype=torch.float32, device=dev) if return_alpha else None
-    pre = None
-    if want_pre:
-        pre = out if GAT_EPILOGUES[epilogue] == 0 else torch.empty(n_rows, W, dtype=torch.float32, device=dev)
-    pre_arg = pre if (pre is not None and pre is not out) else None
-    sa, sad = _seed_args(seed_att, seed_att_dev)
-    sf, sfd = _seed_args(seed, seed_dev)
-    head = (L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(a), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows, H, C,
-            float(negative_slope), float(p_att), sa, sad, GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd)
-    tail = (L.ptr(state), L.ptr(alpha), L.ptr_rows(pre_arg), pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out),
-            out.stride(0), L.stream())
-    if ids:
-        rc = L.lib().bgnn_gatv2_aggregate_rows_f32(*head, L.ptr(row_ids), L.ptr(edge_base), *tail)
-        L.check(rc, "bgnn_gatv2_aggregate_rows_f32")
-    else:
-        rc = L.lib().bgnn_gatv2_aggregate_f32(*head, *tail)
-        L.check(rc, "bgnn_gatv2_aggregate_f32")
+    rc = L.lib().bgnn_gatv2_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(a), L.ptr(bias), L.ptr(rowptr), L.ptr(col), E, n_rows, H, C,
+        float(negative_slope), float(p_att), *_seed_args(seed_att, seed_att_dev), GAT_EPILOGUES[epilogue], float(p_drop),
+        *_seed_args(seed, seed_dev), L.ptr(row_ids), L.ptr(edge_base), L.ptr(state), L.ptr(alpha), L.ptr_rows(pre_arg),
+        pre_arg.stride(0) if pre_arg is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gatv2_aggregate_f32")
     return out, state, pre, alpha
 
 
@@ -1339,7 +1320,7 @@ def gatv2_aggregate_bwd(tbl, att, state, pre, grad_y, rowptr, col, t_rowptr, t_e
     grad_att [H*C]; grad_bias [H*C] | None).  (t_rowptr, t_eid, t_dst) = `DstCSR.transposed()`.  The coefficients are rebuilt from
     the state and both dropout masks redrawn from their seeds.  Four launches, no atomics: bit-identical runs.
     n_rows: the destination rows when the table holds more sources than that (a rank's extended graph: N = tbl rows = n_ext
-    sources, the first n_rows of them the owned rows; bgnn_gatv2_aggregate_bwd_rows_f32).  Then state, pre, grad_y and rowptr
+    sources, the first n_rows of them the owned rows).  Then state, pre, grad_y and rowptr
     ([n_rows + 1]) are over n_rows, t_rowptr ([N + 1]) over N, and grad_tbl is [N, 2P] with the dx_r half of the rows n_rows .. N
     exactly 0; grad_att sums this call's edges.  None: N.
     row_ids, edge_base: as in `gatv2_aggregate`: both masks are redrawn at the global positions."""
@@ -1357,32 +1338,23 @@ def gatv2_aggregate_bwd(tbl, att, state, pre, grad_y, rowptr, col, t_rowptr, t_e
     _gat_need(state, "state", (R, H, 2))
     _gat_need_rows(pre, "pre", R, W)
     _gat_need_rows(grad_y, "grad_y", R, W)
-    for t, what, n in ((rowptr, "rowptr", R + 1), (col, "col", E), (t_rowptr, "t_rowptr", N + 1), (t_eid, "t_eid", E), (t_dst, "t_dst", E)):
-        _gat_need(t, what, (n,), torch.int32)
-    ids = _gat_ids(row_ids, edge_base, R, dev, "gatv2_aggregate_bwd")
-    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < H * C):
-        raise ValueError("bias must be float32 [>= H*C]")
-    _gat_need_seed_word(seed_att_dev, "seed_att_dev")
-    _gat_need_seed_word(seed_dev, "seed_dev")
+    _gat_need_csrs(rowptr, col, t_rowptr, t_eid, t_dst, R, N, E)
+    _gat_ids(row_ids, edge_base, R, dev, "gatv2_aggregate_bwd")
+    _gat_need_bias(bias, H * C)
+    _gat_need_seed_words(seed_att_dev, seed_dev)
     lib = L.lib()
     g = torch.empty(R, W, dtype=torch.float32, device=dev)
     grad_tbl = torch.empty(N, 2 * W, dtype=torch.float32, device=dev)
     grad_att = torch.empty(H * C, dtype=torch.float32, device=dev)
     wsb = int(lib.bgnn_gatv2_aggregate_workspace_bytes(E, R, H, C))
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    sa, sad = _seed_args(seed_att, seed_att_dev)
-    sf, sfd = _seed_args(seed, seed_dev)
-    mid = (L.ptr(a), L.ptr(bias), L.ptr(state), L.ptr_rows(pre), pre.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(rowptr),
-           L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E, R, H, C, float(negative_slope), float(p_att), sa, sad,
-           GAT_EPILOGUES[epilogue], float(p_drop), sf, sfd, L.ptr(ws), ws.numel())
-    tail = (L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.ptr(grad_att), L.stream())
-    if ids or R != N:
-        rc = lib.bgnn_gatv2_aggregate_bwd_rows_f32(L.ptr_rows(tbl), tbl.stride(0), N, *mid, L.ptr(row_ids) if ids else None,
-                                                   L.ptr(edge_base) if ids else None, *tail)
-        L.check(rc, "bgnn_gatv2_aggregate_bwd_rows_f32")
-    else:
-        rc = lib.bgnn_gatv2_aggregate_bwd_f32(L.ptr_rows(tbl), tbl.stride(0), *mid, *tail)
-        L.check(rc, "bgnn_gatv2_aggregate_bwd_f32")
+    rc = lib.bgnn_gatv2_aggregate_bwd_f32(
+        L.ptr_rows(tbl), tbl.stride(0), N, L.ptr(a), L.ptr(bias), L.ptr(state), L.ptr_rows(pre), pre.stride(0), L.ptr_rows(grad_y),
+        grad_y.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(t_rowptr), L.ptr(t_eid), L.ptr(t_dst), E, R, H, C, float(negative_slope),
+        float(p_att), *_seed_args(seed_att, seed_att_dev), GAT_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev),
+        L.ptr(ws), ws.numel(), L.ptr(row_ids), L.ptr(edge_base), L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0),
+        L.ptr(grad_att), L.stream())
+    L.check(rc, "bgnn_gatv2_aggregate_bwd_f32")
     return grad_tbl, grad_att, (column_sums(g)[:H * C] if want_bias else None)
 
 

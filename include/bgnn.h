@@ -29,24 +29,25 @@ extern "C" {
  * 111 adds bgnn_adaptedconv_transform_need_f32, 112 bgnn_classifier_stage_f32, 113 bgnn_adaptedconv_aggregate_bounded_f32 (all
  * call-compatible with 110).  The GraphSAGE entry points (bgnn_sage_mean_aggregate_f32, bgnn_sage_mean_aggregate_bwd_f32 and its
  * workspace size) were added later as purely additive symbols: no existing signature changed, so the revision stays 113.  The
- * same holds for the partitioned-GraphSAGE pair bgnn_sage_mean_aggregate_rows_f32 and bgnn_rows_segment_add_f32, and for the
- * similarity-learner pair passes bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size, and for the cosine
- * scorer's bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
+ * same holds for partitioned GraphSAGE's bgnn_rows_segment_add_f32, and for the similarity-learner pair passes
+ * bgnn_pair_mlp_{stats,loss,segsum,eval}_f32 and their workspace size, and for the cosine scorer's
+ * bgnn_pair_cos_{loss,segsum,count}_f32 and their workspace sizes, and for step 2's loss and metric passes
  * bgnn_step2_{loss,loss_bwd,nll,nll_bwd,counts,auc_count}_f32 and their workspace size, and for the GCN baseline's
- * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for partitioned GCN's
- * bgnn_gcn_aggregate_rows_f32, and for the GAT baseline's bgnn_gat_scores_f32, bgnn_gat_aggregate_f32, bgnn_gat_aggregate_bwd_f32 and
- * their workspace size (added after 114 without changing it), and for the GATv2 baseline's bgnn_gatv2_aggregate_f32,
+ * bgnn_gcn_aggregate_f32, bgnn_gcn_aggregate_bwd_f32 and their workspace size, and for the GAT baseline's bgnn_gat_scores_f32,
+ * bgnn_gat_aggregate_f32, bgnn_gat_aggregate_bwd_f32 and their workspace size (added after 114 without changing it), and for the
+ * GATv2 baseline's bgnn_gatv2_aggregate_f32,
  * bgnn_gatv2_aggregate_bwd_f32 and their workspace size (likewise), and for bgnn_adaptedconv_aggregate_queued_f32 with
- * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue), and for partitioned
- * GAT's bgnn_gat_aggregate_rows_f32 and bgnn_gat_aggregate_bwd_rows_f32 (added after 115 without changing it), and for partitioned
- * GATv2's bgnn_gatv2_aggregate_rows_f32 and bgnn_gatv2_aggregate_bwd_rows_f32 (likewise).
+ * bgnn_aggregate_tile_queue_words (a tile queue of a stated size; the older entries keep their 8-word queue).
  * 114 is NOT call-compatible with 113: bgnn_adaptedconv_aggregate_bwd_pull_f32 and bgnn_adaptedconv_aggregate_heads_bwd_f32 take
  * the hub-table argument list for every width (heads: without t_eid), their workspace functions take the segment counts (the
  * single-head one also D), and the _pull_hub_, _pull_wide_ and _heads_bwd_hub_ entries and workspace functions are gone.
  * 115 is NOT call-compatible with 114: bgnn_adaptedconv_transform_f32 takes delta_opt AND sums_opt (exactly one non-NULL), the
  * tail counts, the need mask and the team runs for every caller, and the _transform_sums_, _transform_need_ and
- * _transform_need2_ entries that each took a prefix of that list are gone. */
-#define BGNN_VERSION 115
+ * _transform_need2_ entries that each took a prefix of that list are gone.
+ * 116 is NOT call-compatible with 115: bgnn_sage_mean_aggregate_f32, bgnn_gcn_aggregate_f32, bgnn_gat_aggregate_f32,
+ * bgnn_gat_aggregate_bwd_f32, bgnn_gatv2_aggregate_f32 and bgnn_gatv2_aggregate_bwd_f32 take the ids (and n_src) for every caller;
+ * the _rows_ entries are gone. */
+#define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
 #define BGNN_E_WORKSPACE (-3)   /* ws_bytes smaller than *_workspace_bytes()    */
@@ -469,6 +470,9 @@ int bgnn_adaptedconv_aggregate_heads_wide_bwd_f32(const float* h_t2s, const floa
  * over element index row * D + column, same seed / seed_dev_opt semantics; p_drop > 0 only with epilogue 1); 2 row log_softmax
  * (D <= 128).  Strides ldt / ldr / ldo are in floats, % 4 == 0 and >= pad4(D); pointers 16-B aligned; pad columns of out are
  * written as 0.  D > 128 runs as 128-column slices.
+ * row_id_opt [n_rows] (int64), for a block of rows of a larger graph (a rank's rows of a destination-node partition): every output
+ * row's GLOBAL row id; the dropout element index is then row_id[i] * D + column, so a rank draws exactly the masks of the
+ * whole-graph call.  NULL (or no dropout): row i; the plain kernels run.
  * bgnn_sage_mean_aggregate_bwd_f32: the atomic-free backward of the same call (mean = 1, root present) -- from the forward's output
  * y and grad_y: g = grad_y (epilogue 0), (y > 0 ? grad_y / (1 - p_drop) : 0) (epilogue 1), grad_y - exp(y) * rowsum(grad_y)
  * (epilogue 2); grad_root[i] = g[i] (n_rows rows) and grad_tbl[j] = sum over the out-edges (j -> i) of g[i] / deg_i, walked over
@@ -477,28 +481,20 @@ int bgnn_adaptedconv_aggregate_heads_wide_bwd_f32(const float* h_t2s, const floa
 int bgnn_sage_mean_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
                                  const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
                                  int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                 float* out, int64_t ldo, void* stream);
+                                 const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
 size_t bgnn_sage_mean_aggregate_bwd_workspace_bytes(int64_t n_rows, int32_t D);
 int bgnn_sage_mean_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy,
                                      const int32_t* rowptr, int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col,
                                      int64_t n_src, int32_t D, int epilogue, float p_drop,
                                      float* grad_tbl, int64_t ldgt, float* grad_root, int64_t ldgr,
                                      void* ws, size_t ws_bytes, void* stream);
-/* bgnn_sage_mean_aggregate_rows_f32: bgnn_sage_mean_aggregate_f32 for a block of rows of a larger graph (a rank's rows of a
- * destination-node partition).  row_id_opt [n_rows] (int64) gives every output row its GLOBAL row id; the dropout element index is
- * then row_id[i] * D + column, so a rank draws exactly the masks of the whole-graph call.  With row_id_opt NULL (or no dropout)
- * this is bgnn_sage_mean_aggregate_f32, bit for bit.  Everything else as there.
- * bgnn_rows_segment_add_f32: for a CSR of segments (seg_ptr [n_seg+1], idx = rows of src < n_src, row [n_seg]),
+/* bgnn_rows_segment_add_f32: for a CSR of segments (seg_ptr [n_seg+1], idx = rows of src < n_src, row [n_seg]),
  *     dst[row[s]] = (accumulate ? dst[row[s]] : 0) + sum_{k in [seg_ptr[s], seg_ptr[s+1])} src[idx[k]]
  * over D columns (pad columns up to pad4(D) written as 0).  The row ids must be distinct; an id outside [0, n_dst) is skipped
  * (its segment is never written).  No atomics: one lane group
  * owns a segment and sums it in a fixed order, so the result is bit-identical from run to run.  Empty segments give dst[row[s]]
  * (accumulate) or 0.  lds / ldd in floats, % 4 == 0 and >= pad4(D); src / dst 16-B aligned.  This is how the owner of a row
  * folds the gradient rows that come back from the reverse halo exchange (a row sent to k ranks gets k rows back). */
-int bgnn_sage_mean_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* root_opt, int64_t ldr,
-                                      const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t D, int mean,
-                                      int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                      const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
 int bgnn_rows_segment_add_f32(const float* src, int64_t lds, int64_t n_src, const int32_t* seg_ptr, const int32_t* idx,
                               const int32_t* row, int64_t n_seg, int32_t D, int accumulate, float* dst, int64_t ldd, int64_t n_dst,
                               void* stream);
@@ -521,18 +517,24 @@ int bgnn_rows_segment_add_f32(const float* src, int64_t lds, int64_t n_src, cons
  * into col (`DstCSR.hub_tables`).  One lane group sums a segment into a partial row of ws
  * (bgnn_gcn_aggregate_workspace_bytes(n_seg, D)), then one group per hub adds its partial rows in segment order and applies
  * scale, bias and epilogue: three launches instead of one, and no row is walked by a single group.  n_hubs == 0: one launch.
+ * row_id_opt [n_rows] (int64), for a block of rows of a larger graph (a rank's rows of a destination-node partition; tbl and dinv
+ * then cover the rank's own rows followed by its halo rows): every output row's GLOBAL row id; the dropout element index is then
+ * row_id[i] * D + column, so a rank draws exactly the masks of the whole-graph call -- in the one-launch row kernel, in the finish
+ * pass of a hub row (row_id[hub_rows[h]]) and in every 128-column slice at D > 128.  NULL (or no dropout): row i; the plain kernels
+ * run.
  * bgnn_gcn_aggregate_bwd_f32: the atomic-free backward.  A row pass writes g [n_rows, ldg] from the forward's output y and
  * grad_y (g = grad_y; (y > 0 ? grad_y / (1 - p_drop) : 0); grad_y - exp(y) * rowsum(grad_y)); the caller takes grad_bias as the
  * column sums of g.  By symmetry of the normalisation grad_tbl[j] = dinv[j] * sum_{i : j -> i} dinv[i] * g[i]: the forward
  * walk without bias or epilogue over the by-source view (t_rowptr [n_src+1], t_col = destinations, self loops included; the
- * hub tables are those of that view).  Deterministic bits. */
+ * hub tables are those of that view).  It takes no ids: the mask is recovered from y > 0, and n_rows (rows of g) and n_src (rows
+ * of grad_tbl) are counted separately.  Deterministic bits. */
 size_t bgnn_gcn_aggregate_workspace_bytes(int64_t n_seg, int32_t D);
 int bgnn_gcn_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias_opt, const int32_t* rowptr,
                            const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D,
                            int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
                            int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
                            const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
-                           void* ws_opt, size_t ws_bytes, float* out, int64_t ldo, void* stream);
+                           void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
 int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows,
                                const int32_t* t_rowptr, const int32_t* t_col, const float* dinv, int64_t n_dinv,
                                int64_t n_src, int32_t D, int epilogue, float p_drop,
@@ -540,19 +542,6 @@ int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y,
                                const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
                                void* ws_opt, size_t ws_bytes, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
                                void* stream);
-/* bgnn_gcn_aggregate_rows_f32: bgnn_gcn_aggregate_f32 for a block of rows of a larger graph (a rank's rows of a destination-node
- * partition; tbl and dinv then cover the rank's own rows followed by its halo rows).  row_id_opt [n_rows] (int64) gives every
- * output row its GLOBAL row id; the dropout element index is then row_id[i] * D + column, so a rank draws exactly the masks of the
- * whole-graph call -- in the one-launch row kernel, in the finish pass of a hub row (row_id[hub_rows[h]]) and in every 128-column
- * slice at D > 128.  With row_id_opt NULL (or no dropout) this is bgnn_gcn_aggregate_f32, bit for bit and kernel for kernel.
- * Everything else as there.  The backward needs no counterpart: bgnn_gcn_aggregate_bwd_f32 recovers the mask from y > 0 and takes
- * n_rows (rows of g) and n_src (rows of grad_tbl) separately. */
-int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* bias_opt, const int32_t* rowptr,
-                                const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D,
-                                int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
-                                const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
-                                void* ws_opt, size_t ws_bytes, const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
@@ -588,7 +577,15 @@ int bgnn_gcn_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, co
  * over n_rows, and so is the workspace: bgnn_gat_aggregate_workspace_bytes(n_edges, n_rows, H)) and n_src >= n_rows source rows
  * (tbl, s_src, grad_tbl and ds_src are over n_src, t_rowptr is [n_src+1]); every id in col is < n_src, every id in t_dst < n_rows.
  * On a whole graph n_src == n_rows (self loops make every node both); a rank's extended graph of a partition has its halo slots
- * as further sources without in-edges.  Deterministic bits.  A row's edge range is cut to [0, n_edges] and ids are
+ * as further sources without in-edges.
+ * row_id_opt / edge_base_opt [n_rows] (int64), of both entries, for a block of rows of a larger graph (a rank's rows of a
+ * destination-node partition: tbl and s_src cover the rank's own rows followed by its halo rows, n_src = n_ext in the backward).
+ * Both masks are then drawn where the whole-graph call draws them: row_id is every row's GLOBAL id, the feature-dropout element
+ * index becomes row_id[i]*(H*C) + h*C + c; edge_base is the position of the row's first edge in the WHOLE graph's by-destination
+ * CSR, the attention-dropout element index of edge t of row i becomes (edge_base[i] + (t - rowptr[i])) * H + h -- a rank's rows
+ * must keep the whole graph's edge order inside a row.  The backward redraws both masks from the same ids.  The ids feed the hash
+ * only and never form an address.  NULL (or no dropout): row i, edge t; the plain kernels run.
+ * Deterministic bits.  A row's edge range is cut to [0, n_edges] and ids are
  * checked against their tables: a malformed CSR gives a wrong sum, never a stray access.  The entry points are defined in
  * csrc/bgnn_gat.hip next to their kernels. */
 int bgnn_gat_scores_f32(const float* tbl, int64_t ldt, int64_t n, int32_t H, int32_t C, const float* att_src,
@@ -598,40 +595,18 @@ int bgnn_gat_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const f
                            const float* bias_opt, const int32_t* rowptr, const int32_t* col, int64_t n_edges,
                            int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
                            const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                           const uint64_t* seed_dev_opt, float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes,
-                           float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
+                           const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt, float* state,
+                           float* alpha_out_opt, void* ws_opt, size_t ws_bytes, float* pre_out_opt, int64_t ldp, float* out,
+                           int64_t ldo, void* stream);
 int bgnn_gat_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
                                const float* bias_opt, const float* state, const float* alpha, const float* pre, int64_t ldp,
                                const float* grad_y, int64_t ldgy, const int32_t* rowptr, const int32_t* col,
                                const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges,
                                int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
                                const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                               const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
-                               float* grad_tbl, int64_t ldgt, float* ds_src, float* ds_dst, void* stream);
-/* bgnn_gat_aggregate_rows_f32 / bgnn_gat_aggregate_bwd_rows_f32: the two entries above for a block of rows of a larger graph (a
- * rank's rows of a destination-node partition: tbl and s_src cover the rank's own rows followed by its halo rows, n_src = n_ext in
- * the backward).  Both masks are then drawn where the whole-graph call draws them: row_id_opt [n_rows] (int64) is every row's
- * GLOBAL id, the feature-dropout element index becomes row_id[i]*(H*C) + h*C + c; edge_base_opt [n_rows] (int64) is the position
- * of the row's first edge in the WHOLE graph's by-destination CSR, the attention-dropout element index of edge t of row i becomes
- * (edge_base[i] + (t - rowptr[i])) * H + h -- a rank's rows must keep the whole graph's edge order inside a row.  The backward
- * redraws both masks from the same ids.  The ids feed the hash only and never form an address.  With both pointers NULL (or no
- * dropout) these are bgnn_gat_aggregate_f32 / bgnn_gat_aggregate_bwd_f32, bit for bit and kernel for kernel. */
-int bgnn_gat_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s_src, const float* s_dst,
-                                const float* bias_opt, const int32_t* rowptr, const int32_t* col, int64_t n_edges,
-                                int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                const uint64_t* seed_dev_opt, const int64_t* row_id_opt, const int64_t* edge_base_opt,
-                                float* state, float* alpha_out_opt, void* ws_opt, size_t ws_bytes, float* pre_out_opt, int64_t ldp,
-                                float* out, int64_t ldo, void* stream);
-int bgnn_gat_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* s_src, const float* s_dst,
-                                    const float* bias_opt, const float* state, const float* alpha, const float* pre, int64_t ldp,
-                                    const float* grad_y, int64_t ldgy, const int32_t* rowptr, const int32_t* col,
-                                    const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst, int64_t n_edges,
-                                    int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att, uint64_t seed_att,
-                                    const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                    const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id_opt,
-                                    const int64_t* edge_base_opt, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
-                                    float* ds_src, float* ds_dst, void* stream);
+                               const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, const int64_t* row_id_opt,
+                               const int64_t* edge_base_opt, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt, float* ds_src,
+                               float* ds_dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GATv2 attention conv (the `gnn='GATv2'` baseline of main_graph_knowledge_transfer.py:329-330):
@@ -651,59 +626,46 @@ int bgnn_gat_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src
  * denominator >= 1); alpha_out_opt [n_edges, H]: the coefficients a~ in CSR order (NULL: not formed; the pass parks the logits
  * there and a sweep over the row's own words finishes them, no second gather); pre_out_opt [n_rows, ldp]: the conv output
  * before the epilogue (NULL: not written); out [n_rows, ldo]; pad columns H*C .. P of out and pre_out leave as 0.
- * bgnn_gatv2_aggregate_bwd_f32: the atomic-free backward from (tbl, att, state, pre) and grad_y; here n_rows rows are both sources
- * and destinations (n_src == n_rows; bgnn_gatv2_aggregate_bwd_rows_f32 below counts them separately).  A row pass writes g [n_rows, ldg] and r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]> as GAT's does; a pass
+ * bgnn_gatv2_aggregate_bwd_f32: the atomic-free backward from (tbl, att, state, pre) and grad_y.  A row pass writes g [n_rows, ldg] and r[i,h] = <g[i,h,:], pre[i,h,:] - bias[h,:]> as GAT's does; a pass
  * over the by-destination CSR regathers x_l[j], rebuilds e with the forward's own operations, alpha = exp(e - max) / den,
  * da = mask * <g[i,h,:], x_l[j,h,:]>, de = alpha * (da - r); de and a~ go to ws, grad_tbl[i, P + h*C + c] = sum_t de * att[h,c] *
  * leaky'(m_c), and grad_att[h,c] = sum over all edges of de * leaky(m_c): per block partial rows added in a fixed order by a small
  * second kernel; a pass over the by-source view (t_rowptr, t_eid, t_dst: `DstCSR.transposed()`) gathers g[i] and x_r[i]:
- * grad_tbl[j, h*C + c] = sum a~ * g[i,h,c] + de * att[h,c] * leaky'(x_l[j,h,c] + x_r[i,h,c]).  grad_tbl [n_rows, ldgt >= 2P] is the
- * whole gradient of tbl (pad columns 0); the caller finishes with grad_bias = column sums of g.  No float atomics: two identical
- * calls are bitwise equal.  ws: bgnn_gatv2_aggregate_workspace_bytes(n_edges, n_rows, H, C).  A row's edge range is cut to
+ * grad_tbl[j, h*C + c] = sum a~ * g[i,h,c] + de * att[h,c] * leaky'(x_l[j,h,c] + x_r[i,h,c]).  grad_tbl [n_src, ldgt >= 2P] is the
+ * whole gradient of tbl (pad columns 0); the caller finishes with grad_bias = column sums of g.
+ * Rows and sources are counted separately: n_rows destination rows (rowptr [n_rows+1]; state, pre, grad_y and g are over n_rows,
+ * and so is the workspace: bgnn_gatv2_aggregate_workspace_bytes(n_edges, n_rows, H, C)) and n_src >= n_rows source rows (else
+ * BGNN_E_SHAPE; tbl and grad_tbl are over n_src, t_rowptr is [n_src+1]); every id in col is < n_src, every id in t_dst < n_rows.
+ * On a whole graph n_src == n_rows; a rank's extended graph of a partition has its halo slots as further sources.  The
+ * by-destination pass regathers x_l[j] for j < n_src; the by-source pass walks n_src sources and reads x_r and g of rows < n_rows
+ * only.  The x_r half of grad_tbl (columns [P, 2P)) is written for rows < n_rows and is 0 for the rows n_rows .. n_src (a halo slot
+ * has no in-edges, its x_r is never read); grad_att is the sum over this call's edges.
+ * row_id_opt / edge_base_opt [n_rows] (int64), of both entries, for a block of rows of a larger graph (a rank's rows of a
+ * destination-node partition: tbl covers the rank's own rows followed by its halo rows).  Both masks are then drawn where the
+ * whole-graph call draws them: row_id is every row's GLOBAL id, the feature-dropout element index becomes
+ * row_id[i]*(H*C) + h*C + c; edge_base is the position of the row's first edge in the WHOLE graph's by-destination CSR, the
+ * attention-dropout element index of edge t of row i becomes (edge_base[i] + (t - rowptr[i])) * H + h -- a rank's rows must keep
+ * the whole graph's edge order inside a row.  The two pointers are given together (else BGNN_E_NULL); the ids feed the hash only
+ * and never form an address.  The backward redraws both masks from the same ids.  NULL (or no dropout): row i, edge t; the plain
+ * kernels run.
+ * No float atomics: two identical calls are bitwise equal.  A row's edge range is cut to
  * [0, n_edges] and ids are checked against their tables.  The entry points are defined in csrc/bgnn_gatv2.hip next to their
  * kernels. */
 size_t bgnn_gatv2_aggregate_workspace_bytes(int64_t n_edges, int64_t n_rows, int32_t H, int32_t C);
 int bgnn_gatv2_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
                              const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
                              float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
-                             int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* state,
-                             float* alpha_out_opt, float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
-int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, const float* att, const float* bias_opt, const float* state,
-                                 const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy, const int32_t* rowptr,
-                                 const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid, const int32_t* t_dst,
-                                 int64_t n_edges, int64_t n_rows, int32_t H, int32_t C, float negative_slope, float p_att,
-                                 uint64_t seed_att, const uint64_t* seed_att_dev_opt, int epilogue, float p_drop, uint64_t seed,
-                                 const uint64_t* seed_dev_opt, void* ws, size_t ws_bytes, float* g, int64_t ldg,
+                             int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                             const int64_t* row_id_opt, const int64_t* edge_base_opt, float* state, float* alpha_out_opt,
+                             float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
+int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt,
+                                 const float* state, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
+                                 const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid,
+                                 const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
+                                 float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
+                                 int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, void* ws,
+                                 size_t ws_bytes, const int64_t* row_id_opt, const int64_t* edge_base_opt, float* g, int64_t ldg,
                                  float* grad_tbl, int64_t ldgt, float* grad_att, void* stream);
-/* bgnn_gatv2_aggregate_rows_f32 / bgnn_gatv2_aggregate_bwd_rows_f32: the two entries above for a block of rows of a larger graph (a
- * rank's rows of a destination-node partition: tbl covers the rank's own rows followed by its halo rows).  Both masks are then drawn
- * where the whole-graph call draws them: row_id_opt [n_rows] (int64) is every row's GLOBAL id, the feature-dropout element index
- * becomes row_id[i]*(H*C) + h*C + c; edge_base_opt [n_rows] (int64) is the position of the row's first edge in the WHOLE graph's
- * by-destination CSR, the attention-dropout element index of edge t of row i becomes (edge_base[i] + (t - rowptr[i])) * H + h -- a
- * rank's rows must keep the whole graph's edge order inside a row.  The two pointers are given together (else BGNN_E_NULL); the
- * ids feed the hash only and never form an address.  The backward redraws both masks from the same ids and counts rows and sources
- * separately: n_rows destination rows (rowptr [n_rows+1]; state, pre, grad_y and g are over n_rows, and so is the workspace:
- * bgnn_gatv2_aggregate_workspace_bytes(n_edges, n_rows, H, C)) and n_src >= n_rows source rows (else BGNN_E_SHAPE; tbl and grad_tbl
- * are over n_src, t_rowptr is [n_src+1]); every id in col is < n_src, every id in t_dst < n_rows.  The by-destination pass
- * regathers x_l[j] for j < n_src; the by-source pass walks n_src sources and reads x_r and g of rows < n_rows only.  The x_r half of
- * grad_tbl (columns [P, 2P)) is written for rows < n_rows and is 0 for the rows n_rows .. n_src (a halo slot has no in-edges, its
- * x_r is never read); pad columns are 0; grad_att is the sum over this call's edges.  No float atomics: two identical calls are
- * bitwise equal.  With both pointers NULL (or no dropout) and n_src == n_rows these are bgnn_gatv2_aggregate_f32 /
- * bgnn_gatv2_aggregate_bwd_f32, bit for bit and kernel for kernel. */
-int bgnn_gatv2_aggregate_rows_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* att, const float* bias_opt,
-                                  const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
-                                  float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
-                                  int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                  const int64_t* row_id_opt, const int64_t* edge_base_opt, float* state, float* alpha_out_opt,
-                                  float* pre_out_opt, int64_t ldp, float* out, int64_t ldo, void* stream);
-int bgnn_gatv2_aggregate_bwd_rows_f32(const float* tbl, int64_t ldt, int64_t n_src, const float* att, const float* bias_opt,
-                                      const float* state, const float* pre, int64_t ldp, const float* grad_y, int64_t ldgy,
-                                      const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_eid,
-                                      const int32_t* t_dst, int64_t n_edges, int64_t n_rows, int32_t H, int32_t C,
-                                      float negative_slope, float p_att, uint64_t seed_att, const uint64_t* seed_att_dev_opt,
-                                      int epilogue, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, void* ws,
-                                      size_t ws_bytes, const int64_t* row_id_opt, const int64_t* edge_base_opt, float* g, int64_t ldg,
-                                      float* grad_tbl, int64_t ldgt, float* grad_att, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a2,a3,a5,a6,a7) kNN bridge: pair scoring + per-query top-k.

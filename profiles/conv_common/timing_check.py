@@ -1,5 +1,5 @@
 """The speed criterion of this comparison over the JSON lines in a directory (`<tool>_<parent|branch>_<run>.json` written by
-tools/sage_time.py, tools/gcn_time.py and tools/gat_time.py with --out): every branch median must lie inside the parent's
+tools/sage_time.py, tools/gcn_time.py, tools/gat_time.py and tools/gatv2_time.py with --out): every branch median must lie inside the parent's
 min-to-max range widened by that range's own width on each side.
 
     python profiles/conv_common/timing_check.py profiles/conv_common/timing"""
@@ -17,6 +17,8 @@ FIGURES = {
             "office_epoch_ms.eager", "office_epoch_ms.graphed"),
     "gat": ("shapes.H3C64.fused_fwd_ms", "shapes.H3C64.fused_fwd_bwd_ms", "shapes.H1C2.fused_fwd_ms", "shapes.H1C2.fused_fwd_bwd_ms",
             "office_epoch_ms.eager", "office_epoch_ms.graphed"),
+    "gatv2": ("shapes.H1C64.fused_fwd_ms", "shapes.H1C64.fused_fwd_bwd_ms", "shapes.H1C2.fused_fwd_ms", "shapes.H1C2.fused_fwd_bwd_ms",
+              "office_epoch_ms.eager", "office_epoch_ms.graphed"),
 }
 
 

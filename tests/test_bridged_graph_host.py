@@ -125,4 +125,4 @@ def test_edge_filter_entries_are_declared_and_exported():
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
     assert "bgnn_edge_filter.hip" in _lib._HASHED_SOURCES
     assert _lib.lib().bgnn_quantile_workspace_bytes(1 << 30) <= 16384            # the select's scratch does not grow with n
-    assert _lib.ABI_VERSION == 115
+    assert _lib.ABI_VERSION == 116

@@ -1,14 +1,15 @@
 """CPU: the host side of partitioned GAT (bridged_gnn_amd.dist_gat.GatPartition) -- `SagePartition`'s invariants over A' + I and
 `edge_base`, the position of every owned row's first edge in the whole graph's by-destination CSR, against a numpy stable sort:
 over all ranks the positions edge_base[i] + k cover the whole graph's edges exactly once and name the same sources, which is what
-lets a rank hash the attention dropout where the single-GPU call hashes it; the two new entry points' symbols and bindings, the
-package exports and the wrappers' keywords."""
+lets a rank hash the attention dropout where the single-GPU call hashes it; the one entry per aggregation that takes the ids (ABI
+116: no `_rows` twin), the package exports and the wrappers' keywords."""
 import ctypes
 import inspect
 
 import numpy as np
 import pytest
 
+from test_gatv2_partition_host import _abi_116, _one_entry
 from test_gcn_partition_host import _case, _chunk
 
 
@@ -83,19 +84,15 @@ def test_partition_tables_and_edge_base(graph, world, owner_kind):
 
 
 def test_rows_entries_are_exported_and_bound():
-    from bridged_gnn_amd import _lib
-    lib = ctypes.CDLL(_lib.SO_PATH)
     P = ctypes.c_void_p
-    # forward: the ids sit before the first output (state); backward: before the first output (g), after the workspace
-    res, args = _lib.SIGNATURES["bgnn_gat_aggregate_rows_f32"]
-    plain = _lib.SIGNATURES["bgnn_gat_aggregate_f32"][1]
-    assert hasattr(lib, "bgnn_gat_aggregate_rows_f32")
-    assert res is ctypes.c_int and args == plain[:-9] + [P, P] + plain[-9:]
-    res, args = _lib.SIGNATURES["bgnn_gat_aggregate_bwd_rows_f32"]
-    plain = _lib.SIGNATURES["bgnn_gat_aggregate_bwd_f32"][1]
-    assert hasattr(lib, "bgnn_gat_aggregate_bwd_rows_f32")
-    assert res is ctypes.c_int and args == plain[:-7] + [P, P] + plain[-7:]
-    assert lib.bgnn_version() == 115 == _lib.ABI_VERSION
+    # forward: the ids sit immediately before the first output (state); backward: before the first output (g), after the workspace
+    names, args = _one_entry("bgnn_gat_aggregate_f32", "bgnn_gat_aggregate_rows_f32")
+    assert names[-11:-8] == ["row_id_opt", "edge_base_opt", "state"] and args[-11:-9] == [P, P]
+    assert names[-12] == "seed_dev_opt" and len(names) == 31
+    names, args = _one_entry("bgnn_gat_aggregate_bwd_f32", "bgnn_gat_aggregate_bwd_rows_f32")
+    assert names[-11:-6] == ["ws", "ws_bytes", "row_id_opt", "edge_base_opt", "g"] and args[-9:-7] == [P, P]
+    assert names[:3] == ["tbl", "ldt", "n_src"] and len(names) == 40
+    _abi_116()
 
 
 def test_package_exports_and_wrapper_keywords():

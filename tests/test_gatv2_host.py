@@ -326,25 +326,35 @@ def test_library_exports_the_new_symbols_and_refuses_shapes_outside_the_envelope
     for n in ("bgnn_gatv2_aggregate_workspace_bytes", "bgnn_gatv2_aggregate_f32", "bgnn_gatv2_aggregate_bwd_f32"):
         assert hasattr(raw, n) and n in _lib.SIGNATURES
     lib = _lib.lib()
-    assert lib.bgnn_version() == 115
+    assert lib.bgnn_version() == 116
     assert lib.bgnn_gatv2_aggregate_workspace_bytes(100, 10, 2, 8) >= 2 * 100 * 2 * 4 + 10 * 2 * 4 + 2 * 8 * 4
     buf = np.zeros(64, np.float32)
     P = ctypes.c_void_p(buf.ctypes.data)
     for H, C in ((9, 4), (0, 4), (1, 129), (1, 0)):
         assert lib.bgnn_gatv2_aggregate_workspace_bytes(100, 10, H, C) == 0
-        rc = lib.bgnn_gatv2_aggregate_f32(P, 8, 1, P, None, P, P, 1, 1, H, C, 0.2, 0.0, 0, None, 0, 0.0, 0, None, P, None, None, 0, P,
-                                          8, None)
+        rc = lib.bgnn_gatv2_aggregate_f32(P, 8, 1, P, None, P, P, 1, 1, H, C, 0.2, 0.0, 0, None, 0, 0.0, 0, None, None, None, P, None, None,
+                                          0, P, 8, None)
         assert rc == -2, (H, C, rc)
-        rc = lib.bgnn_gatv2_aggregate_bwd_f32(P, 8, P, None, P, P, 8, P, 8, P, P, P, P, P, 1, 1, H, C, 0.2, 0.0, 0, None, 0, 0.0, 0,
-                                              None, P, 64, P, 8, P, 8, P, None)
+        rc = lib.bgnn_gatv2_aggregate_bwd_f32(P, 8, 1, P, None, P, P, 8, P, 8, P, P, P, P, P, 1, 1, H, C, 0.2, 0.0, 0, None, 0, 0.0, 0,
+                                              None, P, 64, None, None, P, 8, P, 8, P, None)
         assert rc == -2, (H, C, rc)
+
+    def fwd(tbl=P, epi=0, p_drop=0.0, row_id=None, edge_base=None):
+        return lib.bgnn_gatv2_aggregate_f32(tbl, 16, 1, P, None, P, P, 1, 1, 2, 4, 0.2, 0.0, 0, None, epi, p_drop, 0, None, row_id,
+                                            edge_base, P, None, None, 0, P, 8, None)
+
+    def bwd(n_src=1, n_rows=1, row_id=None, edge_base=None):
+        return lib.bgnn_gatv2_aggregate_bwd_f32(P, 16, n_src, P, None, P, P, 8, P, 8, P, P, P, P, P, 1, n_rows, 2, 4, 0.2, 0.0, 0, None,
+                                                0, 0.0, 0, None, P, 64, row_id, edge_base, P, 8, P, 16, P, None)
+
     # the fused log_softmax is for one head; dropout only after the ELU
-    assert lib.bgnn_gatv2_aggregate_f32(P, 16, 1, P, None, P, P, 1, 1, 2, 4, 0.2, 0.0, 0, None, 2, 0.0, 0, None, P, None, None, 0, P, 8,
-                                        None) == -2
-    assert lib.bgnn_gatv2_aggregate_f32(P, 16, 1, P, None, P, P, 1, 1, 2, 4, 0.2, 0.0, 0, None, 0, 0.5, 0, None, P, None, None, 0, P, 8,
-                                        None) == -2
-    assert lib.bgnn_gatv2_aggregate_f32(None, 16, 1, P, None, P, P, 1, 1, 2, 4, 0.2, 0.0, 0, None, 0, 0.0, 0, None, P, None, None, 0, P,
-                                        8, None) == -1
+    assert fwd(epi=2) == -2
+    assert fwd(p_drop=0.5) == -2
+    assert fwd(tbl=None) == -1
+    # the ids are given together, and the sources include the destination rows: refused before any launch
+    assert fwd(row_id=P) == -1 and fwd(edge_base=P) == -1
+    assert bwd(row_id=P) == -1 and bwd(edge_base=P) == -1
+    assert bwd(n_src=0, n_rows=1) == -2 and bwd(n_src=1, n_rows=2) == -2
 
 
 @pytest.mark.skipif(not __import__("oracle.ref_import").ref_import.reference_available(), reason="reference tree not present")

@@ -1,5 +1,5 @@
-"""CPU: the host side of partitioned GATv2 (bridged_gnn_amd.dist_gatv2) -- the two `_rows` entry points' symbols, their ctypes
-bindings against the prototypes of include/bgnn.h, the ABI revision, what `ops.gatv2_aggregate` / `ops.gatv2_aggregate_bwd` refuse
+"""CPU: the host side of partitioned GATv2 (bridged_gnn_amd.dist_gatv2) -- the one entry per aggregation that takes the ids (ABI
+116: no `_rows` twin in the library, the binding or the header), its ctypes binding against the prototype of include/bgnn.h, what `ops.gatv2_aggregate` / `ops.gatv2_aggregate_bwd` refuse
 before anything reaches a device (one id array without the other, ids of another dtype or length, host tensors), the package
 export and the CPU-device refusal of the driver.  The partition itself is `dist_gat.GatPartition`: tests/test_gat_partition_host.py."""
 import ctypes
@@ -28,28 +28,45 @@ def _prototype(name):
     return CTYPE[m.group(1)], types, names
 
 
-def test_rows_entries_are_exported_bound_and_declared():
+def _one_entry(plain, twin):
+    """`plain` is the one entry (exported, bound as bgnn.h declares it) and its former twin is gone from the library, the binding
+    and the header -> the argument names of `plain`"""
     from bridged_gnn_amd import _lib
     lib = ctypes.CDLL(_lib.SO_PATH)
-    P, I64 = ctypes.c_void_p, ctypes.c_int64
-    for name in ("bgnn_gatv2_aggregate_rows_f32", "bgnn_gatv2_aggregate_bwd_rows_f32", "bgnn_gatv2_aggregate_f32",
-                 "bgnn_gatv2_aggregate_bwd_f32"):
-        assert hasattr(lib, name), name
-        res, args, _ = _prototype(name)
-        assert (res, args) == (_lib.SIGNATURES[name][0], list(_lib.SIGNATURES[name][1])), f"{name}: SIGNATURES against bgnn.h"
-    # forward: the plain entry plus the two ids before the first output (state)
-    plain, rows = _prototype("bgnn_gatv2_aggregate_f32"), _prototype("bgnn_gatv2_aggregate_rows_f32")
-    assert rows[1] == plain[1][:-7] + [P, P] + plain[1][-7:]
-    assert rows[2] == plain[2][:-7] + ["row_id_opt", "edge_base_opt"] + plain[2][-7:] and rows[2][-7] == "state"
-    # backward: the plain entry plus n_src after the table's leading dimension and the two ids after the workspace, before g
-    plain, rows = _prototype("bgnn_gatv2_aggregate_bwd_f32"), _prototype("bgnn_gatv2_aggregate_bwd_rows_f32")
-    assert rows[1] == plain[1][:2] + [I64] + plain[1][2:-6] + [P, P] + plain[1][-6:]
-    assert rows[2] == plain[2][:2] + ["n_src"] + plain[2][2:-6] + ["row_id_opt", "edge_base_opt"] + plain[2][-6:]
-    assert rows[2][-6] == "g" and rows[2][-10:-8] == ["ws", "ws_bytes"]
-    assert lib.bgnn_version() == 115 == _lib.ABI_VERSION
+    assert hasattr(lib, plain) and not hasattr(lib, twin), f"{plain} exported, {twin} not"
+    assert plain in _lib.SIGNATURES and twin not in _lib.SIGNATURES
+    assert twin not in open(os.path.join(ROOT, "include", "bgnn.h")).read(), f"{twin} is still named in bgnn.h"
+    res, args, names = _prototype(plain)
+    assert (res, args) == (_lib.SIGNATURES[plain][0], list(_lib.SIGNATURES[plain][1])), f"{plain}: SIGNATURES against bgnn.h"
+    assert len(names) == len(set(names))
+    return names, args
+
+
+def _abi_116():
+    """the library, the binding and the header's revision comment are at 116"""
+    from bridged_gnn_amd import _lib
+    assert ctypes.CDLL(_lib.SO_PATH).bgnn_version() == 116 == _lib.ABI_VERSION
     head = open(os.path.join(ROOT, "include", "bgnn.h")).read()
-    head = head[:head.index("114 is NOT call-compatible")]
-    assert "bgnn_gatv2_aggregate_rows_f32" in head and "bgnn_gatv2_aggregate_bwd_rows_f32" in head, "the revision comment's list"
+    assert "#define BGNN_VERSION 116\n" in head
+    note = " ".join(head[head.index("116 is NOT call-compatible with 115"):head.index("#define BGNN_VERSION")].replace("*", " ").split())
+    assert "take the ids (and n_src) for every caller; the _rows_ entries are gone" in note
+    for name in ("bgnn_sage_mean_aggregate_f32", "bgnn_gcn_aggregate_f32", "bgnn_gat_aggregate_f32", "bgnn_gat_aggregate_bwd_f32",
+                 "bgnn_gatv2_aggregate_f32", "bgnn_gatv2_aggregate_bwd_f32"):
+        assert name in note, name
+
+
+def test_rows_entries_are_exported_bound_and_declared():
+    P, I64 = ctypes.c_void_p, ctypes.c_int64
+    # forward: the two ids sit immediately before the first output (state)
+    names, args = _one_entry("bgnn_gatv2_aggregate_f32", "bgnn_gatv2_aggregate_rows_f32")
+    assert names[-9:-6] == ["row_id_opt", "edge_base_opt", "state"] and args[-9:-7] == [P, P]
+    assert names[-10] == "seed_dev_opt" and len(names) == 28
+    # backward: n_src third, after the table's leading dimension; the two ids after the workspace, immediately before g
+    names, args = _one_entry("bgnn_gatv2_aggregate_bwd_f32", "bgnn_gatv2_aggregate_bwd_rows_f32")
+    assert names[:3] == ["tbl", "ldt", "n_src"] and args[2] is I64
+    assert names[-10:-5] == ["ws", "ws_bytes", "row_id_opt", "edge_base_opt", "g"] and args[-8:-6] == [P, P]
+    assert len(names) == 37
+    _abi_116()
 
 
 def test_wrapper_keywords_and_refusals():

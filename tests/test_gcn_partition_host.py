@@ -1,6 +1,7 @@
 """CPU: the host side of partitioned GCN (bridged_gnn_amd.dist_gcn.GcnPartition) -- the owned rows, the extended CSR of A' + I,
 the global-degree `dinv_ext` of owned rows and halo slots, the send / receive lists and the segment CSR of the gradient return --
-against a numpy brute force and the degrees of test_gcn_host.norm_adj; the new entry point's symbol and the package exports."""
+against a numpy brute force and the degrees of test_gcn_host.norm_adj; the one aggregation entry that takes the row ids (ABI 116:
+no `_rows` twin, for GCN and for GraphSAGE) and the package exports."""
 import ctypes
 import functools
 
@@ -9,6 +10,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from test_gatv2_partition_host import _abi_116, _one_entry
 from test_gcn_host import norm_adj
 
 
@@ -99,12 +101,12 @@ def test_partition_tables(graph, world, owner_kind):
 
 
 def test_rows_entry_is_exported_and_bound():
-    from bridged_gnn_amd import _lib
-    lib = ctypes.CDLL(_lib.SO_PATH)
-    assert hasattr(lib, "bgnn_gcn_aggregate_rows_f32")
-    res, args = _lib.SIGNATURES["bgnn_gcn_aggregate_rows_f32"]
-    plain = _lib.SIGNATURES["bgnn_gcn_aggregate_f32"][1]
-    assert res is ctypes.c_int and args == plain[:-3] + [ctypes.c_void_p] + plain[-3:]     # the ids sit before `out`
+    for plain, twin, n_args in (("bgnn_gcn_aggregate_f32", "bgnn_gcn_aggregate_rows_f32", 26),
+                                ("bgnn_sage_mean_aggregate_f32", "bgnn_sage_mean_aggregate_rows_f32", 18)):
+        names, args = _one_entry(plain, twin)
+        assert names[-4:] == ["row_id_opt", "out", "ldo", "stream"] and args[-4] is ctypes.c_void_p     # the ids sit before `out`
+        assert len(names) == n_args
+    _abi_116()
 
 
 def test_package_exports_and_wrapper_keyword():

@@ -89,7 +89,7 @@ def _bwd(T, att, kept, dy, rowptr, col, tr, H, C, b, p_att, epi, p_drop, **kw):
 
 def _bwd_raw(T, att, kept, dy, rowptr, col, tr, n_src, n_rows, H, C, b, p_att, epi, p_drop, row_ids=None, edge_base=None,
              ws_bytes=None):
-    """bgnn_gatv2_aggregate_bwd_rows_f32 itself, on outputs pre-filled with NaN -> (return code, g, grad_tbl, grad_att)"""
+    """bgnn_gatv2_aggregate_bwd_f32 itself, on outputs pre-filled with NaN -> (return code, g, grad_tbl, grad_att)"""
     from bridged_gnn_amd import _lib as L
     from bridged_gnn_amd import ops
     _, state, pre, _ = kept
@@ -100,7 +100,7 @@ def _bwd_raw(T, att, kept, dy, rowptr, col, tr, n_src, n_rows, H, C, b, p_att, e
     ga = torch.full((H * C,), nan, device=DEV)
     need = int(L.lib().bgnn_gatv2_aggregate_workspace_bytes(E, n_rows, H, C))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=DEV)
-    rc = L.lib().bgnn_gatv2_aggregate_bwd_rows_f32(
+    rc = L.lib().bgnn_gatv2_aggregate_bwd_f32(
         L.ptr_rows(T), T.stride(0), n_src, L.ptr(att.reshape(-1)), L.ptr(b), L.ptr(state), L.ptr_rows(pre), pre.stride(0),
         L.ptr_rows(dy), dy.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(tr[0]), L.ptr(tr[1]), L.ptr(tr[2]), E, n_rows, H, C, 0.2,
         float(p_att), 1234, None, ops.GAT_EPILOGUES[epi], float(p_drop), 99, None, L.ptr(ws), need if ws_bytes is None else ws_bytes,
@@ -222,7 +222,7 @@ def test_extended_graphs_of_a_partition_match_the_whole_graph(H, C):
         rc, g_ref, gt_ref, ga_ref = _bwd_raw(T, att, ref, dy, g.rowptr, g.col, tr, n, n, H, C, b, p_att, epi, p_drop)
         assert rc == 0
         rb = _bwd(T, att, ref, dy, g.rowptr, g.col, tr, H, C, b, p_att, epi, p_drop)
-        assert torch.equal(gt_ref, rb[0]) and torch.equal(ga_ref, rb[1]), tag + ": without ids and halo the _rows entry is the plain one"
+        assert torch.equal(gt_ref, rb[0]) and torch.equal(ga_ref, rb[1]), tag + ": without ids and halo the raw call is the wrapper's"
         dxl = torch.zeros(n, P, dtype=torch.float64, device=DEV)
         datt = torch.zeros(HC, dtype=torch.float64, device=DEV)
         for part, tb in _CACHE["parts"]:

@@ -32,7 +32,7 @@ def test_adam_entry_is_declared_exported_and_bound():
     assert "main_graph_knowledge_transfer.py:205, :67, :353, :274" in open(os.path.join(ROOT, "include", "bgnn.h")).read()
     assert "bgnn_optim.hip" in _lib._HASHED_SOURCES
     assert "bgnn_optim.hip" in open(os.path.join(ROOT, "bridged_gnn_amd", "csrc", "Makefile")).read()
-    assert _lib.ABI_VERSION == 115 and _lib.lib().bgnn_version() == 115
+    assert _lib.ABI_VERSION == 116 and _lib.lib().bgnn_version() == 116
     chunk = _lib.lib().bgnn_adam_chunk_elems()
     assert chunk > 0 and chunk % 4 == 0
 

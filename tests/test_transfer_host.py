@@ -165,7 +165,7 @@ def test_step2_entries_are_bound():
     from bridged_gnn_amd import _lib, ops
     for n in ("loss_workspace_bytes", "loss_f32", "loss_bwd_f32", "nll_f32", "nll_bwd_f32", "counts_f32", "auc_count_f32"):
         assert "bgnn_step2_" + n in _lib.SIGNATURES
-    assert "bgnn_step2.hip" in _lib._HASHED_SOURCES and _lib.ABI_VERSION == 115
+    assert "bgnn_step2.hip" in _lib._HASHED_SOURCES and _lib.ABI_VERSION == 116
     for n in ("step2_loss", "step2_nll", "step2_counts", "step2_auc"):
         assert callable(getattr(ops, n))
     import torch
