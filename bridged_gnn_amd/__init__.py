@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("GATv2", "GATv2Conv"):                 # the GATv2 baseline's, likewise
         from . import gatv2
         return getattr(gatv2, name)
+    if name in ("APPNP", "APPNP_Net"):                 # the APPNP baseline's, likewise
+        from . import appnp
+        return getattr(appnp, name)
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)

@@ -1074,6 +1074,135 @@ def gcn_aggregate_bwd(y, grad_y, t_rowptr, t_col, dinv, n_src, D, epilogue=None,
     return grad_tbl, (column_sums(g)[:D] if want_bias else None)
 
 
+APPNP_EPILOGUES = {None: 0, "none": 0, "log_softmax": 2}
+
+
+def _need_rows_f32(t, what, D):
+    L._check_device(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < D:
+        raise ValueError(f"{what} must be float32 [rows, >= D]")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < pad4(D) or t.data_ptr() % 16 != 0:
+        raise ValueError(f"{what}: rows must have unit column stride, a stride that is a multiple of 4 floats and >= pad4(D), and a "
+                         "16-byte aligned base")
+
+
+def appnp_propagate(h, rowptr, col, dinv, n_rows, D, K, alpha, epilogue=None, hubs=None, out=None):
+    """APPNP propagation (models/backbones.py:110-128, bgnn.h: bgnn_appnp_propagate_f32) -> out [n_rows, pad4(D)] (use out[:, :D]):
+    z_0 = h, z_{k+1} = (1 - alpha) * A^ z_k + alpha * h for k < K, out = epi(z_K), A^ = D^-1/2 (A' + I) D^-1/2 over the CSR of
+    `gcn_aggregate` (one self loop per row; `GcnGraph`: csr.rowptr, col, dinv, hubs) or, for the gradient with respect to h, its
+    by-source view (t_rowptr, t_dst, t_hubs) applied to the output gradient.  h / out: 2-D row-strided views with unit column
+    stride, n_rows rows, distinct.  1 <= D <= 128, K >= 0 (0: epi(h)), 0 <= alpha <= 1 (1: h bit for bit); epilogue None or
+    "log_softmax".  One launch per step (three with `hubs`), no atomics, no host synchronisation."""
+    n_rows, D, K, alpha = int(n_rows), int(D), int(K), float(alpha)
+    if epilogue not in APPNP_EPILOGUES:
+        raise ValueError(f"epilogue must be None or 'log_softmax', got {epilogue!r}")
+    if D < 1:
+        raise ValueError("D must be at least 1")
+    _need_rows_f32(h, "h", D)
+    if h.shape[0] != n_rows:
+        raise ValueError(f"h must have n_rows = {n_rows} rows (the graph is square), got {h.shape[0]}")
+    if dinv.dtype != torch.float32 or dinv.dim() != 1 or dinv.shape[0] < n_rows:
+        raise ValueError("dinv must be float32 [>= n_rows]")
+    if rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.shape[0] < n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
+        raise ValueError("rowptr must be int32 [n_rows + 1] and col int32 [E]")
+    if K < 0:
+        raise ValueError("K must be >= 0")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must lie in [0, 1]")
+    if out is None:
+        out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=h.device)
+    else:
+        _need_rows_f32(out, "out", D)
+        if out.shape[0] != n_rows:
+            raise ValueError(f"out must have n_rows = {n_rows} rows")
+    lib = L.lib()
+    if hubs is None:
+        hub_args, n_seg = (0, None, 0, None, None, 0), 0
+    else:
+        thr, rows, seg_ptr, bounds = hubs
+        n_seg = int(bounds.shape[0]) // 2
+        hub_args = (int(thr), L.ptr(rows), int(rows.shape[0]), L.ptr(seg_ptr), L.ptr(bounds), n_seg)
+    wsb = int(lib.bgnn_appnp_propagate_workspace_bytes(n_rows, D, n_seg))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=h.device)
+    rc = lib.bgnn_appnp_propagate_f32(
+        L.ptr_rows(h), h.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(dinv), int(dinv.shape[0]), n_rows, D, K, alpha,
+        APPNP_EPILOGUES[epilogue], *hub_args, L.ptr(ws), ws.numel(), L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_appnp_propagate_f32")
+    return out
+
+
+def appnp_log_softmax_bwd(y, grad_y, D, out=None):
+    """g = grad_y - exp(y) * rowsum(grad_y) over D <= 128 columns (bgnn.h: bgnn_appnp_log_softmax_bwd_f32): the gradient at z_K of
+    `appnp_propagate(..., epilogue="log_softmax")` from its output y -> g [rows, pad4(D)], pad columns 0; `appnp_propagate` over
+    the by-source view then turns g into the gradient with respect to h."""
+    D = int(D)
+    _need_rows_f32(y, "y", D)
+    _need_rows_f32(grad_y, "grad_y", D)
+    if grad_y.shape[0] != y.shape[0]:
+        raise ValueError("y and grad_y must have the same number of rows")
+    if out is None:
+        out = torch.empty(y.shape[0], pad4(D), dtype=torch.float32, device=y.device)
+    else:
+        _need_rows_f32(out, "out", D)
+    rc = L.lib().bgnn_appnp_log_softmax_bwd_f32(L.ptr_rows(y), y.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), int(y.shape[0]), D,
+                                                L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_appnp_log_softmax_bwd_f32")
+    return out
+
+
+def _fdrop_check(t, what, shape=None):
+    if t.dtype != torch.float32 or t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what} must be float32 [N, D]" + (f" = {tuple(shape)}" if shape is not None else ""))
+    L._check_device(t)
+    if not t.is_contiguous() or t.data_ptr() % 16 != 0:
+        raise ValueError(f"{what} must be contiguous and 16-byte aligned")
+
+
+def feature_dropout(x, p, seed, seed_dev=None, bias=None, relu=False, out=None):
+    """y = drop(act(x + bias)) over a contiguous [N, D] activation of any width (models/backbones.py:110-128: APPNP_Net's
+    F.dropout(x) and F.dropout(F.relu(lin1(x))); bgnn.h: bgnn_feature_dropout_f32).  act = ReLU when `relu`; bias float32 [D] or
+    None; element row * D + column is kept by the (seed + seed_dev, element index) hash of `bn_relu_dropout` and scaled by
+    1 / (1 - p).  0 <= p < 1; `out` may be x."""
+    _fdrop_check(x, "x")
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("p must lie in [0, 1)")
+    N, D = x.shape
+    if D < 1:
+        raise ValueError("x needs at least one column")
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] != D):
+        raise ValueError("bias must be float32 [D]")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _fdrop_check(out, "out", x.shape)
+    rc = L.lib().bgnn_feature_dropout_f32(L.ptr(x), L.ptr(bias), N, D, 1 if relu else 0, float(p), *_seed_args(seed, seed_dev),
+                                          L.ptr(out), L.stream())
+    L.check(rc, "bgnn_feature_dropout_f32")
+    return out
+
+
+def feature_dropout_bwd(grad_y, p, seed, seed_dev=None, y=None, relu=False, out=None):
+    """Backward of `feature_dropout(x, p, seed, seed_dev, bias, relu)` -> grad_x = grad_y * keep / (1 - p) * [act'] (the bias
+    gradient is its column sums).  With `relu` the mask and the ReLU state are read off the forward's output `y` (y > 0 <=> kept
+    and positive); without it the mask is redrawn from the seed and `y` is not needed."""
+    _fdrop_check(grad_y, "grad_y")
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError("p must lie in [0, 1)")
+    if relu:
+        if y is None:
+            raise ValueError("feature_dropout_bwd(relu=True) needs the forward's output y")
+        _fdrop_check(y, "y", grad_y.shape)
+    N, D = grad_y.shape
+    if out is None:
+        out = torch.empty_like(grad_y)
+    else:
+        _fdrop_check(out, "out", grad_y.shape)
+    rc = L.lib().bgnn_feature_dropout_bwd_f32(L.ptr(y) if relu else None, L.ptr(grad_y), N, D, 1 if relu else 0, float(p),
+                                              *_seed_args(seed, seed_dev), L.ptr(out), L.stream())
+    L.check(rc, "bgnn_feature_dropout_bwd_f32")
+    return out
+
+
 GAT_EPILOGUES = {None: 0, "none": 0, "elu": 1, "log_softmax": 2}
 GAT_MAX_HEADS, GAT_MAX_C = 8, 128
 

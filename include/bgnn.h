@@ -46,7 +46,8 @@ extern "C" {
  * _transform_need2_ entries that each took a prefix of that list are gone.
  * 116 is NOT call-compatible with 115: bgnn_sage_mean_aggregate_f32, bgnn_gcn_aggregate_f32, bgnn_gat_aggregate_f32,
  * bgnn_gat_aggregate_bwd_f32, bgnn_gatv2_aggregate_f32 and bgnn_gatv2_aggregate_bwd_f32 take the ids (and n_src) for every caller;
- * the _rows_ entries are gone. */
+ * the _rows_ entries are gone.  The APPNP baseline's bgnn_appnp_propagate_f32 with its workspace size, bgnn_appnp_log_softmax_bwd_f32 and
+ * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 were added after 116 as purely additive symbols. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -542,6 +543,52 @@ int bgnn_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y,
                                const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
                                void* ws_opt, size_t ws_bytes, float* g, int64_t ldg, float* grad_tbl, int64_t ldgt,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * APPNP propagation (the APPNP_Net baseline, models/backbones.py:110-128: an MLP followed by PyG `APPNP(K=10, alpha=0.1)`,
+ * then F.log_softmax): K personalised-PageRank steps over the GCN-normalised graph at class width,
+ *     z_0 = h,   z_{k+1} = (1 - alpha) * A^ z_k + alpha * h   (k = 0 .. K-1),   out = epi(z_K),
+ * A^ = D^-1/2 (A' + I) D^-1/2 over the CSR of bgnn_gcn_aggregate_f32 (exactly one self loop per row, dinv[i] = 1/sqrt(deg_i)).
+ * The graph is square: rowptr [n_rows+1], every id in col < n_rows, h and out have n_rows rows, dinv [n_dinv >= n_rows].
+ * One launch per step on `stream` (three with hub tables), ordered by launch order alone; nothing is allocated and the host
+ * never waits, so a captured graph records the launches.  Between steps the state is kept pre-scaled, s_k = dinv * z_k, in two
+ * [n_rows, pad4(D)] buffers of the workspace that alternate: a step gathers s_k[col[t]] only (the first one reads h and
+ * gathers dinv[col[t]] next to it), forms (1 - alpha) * dinv[i] * sum + alpha * h[i] and stores dinv[i] times that; the last
+ * step stores the value itself, or its row log_softmax.  1 <= D <= 128 (else BGNN_E_SHAPE), K >= 0 (K == 0: out = epi(h)),
+ * 0 <= alpha <= 1 (alpha == 1: out == h bit for bit), epilogue 0 (none) or 2 (row log_softmax).  ld_h / ld_out in floats,
+ * % 4 == 0 and >= pad4(D), h / out 16-B aligned and distinct; pad columns of out are written as 0.
+ * Hub rows: the argument group and the scheme of bgnn_gcn_aggregate_f32 -- the row kernel skips them, one lane group sums
+ * a segment into a partial row of the workspace, one group per hub adds its partial rows in segment order and applies the
+ * step's scaling, teleport term, store and epilogue.  No float atomics: bit-identical from run to run.
+ * ws: bgnn_appnp_propagate_workspace_bytes(n_rows, D, n_seg) bytes (two state buffers + n_seg partial rows; may be NULL when
+ * K <= 1 and n_hubs == 0).
+ * The operator is linear in h and A^ is symmetric in its dinv products, so the gradient of z_K with respect to h is the SAME
+ * call on the by-source view (t_rowptr, t_dst and that view's hub tables) applied to the gradient at z_K, epilogue 0: there
+ * is no _bwd entry.  Under epilogue 2 the caller first forms g = dy - exp(y) * rowsum(dy):
+ * bgnn_appnp_log_softmax_bwd_f32 (models/backbones.py:110-128, the backward of :128's F.log_softmax) is the convs' backward
+ * row pass under its log_softmax rule, y = the forward's output; g is written once and read by every step as the teleport
+ * term.  Leading dimensions and alignment as above, D <= 128; pad columns of g are written as 0. */
+size_t bgnn_appnp_propagate_workspace_bytes(int64_t n_rows, int32_t D, int64_t n_seg);
+int bgnn_appnp_propagate_f32(const float* h, int64_t ld_h, const int32_t* rowptr, const int32_t* col, const float* dinv,
+                             int64_t n_dinv, int64_t n_rows, int32_t D, int32_t K, float alpha, int epilogue,
+                             int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                             const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                             void* ws_opt, size_t ws_bytes, float* out, int64_t ld_out, void* stream);
+int bgnn_appnp_log_softmax_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows, int32_t D,
+                                   float* g, int64_t ldg, void* stream);
+/* Feature dropout of APPNP_Net (models/backbones.py:110-128: F.dropout(x, 0.5) on the input, F.relu + F.dropout(0.5) on the
+ * hidden activation) over a contiguous [n_rows, D] activation of any width, x and y 16-B aligned (y may be x):
+ *     y = drop(act(x + bias)),  act = ReLU when relu != 0,  bias_opt [D] or NULL,
+ * element e = row * D + column kept when the 16 bits of the shared (seed + *seed_dev_opt, e) hash reach round(p_drop * 65536),
+ * kept values scaled by the reciprocal of the quantised keep probability (the contract of bgnn_bn_relu_dropout_f32);
+ * 0 <= p_drop < 1.
+ * bgnn_feature_dropout_bwd_f32 (models/backbones.py:110-128, the backward of the same two sites):
+ * grad_x = grad_y * keep / (1 - p) * [act'], the mask read off y > 0 under ReLU (y required) and redrawn from the seed
+ * otherwise (y_opt unused). */
+int bgnn_feature_dropout_f32(const float* x, const float* bias_opt, int64_t n_rows, int32_t D, int relu, float p_drop,
+                             uint64_t seed, const uint64_t* seed_dev_opt, float* y, void* stream);
+int bgnn_feature_dropout_bwd_f32(const float* y_opt, const float* grad_y, int64_t n_rows, int32_t D, int relu, float p_drop,
+                                 uint64_t seed, const uint64_t* seed_dev_opt, float* grad_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
