@@ -111,8 +111,12 @@ __global__ __launch_bounds__(NT) void colstats_kernel(NormParams p) {
   block_sum8_to_global(v, l, p.D, const_cast<double*>(p.stats));
 }
 
-// batch mean / biased variance of this lane's 4 columns (fp64 from the sums), as fp32 mean and 1/sqrt(var + eps)
-__device__ __forceinline__ void col_consts(const NormParams& p, int64_t n, const double* st /*totals [2*D]*/, int cg, float mean[4], float rstd[4], float ga[4], float be[4]) {
+// batch mean / biased variance of this lane's 4 columns (fp64 from the sums), as an fp32 mean, its low word and 1/sqrt(var + eps).
+// The mean goes as a pair: rounded once to fp32 it sits up to half an ulp off, and under a column of mean / std = 2000 that is
+// 6e-5 of a standard deviation on EVERY row -- inside the forward's bar, but sum g'.xhat adds it up with one sign (its error is
+// that offset times sum g', 1e-4 of the column's value).  x - mean is exact for x within a factor 2 of the mean, so the low word
+// then restores xhat to an fp32 rounding.
+__device__ __forceinline__ void col_consts(const NormParams& p, int64_t n, const double* st /*totals [2*D]*/, int cg, float mean[4], float mlo[4], float rstd[4], float ga[4], float be[4]) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int c = 4 * cg + e;
@@ -120,6 +124,7 @@ __device__ __forceinline__ void col_consts(const NormParams& p, int64_t n, const
     double var = st[p.D + c] / (double)n - m * m;
     var = var > 0.0 ? var : 0.0;
     mean[e] = (float)m;
+    mlo[e] = (float)(m - (double)mean[e]);
     rstd[e] = (float)(1.0 / sqrt(var + (double)p.eps));
     ga[e] = p.gamma ? p.gamma[c] : 1.f;
     be[e] = p.beta ? p.beta[c] : 0.f;
@@ -144,8 +149,8 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(NormParams p) {
     }
   }
   if (!l.on) return;
-  float mean[4], rstd[4], ga[4], be[4];
-  col_consts(p, n, st, l.cg, mean, rstd, ga, be);
+  float mean[4], mlo[4], rstd[4], ga[4], be[4];
+  col_consts(p, n, st, l.cg, mean, mlo, rstd, ga, be);
   for (int64_t r = (int64_t)blockIdx.x * l.rpp + l.rof; r < p.N; r += (int64_t)gridDim.x * l.rpp) {
     const float4 a = *reinterpret_cast<const float4*>(p.x + r * p.ldx + 4 * l.cg);
     float o[4] = {a.x, a.y, a.z, a.w};
@@ -154,7 +159,7 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(NormParams p) {
     const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float t = fmaf((o[e] - mean[e]) * rstd[e], ga[e], be[e]);
+      float t = fmaf(((o[e] - mean[e]) - mlo[e]) * rstd[e], ga[e], be[e]);
       if (p.relu) t = fmaxf(t, 0.f);
       o[e] = bits[e] >= p.thr ? t * p.keep_scale : 0.f;
     }
@@ -164,8 +169,8 @@ __global__ __launch_bounds__(NT) void bn_apply_kernel(NormParams p) {
 
 // g' = dL/d(bn output) = gy * keep_scale where kept and the ReLU is open, else 0
 template <bool SPLIT>
-__device__ __forceinline__ void grad_prime(const NormParams& p, const Lay& l, int64_t r, const float mean[4], const float rstd[4],
-                                           const float ga[4], const float be[4], float xh[4], float gp[4]) {
+__device__ __forceinline__ void grad_prime(const NormParams& p, const Lay& l, int64_t r, const float mean[4], const float mlo[4],
+                                           const float rstd[4], const float ga[4], const float be[4], float xh[4], float gp[4]) {
   const float4 a = *reinterpret_cast<const float4*>(p.x + r * p.ldx + 4 * l.cg);
   const float4 g = *reinterpret_cast<const float4*>(p.gy + r * p.ldg + 4 * l.cg);
   const float xa[4] = {a.x, a.y, a.z, a.w}, gv[4] = {g.x, g.y, g.z, g.w};
@@ -174,7 +179,7 @@ __device__ __forceinline__ void grad_prime(const NormParams& p, const Lay& l, in
   const uint32_t bits[4] = {w0 & 0xFFFFu, w0 >> 16, w1 & 0xFFFFu, w1 >> 16};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    xh[e] = (xa[e] - mean[e]) * rstd[e];
+    xh[e] = ((xa[e] - mean[e]) - mlo[e]) * rstd[e];
     const bool open = !p.relu || fmaf(xh[e], ga[e], be[e]) > 0.f;
     gp[e] = (open && bits[e] >= p.thr) ? gv[e] * p.keep_scale : 0.f;
   }
@@ -188,11 +193,11 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_kernel(NormParams p) {
   load_totals<SPLIT>(p.stats, p.D, st);
   double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (l.on) {
-    float mean[4], rstd[4], ga[4], be[4];
-    col_consts(p, stat_rows<SPLIT>(p), st, l.cg, mean, rstd, ga, be);
+    float mean[4], mlo[4], rstd[4], ga[4], be[4];
+    col_consts(p, stat_rows<SPLIT>(p), st, l.cg, mean, mlo, rstd, ga, be);
     for (int64_t r = (int64_t)blockIdx.x * l.rpp + l.rof; r < p.N; r += (int64_t)gridDim.x * l.rpp) {
       float xh[4], gp[4];
-      grad_prime<SPLIT>(p, l, r, mean, rstd, ga, be, xh, gp);
+      grad_prime<SPLIT>(p, l, r, mean, mlo, rstd, ga, be, xh, gp);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         v[e] += (double)gp[e];
@@ -212,8 +217,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(NormParams p) {
   load_totals<SPLIT>(p.stats, p.D, st);
   load_totals<SPLIT>(p.gsum, p.D, gs);
   if (!l.on) return;
-  float mean[4], rstd[4], ga[4], be[4], c1[4], c2[4];
-  col_consts(p, n, st, l.cg, mean, rstd, ga, be);
+  float mean[4], mlo[4], rstd[4], ga[4], be[4], c1[4], c2[4];
+  col_consts(p, n, st, l.cg, mean, mlo, rstd, ga, be);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     c1[e] = (float)(gs[4 * l.cg + e] / (double)n);
@@ -221,7 +226,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(NormParams p) {
   }
   for (int64_t r = (int64_t)blockIdx.x * l.rpp + l.rof; r < p.N; r += (int64_t)gridDim.x * l.rpp) {
     float xh[4], gp[4], o[4];
-    grad_prime<SPLIT>(p, l, r, mean, rstd, ga, be, xh, gp);
+    grad_prime<SPLIT>(p, l, r, mean, mlo, rstd, ga, be, xh, gp);
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = ga[e] * rstd[e] * (gp[e] - c1[e] - xh[e] * c2[e]);
     *reinterpret_cast<float4*>(p.gx + r * p.ldgx + 4 * l.cg) = make_float4(o[0], o[1], o[2], o[3]);

@@ -1,6 +1,9 @@
 """GPU: step 2's fused loss, metric counts and driver (ops.step2_*, bridged_gnn_amd.transfer) against the reference's own numbers in
 tests/golden/transfer_office_a2d.npz (tools/gen_golden_transfer.py), against fp64 torch on the host, and against a loop composed
-from the existing pieces (model forward, the torch-op loss of bench.py, optimizer.step(), separate eval forwards)."""
+from the existing pieces (model forward, the torch-op loss of bench.py, optimizer.step(), separate eval forwards).
+Past the grid cap of 1024 blocks: the three-table loss at (N, C) = (16389, 31), (16389, 40), (131077, 3), the
+single-table loss at (524295, 2) and (16389, 31), the AUC count at N = 600 011 with and without ties against the integer rank
+statistic on the host; and labels outside [0, C), which select nothing in the loss, the single-table loss and the counts."""
 import os
 import types
 
@@ -128,6 +131,132 @@ def test_single_table_loss(C):
     assert abs(terms[0].item() - ref.item()) <= FWD_RTOL * abs(ref.item()) and terms[1].item() == int(train.sum())
     err, bar = float((s.grad.double().cpu() - s64.grad).abs().max()), GRAD_REL_OF_MAX * float(s64.grad.abs().max())
     assert err <= bar
+
+
+# ---- past the grid cap: every block takes a second trip of its grid-stride loop ------------------------------------------------
+S2_MAX_BLOCKS = 1024                           # bgnn_step2.hip: `constexpr int S2_MAX_BLOCKS = 1024`
+
+
+def s2_blocks_wanted(N, C):
+    """the blocks `s2_blocks` (bgnn_step2.hip) would launch without its cap: 256 / GL rows per block, GL = s2_group(C) lanes per row"""
+    gl = 1
+    while gl < C and gl < 32:
+        gl *= 2
+    return -(-N // (256 // gl))
+
+
+@pytest.mark.parametrize("N,C", [(16389, 31), (16389, 40), (131077, 3)])
+@pytest.mark.parametrize("strided", [False, True])
+def test_loss_past_the_grid_cap(N, C, strided):
+    """forward, backward and the finishing block's sum over all 1024 partial rows"""
+    assert s2_blocks_wanted(N, C) > S2_MAX_BLOCKS
+    (s, t, h), y, train, central = random_case(N, C, 200 + C, strided)
+    assert s.stride(0) == (C + 5 if strided else C)
+    want, wgrads = ref_loss64(s, t, h, y, train, central, Lambda=0.7)
+    loss, terms, grads = run_loss(s, t, h, y, train, central, Lambda=0.7)
+    check_terms(terms[:5].cpu().numpy(), want, f"N={N} C={C} strided={strided}")
+    assert terms[5:7].tolist() == [float(train.sum()), float((train & ~central).sum())]
+    check_grads(grads, wgrads, f"N={N} C={C} strided={strided}")
+    loss2, terms2, grads2 = run_loss(s, t, h, y, train, central, Lambda=0.7)
+    assert torch.equal(terms, terms2) and all(torch.equal(a, b) for a, b in zip(grads, grads2))      # bitwise
+
+
+@pytest.mark.parametrize("N,C", [(524295, 2), (16389, 31)])
+def test_single_table_loss_past_the_grid_cap(N, C):
+    from bridged_gnn_amd import ops
+    # forward: one row per lane (s2_nll_fwd_kernel: s2_blocks(N, 1)), backward: 256 / GL rows per block (s2_nll_bwd_kernel)
+    assert s2_blocks_wanted(N, C) > S2_MAX_BLOCKS and (C != 2 or s2_blocks_wanted(N, 1) > S2_MAX_BLOCKS)
+    (s, _, _), y, train, _ = random_case(N, C, 17, True)
+    s = s.detach().requires_grad_(True)
+    loss, terms = ops.step2_nll(s, y, train, return_terms=True)
+    (loss * 3).backward()
+    s64 = s.detach().double().cpu().requires_grad_(True)
+    ref = F.nll_loss(s64[train.cpu()], y.cpu()[train.cpu()])
+    (ref * 3).backward()
+    assert abs(terms[0].item() - ref.item()) <= FWD_RTOL * abs(ref.item()) and terms[1].item() == int(train.sum())
+    err, bar = float((s.grad.double().cpu() - s64.grad).abs().max()), GRAD_REL_OF_MAX * float(s64.grad.abs().max())
+    print(f"[N={N} C={C}] nll rel err {abs(terms[0].item() - ref.item()) / abs(ref.item()):.3e}, grad max err {err:.3e}, bar {bar:.3e}")
+    assert err <= bar
+
+
+def test_labels_outside_the_classes_select_nothing():
+    """the kernels' contract for y < 0 and y >= C: such a row is in no selection.  Loss terms, row counts and all three gradients,
+    the single-table loss and its gradient and the confusion counts equal, bit for bit, the same calls with those rows cleared
+    from the masks and relabelled 0 -- and the cleared calls meet the fp64 reference."""
+    from bridged_gnn_amd import ops, transfer
+    N, C = 1003, 31
+    (s, t, h), y, train, central = random_case(N, C, 300, True)
+    gen = torch.Generator().manual_seed(301)
+    u = torch.rand(N, generator=gen).to(DEV)
+    bad = train & (u < 0.05)
+    low = bad & (torch.rand(N, generator=gen).to(DEV) < 0.5)
+    assert 10 <= int(bad.sum()) and 0 < int(low.sum()) < int(bad.sum()) and bool((bad & ~central).any()) and bool((bad & central).any())
+    y_bad = torch.where(low, torch.full_like(y, -1), torch.where(bad, torch.full_like(y, C), y))
+    y_clr, train_clr = torch.where(bad, torch.zeros_like(y), y), train & ~bad
+    # the three-table loss
+    loss, terms, grads = run_loss(s, t, h, y_bad, train, central, Lambda=0.7)
+    loss_c, terms_c, grads_c = run_loss(s, t, h, y_clr, train_clr, central, Lambda=0.7)
+    assert torch.equal(terms, terms_c) and torch.equal(loss.detach(), loss_c.detach())
+    assert all(torch.equal(a, b) for a, b in zip(grads, grads_c))
+    want, wgrads = ref_loss64(s, t, h, y_clr, train_clr, central, Lambda=0.7)
+    check_terms(terms_c[:5].cpu().numpy(), want, "cleared labels")
+    check_grads(grads_c, wgrads, "cleared labels")
+    assert terms_c[5:7].tolist() == [float(train_clr.sum()), float((train_clr & ~central).sum())]
+    # the single-table loss
+    outs = []
+    for yy, mm in ((y_bad, train), (y_clr, train_clr)):
+        sv = s.detach().requires_grad_(True)
+        l1, t1 = ops.step2_nll(sv, yy, mm, return_terms=True)
+        (l1 * 3).backward()
+        outs.append((t1, sv.grad))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    s64 = s.detach().double().cpu().requires_grad_(True)
+    ref = F.nll_loss(s64[train_clr.cpu()], y_clr.cpu()[train_clr.cpu()])
+    (ref * 3).backward()
+    assert abs(outs[1][0][0].item() - ref.item()) <= FWD_RTOL * abs(ref.item()) and outs[1][0][1].item() == int(train_clr.sum())
+    assert float((outs[1][1].double().cpu() - s64.grad).abs().max()) <= GRAD_REL_OF_MAX * float(s64.grad.abs().max())
+    # the confusion counts: the bad rows sit in selection 0 (train) and, some of them, in the two others
+    bits = [train, (u < 0.3) & ~central, ((u > 0.5) | bad) & ~central]
+    assert all(bool((b & bad).any()) for b in bits)
+    bits_clr = [b & ~bad for b in bits]
+
+    def pack(bs):
+        return (bs[0].to(torch.uint8) | (bs[1].to(torch.uint8) << 1) | (bs[2].to(torch.uint8) << 2)).contiguous()
+    combos = transfer._DTC_COMBOS
+    got = ops.step2_counts((s, t, h), y_bad, pack(bits), combos)
+    got_c = ops.step2_counts((s, t, h), y_clr, pack(bits_clr), combos)
+    assert torch.equal(got, got_c) and torch.equal(got_c, bincount_counts((s, t, h), y_clr, bits_clr, combos, C))
+
+
+def auc_by_ranks(score, y, sel):
+    """roc_auc_score(y[sel], score[sel]) as its integer rank statistic on the host: over (positive, negative) pairs, 2 per negative
+    below the positive and 1 per negative level with it, in int64, then one fp64 quotient"""
+    score, y, sel = (v.cpu().numpy() for v in (score, y, sel))
+    neg = np.sort(score[sel & (y == 0)])
+    pos = score[sel & (y == 1)]
+    below = np.searchsorted(neg, pos, side="left").astype(np.int64)
+    upto = np.searchsorted(neg, pos, side="right").astype(np.int64)
+    u2 = int((2 * below + (upto - below)).sum())
+    return u2 / (2.0 * pos.shape[0] * neg.shape[0]), pos.shape[0], neg.shape[0]
+
+
+@pytest.mark.parametrize("ties", [False, True])
+def test_auc_past_one_trip_of_the_grid(ties):
+    from bridged_gnn_amd import ops
+    N = 600_011
+    assert N > S2_MAX_BLOCKS * 256                 # s2_auc_kernel: one row per lane, s2_blocks(N, 1) blocks
+    gen = torch.Generator().manual_seed(400)
+    y = torch.randint(0, 2, (N,), generator=gen)
+    score = torch.rand(N, generator=gen) + 0.1 * y  # positives score a little higher: an AUC away from 1/2
+    if ties:
+        score = torch.round(score * 64) / 64       # 72 distinct scores at the most: every positive has thousands of level negatives
+    sel = torch.rand(N, generator=gen) < 0.5
+    ref, n_pos, n_neg = auc_by_ranks(score, y, sel)
+    assert min(n_pos, n_neg) > 100_000 and 0.55 < ref < 0.75
+    assert score.dtype == torch.float32 and (np.unique(score.numpy()).shape[0] <= 72) == ties
+    got = float(ops.step2_auc(score.to(DEV), y.to(DEV), sel.to(DEV)))
+    print(f"ties={ties}: auc {got!r}, rank statistic {ref!r}")
+    assert abs(got - ref) <= 1e-12
 
 
 def bincount_counts(tabs, y, sel_bits, combos, C):
