@@ -33,4 +33,7 @@ def __getattr__(name):
     if name == "PartitionedGATv2":                     # the GATv2 baseline on the same partition
         from . import dist_gatv2
         return dist_gatv2.PartitionedGATv2
+    if name in ("PartitionedAPPNP", "AppnpPartition"):     # the APPNP baseline on a node partition (two partitions: A and A^T)
+        from . import dist_appnp
+        return getattr(dist_appnp, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -163,31 +163,32 @@ class APPNP(nn.Module):
 
 
 class _FeatureDropFn(torch.autograd.Function):
-    """y = drop(relu?(x)) on the streaming HIP pass; the backward reads the mask off y (ReLU) or redraws it from the seed."""
+    """y = drop(relu?(x)) on the streaming HIP pass; the backward reads the mask off y (ReLU) or redraws it from the seed.
+    row_ids: the global row of every row (a rank's rows of a partition draw the whole-graph masks), or None."""
 
     @staticmethod
-    def forward(ctx, x, p, seed, seed_dev, relu):
-        y = ops.feature_dropout(_flat4(x.detach()), p, seed, seed_dev, relu=relu)
+    def forward(ctx, x, p, seed, seed_dev, relu, row_ids=None):
+        y = ops.feature_dropout(_flat4(x.detach()), p, seed, seed_dev, relu=relu, row_ids=row_ids)
         if relu:
             ctx.save_for_backward(y)           # the node's own output: kept as a saved tensor, never as an attribute (a cycle
-        ctx.cfg, ctx.seed_dev = (p, seed, relu), seed_dev     # output -> node -> output would keep the graph above it alive)
+        ctx.cfg, ctx.seed_dev = (p, seed, relu, row_ids), seed_dev     # output -> node -> output would keep the graph above it alive)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        p, seed, relu = ctx.cfg
+        p, seed, relu, row_ids = ctx.cfg
         y = ctx.saved_tensors[0] if relu else None
-        return ops.feature_dropout_bwd(_flat4(gy), p, seed, ctx.seed_dev, y=y, relu=relu), None, None, None, None
+        return ops.feature_dropout_bwd(_flat4(gy), p, seed, ctx.seed_dev, y=y, relu=relu, row_ids=row_ids), None, None, None, None, None
 
 
-def _feature_drop(x, p, relu):
+def _feature_drop(x, p, relu, row_ids=None):
     """one dropout site: takes its seed (in forward order) only where a mask is drawn"""
     if p <= 0 and not relu:
         return x
     seed, seed_dev = dropout_seed(p, step_word=False)        # a captured epoch: 0 and this site's device word
     if torch.is_grad_enabled() and x.requires_grad:
-        return _FeatureDropFn.apply(x, float(p), seed, seed_dev, relu)
-    return ops.feature_dropout(_flat4(x.detach()), float(p), seed, seed_dev, relu=relu)
+        return _FeatureDropFn.apply(x, float(p), seed, seed_dev, relu, row_ids)
+    return ops.feature_dropout(_flat4(x.detach()), float(p), seed, seed_dev, relu=relu, row_ids=row_ids)
 
 
 class APPNP_Net(nn.Module):

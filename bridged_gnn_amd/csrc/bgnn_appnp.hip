@@ -21,9 +21,13 @@
 // kernel skips rows of at least hub_threshold edges, SEGMENT mode sums a (begin, end) segment into a partial row, FINISH mode
 // adds a hub's partial rows in segment order and applies the step's scaling, teleport term, store and epilogue).  One launch
 // per step (three with hubs) on the caller's stream; steps are ordered by launch order alone.  No float atomics.
+// bgnn_appnp_step_f32 is that per-step launch sequence (run_step) as an entry of its own, over a rectangular graph: n_rows owned
+// rows gather from a table of n_tbl >= n_rows rows (owned rows, then halo slots), so that a rank of a node partition can exchange
+// the halo rows of the state between steps.
 //
 // Feature dropout: streaming passes over a contiguous [N, D] activation of any width, four consecutive elements per lane
 // (16-byte accesses; element index = row * D + column = the flat index, so a quad shares one word pair of the dropout hash).
+// The _rows_ passes take the GLOBAL row of every local row and hash row_ids[r] * D + column: a rank's rows draw the whole-graph masks.
 #include "bgnn_conv_common.h"
 
 namespace {
@@ -163,6 +167,31 @@ int dispatch_step(bool first, int store, const AppnpParams& p, hipStream_t st) {
 int64_t pad4_ld(int32_t D) { return ((int64_t)D + 3) / 4 * 4; }
 size_t state_floats(int64_t n_rows, int32_t D) { return (size_t)n_rows * (size_t)pad4_ld(D); }
 
+// the hub argument group of one step; n_hubs == 0: every row is walked by the row kernel
+struct HubTables {
+  int32_t threshold; const int32_t* rows; int64_t n_hubs; const int32_t* seg_ptr; const int32_t* seg_bounds; int64_t n_seg;
+  float* part;                                     // [n_seg, pad4(D)] partial rows
+};
+
+// one step of the recurrence over p's graph (p: the ROWS launch with tbl, h, out and the CSR set; hub_threshold is set here): the
+// row launch and, with hub tables, the segment and finish launches.  The K-step entry and bgnn_appnp_step_f32 both run this.
+int run_step(AppnpParams p, bool first, int store, const HubTables& ht, hipStream_t st) {
+  const bool hubs = ht.n_hubs > 0;
+  p.hub_threshold = hubs ? ht.threshold : 0;
+  int rc = dispatch_step<MODE_ROWS>(first, store, p, st);
+  if (rc != 0 || !hubs) return rc;
+  const int64_t ldw = pad4_ld(p.D);
+  AppnpParams s = p;                         // partial rows of the segments
+  s.rowptr = ht.seg_bounds; s.n_rows = ht.n_seg; s.hub_threshold = 0;
+  s.out = ht.part; s.ldo = ldw;
+  rc = first ? dispatch_lf<MODE_SEGMENT, true, STORE_STATE>(s, st) : dispatch_lf<MODE_SEGMENT, false, STORE_STATE>(s, st);
+  if (rc != 0) return rc;
+  AppnpParams f = p;                         // a hub's partial rows in segment order, then the step's scaling, teleport and store
+  f.tbl = ht.part; f.ldt = ldw; f.n_tbl = ht.n_seg;
+  f.rowptr = ht.seg_ptr; f.col = nullptr; f.n_rows = ht.n_hubs; f.hub_threshold = 0; f.hub_rows = ht.rows;
+  return dispatch_step<MODE_FINISH>(first, store, f, st);
+}
+
 // ---- feature dropout ---------------------------------------------------------------------------------------------------------
 struct FdropParams {
   const float* x;            // forward: the input; backward: y (read only under ReLU)
@@ -173,6 +202,51 @@ struct FdropParams {
   float* y;                  // forward: the output; backward: grad_x
 };
 
+// one quad (elements e .. e+3 of the flat activation) of a pass: load, bias and activation (forward) or the gradient (backward),
+// the mask through drop(o), store.  col_of(): the column of element e, asked for only where a bias is added.
+template <bool RELU, bool BWD, class ColOf, class Drop>
+__device__ __forceinline__ void fdrop_quad(const FdropParams& p, int64_t e, ColOf col_of, Drop drop) {
+  const bool full = e + 3 < p.total;                            // the last quad of a tensor of total % 4 != 0 goes element by element
+  float v[4] = {0.f, 0.f, 0.f, 0.f}, d[4] = {0.f, 0.f, 0.f, 0.f};
+  const bool need_v = !BWD || RELU;
+  if (full) {
+    if (need_v) { const float4 t = *reinterpret_cast<const float4*>(p.x + e); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    if (BWD) { const float4 t = *reinterpret_cast<const float4*>(p.gy + e); d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w; }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) if (e + c < p.total) { if (need_v) v[c] = p.x[e + c]; if (BWD) d[c] = p.gy[e + c]; }
+  }
+  float o[4];
+  if (BWD && RELU) {
+    // ReLU then dropout: y > 0 <=> kept and positive
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = v[c] > 0.f ? d[c] * p.keep_scale : 0.f;
+  } else {
+    if (!BWD) {
+      if (p.bias != nullptr) {
+        int32_t col = col_of();
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (e + c < p.total) v[c] += p.bias[col];
+          if (++col == p.D) col = 0;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = RELU ? fmaxf(v[c], 0.f) : v[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = d[c];
+    }
+    if (p.thr != 0u) drop(o);
+  }
+  if (full) {
+    *reinterpret_cast<float4*>(p.y + e) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) if (e + c < p.total) p.y[e + c] = o[c];
+  }
+}
+
 template <bool RELU, bool BWD>
 __global__ __launch_bounds__(256) void feature_dropout_kernel(FdropParams p) {
   uint64_t seed = p.seed;
@@ -180,45 +254,8 @@ __global__ __launch_bounds__(256) void feature_dropout_kernel(FdropParams p) {
   const int64_t nquad = (p.total + 3) >> 2;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t e = q << 2;
-    const bool full = e + 3 < p.total;                          // the last quad of a tensor of total % 4 != 0 goes element by element
-    float v[4] = {0.f, 0.f, 0.f, 0.f}, d[4] = {0.f, 0.f, 0.f, 0.f};
-    const bool need_v = !BWD || RELU;
-    if (full) {
-      if (need_v) { const float4 t = *reinterpret_cast<const float4*>(p.x + e); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-      if (BWD) { const float4 t = *reinterpret_cast<const float4*>(p.gy + e); d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w; }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (e + c < p.total) { if (need_v) v[c] = p.x[e + c]; if (BWD) d[c] = p.gy[e + c]; }
-    }
-    float o[4];
-    if (BWD && RELU) {
-      // ReLU then dropout: y > 0 <=> kept and positive
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[c] = v[c] > 0.f ? d[c] * p.keep_scale : 0.f;
-    } else {
-      if (!BWD) {
-        if (p.bias != nullptr) {
-          int32_t col = (int32_t)(e % p.D);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            if (e + c < p.total) v[c] += p.bias[col];
-            if (++col == p.D) col = 0;
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o[c] = RELU ? fmaxf(v[c], 0.f) : v[c];
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o[c] = d[c];
-      }
-      if (p.thr != 0u) drop4(o, (uint64_t)e, true, seed, p.thr, p.keep_scale);
-    }
-    if (full) {
-      *reinterpret_cast<float4*>(p.y + e) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) if (e + c < p.total) p.y[e + c] = o[c];
-    }
+    fdrop_quad<RELU, BWD>(p, e, [&] { return (int32_t)(e % p.D); },
+                          [&](float (&o)[4]) { drop4(o, (uint64_t)e, true, seed, p.thr, p.keep_scale); });
   }
 }
 
@@ -228,6 +265,64 @@ int launch_fdrop(const FdropParams& p, hipStream_t st) {
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL((feature_dropout_kernel<RELU, BWD>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
+// The same pass over a rank's rows of a partitioned activation: element (r, c) draws the bits of flat element
+// row_ids[r] * D + c, the whole-graph call's.  The data are still walked as quads of the local flat index (16-byte accesses);
+// one division per quad splits it into (row, column), the other three elements follow by increment and wrap.
+// ALIGNED (D % 4 == 0): a quad lies inside one row and its global index is a multiple of 4, so it shares one word pair.
+// Otherwise a quad may straddle rows and word pairs: each element is hashed at its own index, the word pair kept while
+// the index's quad does not change.
+template <bool RELU, bool BWD, bool ALIGNED>
+__global__ __launch_bounds__(256) void feature_dropout_rows_kernel(FdropParams p, const int64_t* __restrict__ row_ids) {
+  uint64_t seed = p.seed;
+  if (p.thr != 0u && p.seed_dev != nullptr) seed += *p.seed_dev;
+  const int64_t nquad = (p.total + 3) >> 2;
+  const bool narrow = p.total < ((int64_t)1 << 32);             // block-uniform: a 32-bit division where the index fits
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t e = q << 2;
+    const int64_t row0 = narrow ? (int64_t)((uint32_t)e / (uint32_t)p.D) : e / p.D;
+    const int32_t col0 = (int32_t)(e - row0 * p.D);
+    fdrop_quad<RELU, BWD>(p, e, [&] { return col0; }, [&](float (&o)[4]) {
+      if (ALIGNED) {                                            // D % 4 == 0: total % 4 == 0 too, every quad is full
+        drop4(o, (uint64_t)row_ids[row0] * (uint64_t)p.D + (uint64_t)col0, true, seed, p.thr, p.keep_scale);
+        return;
+      }
+      int64_t row = row0;
+      int32_t col = col0;
+      uint64_t base = (uint64_t)row_ids[row] * (uint64_t)p.D, pair = ~(uint64_t)0;
+      uint32_t w0 = 0u, w1 = 0u;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (e + c < p.total) {
+          const uint64_t g = base + (uint64_t)col;
+          if ((g >> 2) != pair) { pair = g >> 2; drop_words(pair, seed, w0, w1); }
+          const uint32_t w = (g & 2) ? w1 : w0;
+          const uint32_t bits = (g & 1) ? (w >> 16) : (w & 0xFFFFu);
+          o[c] = bits >= p.thr ? o[c] * p.keep_scale : 0.f;
+          if (++col == p.D) {                                   // the next element opens the next row
+            col = 0; ++row;
+            if (c < 3 && e + c + 1 < p.total) base = (uint64_t)row_ids[row] * (uint64_t)p.D;
+          }
+        }
+      }
+    });
+  }
+}
+
+constexpr int FDROP_ROWS_MAX_GRID = 4096;    // blocks of 256 lanes, one quad per lane and trip; the rest is walked by stride
+
+template <bool RELU, bool BWD>
+int launch_fdrop_rows(const FdropParams& p, const int64_t* row_ids, hipStream_t st) {
+  int64_t grid = ((p.total + 3) / 4 + 255) / 256;
+  if (grid > FDROP_ROWS_MAX_GRID) grid = FDROP_ROWS_MAX_GRID;
+  if (grid < 1) grid = 1;
+  if (p.D % 4 == 0)
+    hipLaunchKernelGGL((feature_dropout_rows_kernel<RELU, BWD, true>), dim3((unsigned)grid), dim3(256), 0, st, p, row_ids);
+  else
+    hipLaunchKernelGGL((feature_dropout_rows_kernel<RELU, BWD, false>), dim3((unsigned)grid), dim3(256), 0, st, p, row_ids);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
@@ -291,31 +386,52 @@ extern "C" int bgnn_appnp_propagate_f32(const float* h, int64_t ld_h, const int3
     p.out = out; p.ldo = ld_out;
     return dispatch_step<MODE_ROWS>(true, last_store, p, st);
   }
-  p.hub_threshold = hubs ? hub_threshold : 0;
+  HubTables ht{};
+  if (hubs) ht = HubTables{hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, part};
   for (int32_t k = 0; k < K; ++k) {
     const bool first = k == 0, last = k == K - 1;
-    const int store = last ? last_store : STORE_STATE;
     float* src = (k & 1) ? s0 : s1;          // step k reads what step k-1 wrote: s0 after steps 0, 2, .., s1 after 1, 3, ..
     float* dst = (k & 1) ? s1 : s0;
     if (first) { p.tbl = h; p.ldt = ld_h; } else { p.tbl = src; p.ldt = ldw; }
     p.n_tbl = n_rows;
     if (last) { p.out = out; p.ldo = ld_out; } else { p.out = dst; p.ldo = ldw; }
-    int rc = dispatch_step<MODE_ROWS>(first, store, p, st);
-    if (rc != 0) return rc;
-    if (hubs) {
-      AppnpParams s = p;                     // partial rows of the segments
-      s.rowptr = seg_bounds_opt; s.n_rows = n_seg; s.hub_threshold = 0;
-      s.out = part; s.ldo = ldw;
-      rc = first ? dispatch_lf<MODE_SEGMENT, true, STORE_STATE>(s, st) : dispatch_lf<MODE_SEGMENT, false, STORE_STATE>(s, st);
-      if (rc != 0) return rc;
-      AppnpParams f = p;                     // a hub's partial rows in segment order, then the step's scaling, teleport and store
-      f.tbl = part; f.ldt = ldw; f.n_tbl = n_seg;
-      f.rowptr = hub_seg_ptr_opt; f.col = nullptr; f.n_rows = n_hubs; f.hub_threshold = 0; f.hub_rows = hub_rows_opt;
-      rc = dispatch_step<MODE_FINISH>(first, store, f, st);
-      if (rc != 0) return rc;
-    }
+    if (const int rc = run_step(p, first, last ? last_store : STORE_STATE, ht, st)) return rc;
   }
   return 0;
+}
+
+extern "C" int bgnn_appnp_step_f32(const float* tbl, int64_t ld_tbl, int64_t n_tbl, const float* h, int64_t ld_h,
+                                   const int32_t* rowptr, const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows,
+                                   int32_t D, float alpha, int first, int store,
+                                   int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                                   const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                                   void* ws_opt, size_t ws_bytes, float* out, int64_t ld_out, void* stream) {
+  if (!tbl || !h || !rowptr || !col || !dinv || !out) return BGNN_E_NULL;
+  if (n_rows < 0 || n_tbl < n_rows || D < 1 || D > SLICE) return BGNN_E_SHAPE;
+  if (n_dinv < (first ? n_tbl : n_rows)) return BGNN_E_SHAPE;           // the first step gathers dinv[col] over the whole table
+  if (!(alpha >= 0.f && alpha <= 1.f)) return BGNN_E_SHAPE;
+  if (store != STORE_STATE && store != STORE_OUT && store != STORE_LOGSOFTMAX) return BGNN_E_SHAPE;
+  if (!ld_ok(ld_tbl, D) || !ld_ok(ld_h, D) || !ld_ok(ld_out, D)) return BGNN_E_ALIGN;
+  if (!bgnn_aligned16(tbl) || !bgnn_aligned16(h) || !bgnn_aligned16(out)) return BGNN_E_ALIGN;
+  if (out == tbl || out == h) return BGNN_E_SHAPE;
+  if (n_hubs < 0 || n_seg < 0) return BGNN_E_SHAPE;
+  HubTables ht{};
+  if (n_hubs > 0) {
+    if (hub_threshold < 1 || n_seg < n_hubs) return BGNN_E_SHAPE;
+    if (!hub_rows_opt || !hub_seg_ptr_opt || !seg_bounds_opt || !ws_opt) return BGNN_E_NULL;
+    if (ws_bytes < state_floats(n_seg, D) * sizeof(float) + 16) return BGNN_E_WORKSPACE;
+    float* part = reinterpret_cast<float*>(bgnn_align_up(reinterpret_cast<uintptr_t>(ws_opt), 16));
+    ht = HubTables{hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, part};
+  }
+  if (n_rows == 0) return 0;
+  AppnpParams p{};
+  p.tbl = tbl; p.ldt = ld_tbl; p.n_tbl = n_tbl;
+  p.h = h; p.ldh = ld_h;
+  p.rowptr = rowptr; p.col = col; p.dinv = dinv; p.n_dinv = n_dinv; p.n_rows = n_rows; p.D = D;
+  p.n_out = n_rows;
+  p.alpha = alpha; p.beta = 1.f - alpha;
+  p.out = out; p.ldo = ld_out;
+  return run_step(p, first != 0, store, ht, (hipStream_t)stream);
 }
 
 extern "C" int bgnn_appnp_log_softmax_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows,
@@ -353,4 +469,34 @@ extern "C" int bgnn_feature_dropout_bwd_f32(const float* y_opt, const float* gra
   drop_consts(p_drop, p.thr, p.keep_scale);
   p.seed = seed; p.seed_dev = seed_dev_opt; p.y = grad_x;
   return relu ? launch_fdrop<true, true>(p, (hipStream_t)stream) : launch_fdrop<false, true>(p, (hipStream_t)stream);
+}
+
+extern "C" int bgnn_feature_dropout_rows_f32(const float* x, const float* bias_opt, const int64_t* row_ids, int64_t n_rows, int32_t D,
+                                             int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* y,
+                                             void* stream) {
+  if (const int rc = fdrop_check(x, y, n_rows, D, p_drop)) return rc;
+  if (!row_ids) return BGNN_E_NULL;
+  if (n_rows == 0) return 0;
+  FdropParams p{};
+  p.x = x; p.bias = bias_opt; p.total = n_rows * (int64_t)D; p.D = D;
+  drop_consts(p_drop, p.thr, p.keep_scale);
+  p.seed = seed; p.seed_dev = seed_dev_opt; p.y = y;
+  return relu ? launch_fdrop_rows<true, false>(p, row_ids, (hipStream_t)stream)
+              : launch_fdrop_rows<false, false>(p, row_ids, (hipStream_t)stream);
+}
+
+extern "C" int bgnn_feature_dropout_rows_bwd_f32(const float* y_opt, const float* grad_y, const int64_t* row_ids, int64_t n_rows,
+                                                 int32_t D, int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                                 float* grad_x, void* stream) {
+  if (const int rc = fdrop_check(grad_y, grad_x, n_rows, D, p_drop)) return rc;
+  if (!row_ids) return BGNN_E_NULL;
+  if (relu && !y_opt) return BGNN_E_NULL;
+  if (relu && !bgnn_aligned16(y_opt)) return BGNN_E_ALIGN;
+  if (n_rows == 0) return 0;
+  FdropParams p{};
+  p.x = y_opt; p.gy = grad_y; p.total = n_rows * (int64_t)D; p.D = D;
+  drop_consts(p_drop, p.thr, p.keep_scale);
+  p.seed = seed; p.seed_dev = seed_dev_opt; p.y = grad_x;
+  return relu ? launch_fdrop_rows<true, true>(p, row_ids, (hipStream_t)stream)
+              : launch_fdrop_rows<false, true>(p, row_ids, (hipStream_t)stream);
 }

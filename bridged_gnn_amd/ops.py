@@ -1131,6 +1131,56 @@ def appnp_propagate(h, rowptr, col, dinv, n_rows, D, K, alpha, epilogue=None, hu
     return out
 
 
+APPNP_STORES = {"state": 0, "out": 1, "log_softmax": 2}
+
+
+def appnp_step(tbl, h, rowptr, col, dinv, n_rows, D, alpha, first, store, hubs=None, out=None):
+    """One step of `appnp_propagate`'s recurrence over a RECTANGULAR graph (models/backbones.py:110-128 on a node partition; bgnn.h:
+    bgnn_appnp_step_f32) -> out [n_rows, pad4(D)]: row i = store((1 - alpha) * dinv[i] * sum_t w_t * tbl[col[t]] + alpha * h[i]).
+    tbl [n_tbl >= n_rows, >= pad4(D)]: the owned rows followed by the halo slots -- h's rows with `first` (w_t = dinv[col[t]], dinv
+    float32 [>= n_tbl]), else the scaled state dinv * z_k (w_t = 1, dinv [>= n_rows]); h: the n_rows teleport rows; (rowptr, col): the
+    CSR of the n_rows owned rows, `hubs` its hub tables.  store: "state" (dinv[i] * z, the next step's table rows), "out" (z) or
+    "log_softmax".  K calls on a square graph are `appnp_propagate` bit for bit (the same launches).  No allocation beyond `out` and
+    the hub partial rows, no host synchronisation."""
+    n_rows, D, alpha = int(n_rows), int(D), float(alpha)
+    if store not in APPNP_STORES:
+        raise ValueError(f"store must be 'state', 'out' or 'log_softmax', got {store!r}")
+    if D < 1:
+        raise ValueError("D must be at least 1")
+    _need_rows_f32(tbl, "tbl", D)
+    _need_rows_f32(h, "h", D)
+    n_tbl = int(tbl.shape[0])
+    if h.shape[0] != n_rows:
+        raise ValueError(f"h must have n_rows = {n_rows} rows, got {h.shape[0]}")
+    if n_tbl < n_rows:
+        raise ValueError(f"tbl must have at least n_rows = {n_rows} rows (the owned rows, then the halo slots), got {n_tbl}")
+    if dinv.dtype != torch.float32 or dinv.dim() != 1 or dinv.shape[0] < (n_tbl if first else n_rows):
+        raise ValueError("dinv must be float32 [>= rows of tbl] on the first step, [>= n_rows] otherwise")
+    if rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.shape[0] < n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
+        raise ValueError("rowptr must be int32 [n_rows + 1] and col int32 [E]")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must lie in [0, 1]")
+    if out is None:
+        out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=h.device)
+    else:
+        _need_rows_f32(out, "out", D)
+        if out.shape[0] != n_rows:
+            raise ValueError(f"out must have n_rows = {n_rows} rows")
+    if hubs is None:
+        hub_args, ws = (0, None, 0, None, None, 0), None
+    else:
+        thr, rows, seg_ptr, bounds = hubs
+        n_seg = int(bounds.shape[0]) // 2
+        hub_args = (int(thr), L.ptr(rows), int(rows.shape[0]), L.ptr(seg_ptr), L.ptr(bounds), n_seg)
+        ws = torch.empty(n_seg * pad4(D) * 4 + 16, dtype=torch.uint8, device=h.device)
+    rc = L.lib().bgnn_appnp_step_f32(
+        L.ptr_rows(tbl), tbl.stride(0), n_tbl, L.ptr_rows(h), h.stride(0), L.ptr(rowptr), L.ptr(col), L.ptr(dinv), int(dinv.shape[0]),
+        n_rows, D, alpha, 1 if first else 0, APPNP_STORES[store], *hub_args, L.ptr(ws), ws.numel() if ws is not None else 0,
+        L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_appnp_step_f32")
+    return out
+
+
 def appnp_log_softmax_bwd(y, grad_y, D, out=None):
     """g = grad_y - exp(y) * rowsum(grad_y) over D <= 128 columns (bgnn.h: bgnn_appnp_log_softmax_bwd_f32): the gradient at z_K of
     `appnp_propagate(..., epilogue="log_softmax")` from its output y -> g [rows, pad4(D)], pad columns 0; `appnp_propagate` over
@@ -1158,11 +1208,18 @@ def _fdrop_check(t, what, shape=None):
         raise ValueError(f"{what} must be contiguous and 16-byte aligned")
 
 
-def feature_dropout(x, p, seed, seed_dev=None, bias=None, relu=False, out=None):
+def _fdrop_row_ids(row_ids, N):
+    if row_ids.dtype != torch.int64 or row_ids.dim() != 1 or row_ids.shape[0] != N or not row_ids.is_contiguous():
+        raise ValueError(f"row_ids must be a contiguous int64 [{N}]")
+    L._check_device(row_ids)
+
+
+def feature_dropout(x, p, seed, seed_dev=None, bias=None, relu=False, out=None, row_ids=None):
     """y = drop(act(x + bias)) over a contiguous [N, D] activation of any width (models/backbones.py:110-128: APPNP_Net's
     F.dropout(x) and F.dropout(F.relu(lin1(x))); bgnn.h: bgnn_feature_dropout_f32).  act = ReLU when `relu`; bias float32 [D] or
     None; element row * D + column is kept by the (seed + seed_dev, element index) hash of `bn_relu_dropout` and scaled by
-    1 / (1 - p).  0 <= p < 1; `out` may be x."""
+    1 / (1 - p).  0 <= p < 1; `out` may be x.  row_ids: int64 [N], the GLOBAL row of every row (a rank's rows of a partition): the
+    element index is then row_ids[r] * D + column, the masks of the whole-graph call (bgnn_feature_dropout_rows_f32); None = row r."""
     _fdrop_check(x, "x")
     if not 0.0 <= float(p) < 1.0:
         raise ValueError("p must lie in [0, 1)")
@@ -1175,16 +1232,22 @@ def feature_dropout(x, p, seed, seed_dev=None, bias=None, relu=False, out=None):
         out = torch.empty_like(x)
     else:
         _fdrop_check(out, "out", x.shape)
+    if row_ids is not None:
+        _fdrop_row_ids(row_ids, N)
+        rc = L.lib().bgnn_feature_dropout_rows_f32(L.ptr(x), L.ptr(bias), L.ptr(row_ids), N, D, 1 if relu else 0, float(p),
+                                                   *_seed_args(seed, seed_dev), L.ptr(out), L.stream())
+        L.check(rc, "bgnn_feature_dropout_rows_f32")
+        return out
     rc = L.lib().bgnn_feature_dropout_f32(L.ptr(x), L.ptr(bias), N, D, 1 if relu else 0, float(p), *_seed_args(seed, seed_dev),
                                           L.ptr(out), L.stream())
     L.check(rc, "bgnn_feature_dropout_f32")
     return out
 
 
-def feature_dropout_bwd(grad_y, p, seed, seed_dev=None, y=None, relu=False, out=None):
+def feature_dropout_bwd(grad_y, p, seed, seed_dev=None, y=None, relu=False, out=None, row_ids=None):
     """Backward of `feature_dropout(x, p, seed, seed_dev, bias, relu)` -> grad_x = grad_y * keep / (1 - p) * [act'] (the bias
     gradient is its column sums).  With `relu` the mask and the ReLU state are read off the forward's output `y` (y > 0 <=> kept
-    and positive); without it the mask is redrawn from the seed and `y` is not needed."""
+    and positive); without it the mask is redrawn from the seed and `y` is not needed.  row_ids: as in the forward."""
     _fdrop_check(grad_y, "grad_y")
     if not 0.0 <= float(p) < 1.0:
         raise ValueError("p must lie in [0, 1)")
@@ -1197,6 +1260,12 @@ def feature_dropout_bwd(grad_y, p, seed, seed_dev=None, y=None, relu=False, out=
         out = torch.empty_like(grad_y)
     else:
         _fdrop_check(out, "out", grad_y.shape)
+    if row_ids is not None:
+        _fdrop_row_ids(row_ids, N)
+        rc = L.lib().bgnn_feature_dropout_rows_bwd_f32(L.ptr(y) if relu else None, L.ptr(grad_y), L.ptr(row_ids), N, D,
+                                                       1 if relu else 0, float(p), *_seed_args(seed, seed_dev), L.ptr(out), L.stream())
+        L.check(rc, "bgnn_feature_dropout_rows_bwd_f32")
+        return out
     rc = L.lib().bgnn_feature_dropout_bwd_f32(L.ptr(y) if relu else None, L.ptr(grad_y), N, D, 1 if relu else 0, float(p),
                                               *_seed_args(seed, seed_dev), L.ptr(out), L.stream())
     L.check(rc, "bgnn_feature_dropout_bwd_f32")

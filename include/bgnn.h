@@ -47,7 +47,8 @@ extern "C" {
  * 116 is NOT call-compatible with 115: bgnn_sage_mean_aggregate_f32, bgnn_gcn_aggregate_f32, bgnn_gat_aggregate_f32,
  * bgnn_gat_aggregate_bwd_f32, bgnn_gatv2_aggregate_f32 and bgnn_gatv2_aggregate_bwd_f32 take the ids (and n_src) for every caller;
  * the _rows_ entries are gone.  The APPNP baseline's bgnn_appnp_propagate_f32 with its workspace size, bgnn_appnp_log_softmax_bwd_f32 and
- * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 were added after 116 as purely additive symbols. */
+ * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 were added after 116 as purely additive symbols, and so were the
+ * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -589,6 +590,34 @@ int bgnn_feature_dropout_f32(const float* x, const float* bias_opt, int64_t n_ro
                              uint64_t seed, const uint64_t* seed_dev_opt, float* y, void* stream);
 int bgnn_feature_dropout_bwd_f32(const float* y_opt, const float* grad_y, int64_t n_rows, int32_t D, int relu, float p_drop,
                                  uint64_t seed, const uint64_t* seed_dev_opt, float* grad_x, void* stream);
+/* One step of the APPNP propagation over a RECTANGULAR graph (APPNP_Net, models/backbones.py:110-128, on a destination-node
+ * partition: the caller exchanges halo rows between steps, which the K-step entry cannot do):
+ *     out[i] = store((1 - alpha) * dinv[i] * sum_{t in row i} w_t * tbl[col[t]] + alpha * h[i]),   i < n_rows,
+ * rowptr [n_rows+1] and h / out with n_rows rows (a rank's owned rows), tbl with n_tbl >= n_rows rows (the owned rows, then the
+ * halo slots); ids >= n_tbl are never dereferenced.  first != 0: tbl holds h's rows and w_t = dinv[col[t]] (dinv [n_dinv >=
+ * n_tbl]); first == 0: tbl holds the scaled state s_k = dinv * z_k and w_t = 1 (dinv [n_dinv >= n_rows]).  store: 0 the next
+ * scaled state dinv[i] * z, 1 the value z itself, 2 its row log_softmax; pad columns are written as 0.  It is the launch
+ * sequence bgnn_appnp_propagate_f32 runs per step (one launch, three with hub tables: the same argument group, over the n_rows
+ * owned rows), through the same code, so K calls on a square graph give that entry's bits.  1 <= D <= 128, 0 <= alpha <= 1,
+ * leading dimensions % 4 == 0 and >= pad4(D), tbl / h / out 16-B aligned, out distinct from tbl and h.
+ * ws: n_seg * pad4(D) * 4 + 16 bytes for the hub partial rows, provided by the caller (may be NULL when n_hubs == 0).  Nothing
+ * is allocated and the host never waits. */
+int bgnn_appnp_step_f32(const float* tbl, int64_t ld_tbl, int64_t n_tbl, const float* h, int64_t ld_h, const int32_t* rowptr,
+                        const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t D, float alpha, int first,
+                        int store, int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                        const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                        void* ws_opt, size_t ws_bytes, float* out, int64_t ld_out, void* stream);
+/* Feature dropout of APPNP_Net (models/backbones.py:110-128) on a rank's rows of a partitioned activation: the passes of
+ * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 with row_ids (int64 [n_rows], the GLOBAL row of every local row):
+ * element (r, c) draws the bits the plain pass draws for flat element row_ids[r] * D + c (word pair e >> 2, 16-bit slot e & 3),
+ * so every rank drops what the whole-graph call drops in its rows; identity ids give the plain pass bit for bit.  Bias, ReLU,
+ * the (seed, seed_dev) pair and the backward's mask off y > 0 as there.  The grid is capped at 4096 blocks of 256 lanes (one
+ * quad of four consecutive local elements per lane and trip), the rest is walked by stride. */
+int bgnn_feature_dropout_rows_f32(const float* x, const float* bias_opt, const int64_t* row_ids, int64_t n_rows, int32_t D,
+                                  int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* y, void* stream);
+int bgnn_feature_dropout_rows_bwd_f32(const float* y_opt, const float* grad_y, const int64_t* row_ids, int64_t n_rows, int32_t D,
+                                      int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* grad_x,
+                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
