@@ -24,6 +24,9 @@ def __getattr__(name):
     if name in ("APPNP", "APPNP_Net"):                 # the APPNP baseline's, likewise
         from . import appnp
         return getattr(appnp, name)
+    if name in ("GCN2", "GCN2Conv", "train_gcn2_noDTC"):   # the GCNII baseline's, likewise
+        from . import gcn2
+        return getattr(gcn2, name)
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)

@@ -1131,6 +1131,96 @@ def appnp_propagate(h, rowptr, col, dinv, n_rows, D, K, alpha, epilogue=None, hu
     return out
 
 
+GCN2_MAX_WIDTH = 128
+
+
+def gcn2_supported(H):
+    """the hidden widths `gcn2_conv` / `gcn2_conv_bwd` take (any H of the range, a multiple of 4 or not)"""
+    return 1 <= int(H) <= GCN2_MAX_WIDTH
+
+
+def _gcn2_need_m(M, H):
+    L._check_device(M)
+    if M.dtype != torch.float32 or tuple(M.shape) != (pad4(H), pad4(H)) or not M.is_contiguous():
+        raise ValueError(f"M must be a contiguous float32 [pad4(H), pad4(H)] = [{pad4(H)}, {pad4(H)}] (zero padding)")
+
+
+def gcn2_conv(x, x0, M, rowptr, col, dinv, n_rows, H, alpha, p_drop=0.0, seed=0, seed_dev=None, hubs=None, m_out=None, out=None):
+    """One GCNII layer with its ReLU and dropout (models/backbones.py:163-197: GCN2Conv(H, alpha, theta, layer) + relu + the next
+    F.dropout; bgnn.h: bgnn_gcn2_conv_f32) -> out [n_rows, pad4(H)] (use out[:, :H]):
+    m_i = (1 - alpha) * dinv[i] * sum_{t in row i} dinv[col[t]] * x[col[t]] + alpha * x0[i],  out_i = drop(relu(m_i @ M)),
+    M = (1 - beta) * I + beta * weight1 as float32 [pad4(H), pad4(H)] with zero padding (applied untransposed), over the CSR of
+    `gcn_aggregate` (`GcnGraph`: csr.rowptr, col, dinv, hubs).  x / x0 / out / m_out: 2-D row-strided views with unit column
+    stride, n_rows rows (x may be a view of a wider table); 1 <= H <= 128, 0 <= alpha <= 1.  Dropout at p_drop keeps element
+    i * H + column by the (seed + seed_dev, element index) hash of `gcn_aggregate`; p_drop = 0 draws no mask.
+    m_out: None (evaluation: the mix never leaves the chip) or a [n_rows, >= pad4(H)] buffer that receives m (training: the
+    backward's operand); out has the same bits either way.  hubs: as in `gcn_aggregate`.  No atomics, no host synchronisation."""
+    n_rows, H, alpha = int(n_rows), int(H), float(alpha)
+    if not gcn2_supported(H):
+        raise ValueError(f"gcn2_conv takes 1 <= H <= {GCN2_MAX_WIDTH}, got {H}")
+    _need_rows_f32(x, "x", H)
+    _need_rows_f32(x0, "x0", H)
+    _gcn2_need_m(M, H)
+    if x.shape[0] != n_rows or x0.shape[0] != n_rows:
+        raise ValueError(f"x and x0 must have n_rows = {n_rows} rows (the graph is square)")
+    if dinv.dtype != torch.float32 or dinv.dim() != 1 or dinv.shape[0] < n_rows:
+        raise ValueError("dinv must be float32 [>= n_rows]")
+    if rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.shape[0] < n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
+        raise ValueError("rowptr must be int32 [n_rows + 1] and col int32 [E]")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must lie in [0, 1]")
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError("p_drop must lie in [0, 1)")
+    if out is None:
+        out = torch.empty(n_rows, pad4(H), dtype=torch.float32, device=x.device)
+    else:
+        _need_rows_f32(out, "out", H)
+    if m_out is not None:
+        _need_rows_f32(m_out, "m_out", H)
+    if out.shape[0] != n_rows or (m_out is not None and m_out.shape[0] != n_rows):
+        raise ValueError(f"out and m_out must have n_rows = {n_rows} rows")
+    lib = L.lib()
+    if hubs is None:
+        hub_args, ws = (0, None, 0, None, None, 0, None, 0), None
+    else:
+        thr, rows, seg_ptr, bounds = hubs
+        n_seg = int(bounds.shape[0]) // 2
+        ws = torch.empty(max(int(lib.bgnn_gcn2_conv_workspace_bytes(n_seg, H)), 16), dtype=torch.uint8, device=x.device)
+        hub_args = (int(thr), L.ptr(rows), int(rows.shape[0]), L.ptr(seg_ptr), L.ptr(bounds), n_seg, L.ptr(ws), ws.numel())
+    rc = lib.bgnn_gcn2_conv_f32(
+        L.ptr_rows(x), x.stride(0), L.ptr_rows(x0), x0.stride(0), L.ptr(M), L.ptr(rowptr), L.ptr(col), L.ptr(dinv),
+        int(dinv.shape[0]), n_rows, H, alpha, float(p_drop), *_seed_args(seed, seed_dev), *hub_args, L.ptr_rows(m_out),
+        m_out.stride(0) if m_out is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gcn2_conv_f32")
+    return out
+
+
+def gcn2_conv_bwd(y, grad_y, M, H, alpha, p_drop):
+    """Dense half of `gcn2_conv`'s backward (models/backbones.py:163-197; bgnn.h: bgnn_gcn2_conv_bwd_f32) -> (gz, t, gx0), each
+    [rows, pad4(H)] with zero pad columns: gz = grad_y * [y > 0] / (1 - p_drop) (y: the forward's output; y > 0 <=> kept and
+    positive, no mask is redrawn), gm = gz @ M^T, t = (1 - alpha) * gm, gx0 = alpha * gm.  The caller finishes with
+    grad_weight1 = beta * m^T gz (`gram`) and grad_x = `gcn_aggregate(t, t_rowptr, t_dst, dinv, ..., hubs=t_hubs)`."""
+    H, alpha = int(H), float(alpha)
+    if not gcn2_supported(H):
+        raise ValueError(f"gcn2_conv_bwd takes 1 <= H <= {GCN2_MAX_WIDTH}, got {H}")
+    _need_rows_f32(y, "y", H)
+    _need_rows_f32(grad_y, "grad_y", H)
+    _gcn2_need_m(M, H)
+    if grad_y.shape[0] != y.shape[0]:
+        raise ValueError("y and grad_y must have the same number of rows")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must lie in [0, 1]")
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError("p_drop must lie in [0, 1)")
+    N = int(y.shape[0])
+    gz, t, gx0 = (torch.empty(N, pad4(H), dtype=torch.float32, device=y.device) for _ in range(3))
+    rc = L.lib().bgnn_gcn2_conv_bwd_f32(L.ptr_rows(y), y.stride(0), L.ptr_rows(grad_y), grad_y.stride(0), L.ptr(M), N, H, alpha,
+                                        float(p_drop), L.ptr_rows(gz), gz.stride(0), L.ptr_rows(t), t.stride(0), L.ptr_rows(gx0),
+                                        gx0.stride(0), L.stream())
+    L.check(rc, "bgnn_gcn2_conv_bwd_f32")
+    return gz, t, gx0
+
+
 APPNP_STORES = {"state": 0, "out": 1, "log_softmax": 2}
 
 

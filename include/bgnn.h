@@ -48,7 +48,8 @@ extern "C" {
  * bgnn_gat_aggregate_bwd_f32, bgnn_gatv2_aggregate_f32 and bgnn_gatv2_aggregate_bwd_f32 take the ids (and n_src) for every caller;
  * the _rows_ entries are gone.  The APPNP baseline's bgnn_appnp_propagate_f32 with its workspace size, bgnn_appnp_log_softmax_bwd_f32 and
  * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 were added after 116 as purely additive symbols, and so were the
- * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32. */
+ * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32, and the GCNII
+ * baseline's bgnn_gcn2_conv_f32 with its workspace size and bgnn_gcn2_conv_bwd_f32. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -618,6 +619,46 @@ int bgnn_feature_dropout_rows_f32(const float* x, const float* bias_opt, const i
 int bgnn_feature_dropout_rows_bwd_f32(const float* y_opt, const float* grad_y, const int64_t* row_ids, int64_t n_rows, int32_t D,
                                       int relu, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* grad_x,
                                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GCNII conv (the GCN2 baseline, models/backbones.py:163-197: PyG GCN2Conv(H, alpha, theta, layer, shared_weights=True,
+ * normalize=False) over the cached gcn_norm adjacency, followed by F.relu and the next F.dropout of GCN2.forward), one pass:
+ *     m_i = (1 - alpha) * dinv[i] * sum_{t in row i} dinv[col[t]] * x[col[t]] + alpha * x0[i]
+ *     y_i = drop(relu(m_i @ M)),       M = (1 - beta) * I + beta * weight1,  beta = log(theta / layer + 1)
+ * over the CSR of bgnn_gcn_aggregate_f32 (exactly one self loop per row, dinv[i] = 1/sqrt(deg_i)).  The graph is square: rowptr
+ * [n_rows+1], every id in col < n_rows, x / x0 / out (and m_out) have n_rows rows, dinv [n_dinv >= n_rows].  M: the caller forms
+ * it once per layer call, [pad4(H), pad4(H)] row-major with zero padding, applied untransposed; rows and columns from H on are
+ * not read into the product.  1 <= H <= 128 (else BGNN_E_SHAPE), any H in that range; 0 <= alpha <= 1 (alpha == 1: y does
+ * not depend on the graph); 0 <= p_drop < 1: element i * H + column is kept by the shared (seed + *seed_dev_opt, element) hash
+ * exactly as bgnn_gcn_aggregate_f32's epilogue 1 keeps it, p_drop == 0 draws no mask.  Leading dimensions in floats, % 4 == 0
+ * and >= pad4(H) (x may be a view of a wider table), bases 16-B aligned, out and m_out distinct from x and from each other; pad
+ * columns of out and m_out are written as 0.
+ * m_out_opt: NULL (evaluation) and the mix is never written to memory; else [n_rows, ldm] and m is written exactly once (the
+ * backward's operand of grad_weight1).  y has the same bits either way.
+ * The product runs inside the tile on the f32-input MFMA (an exact fp32 fmaf chain over k = 0 .. pad4(H)-1); M sits in LDS once
+ * per persistent block.
+ * Hub rows: the argument group and the scheme of bgnn_gcn_aggregate_f32 -- with tables the row launch skips them, a segment
+ * launch writes partial rows to the workspace, a finish launch adds a hub's partial rows in segment order and runs the same
+ * mix, product and epilogue on the finished row: a hub's bits do not depend on which block took which segment.  Without tables
+ * (n_hubs == 0) the row launch walks every row whole.  No float atomics.
+ * ws: bgnn_gcn2_conv_workspace_bytes(n_seg, H) bytes (may be NULL when n_hubs == 0).  Nothing is allocated, the host never waits.
+ *
+ * bgnn_gcn2_conv_bwd_f32 (models/backbones.py:163-197, the dense half of the same layer's backward), one streaming pass:
+ *     gz = grad_y * [y > 0] * keep_scale     (y > 0 <=> kept and positive: the rule of bgnn_gcn_aggregate_bwd_f32; no mask is redrawn)
+ *     gm = gz @ M^T,    t = (1 - alpha) * gm,    gx0 = alpha * gm
+ * y: the forward's output; gz, t, gx0: [n_rows, ld], pad columns written as 0, pairwise distinct (gz may be grad_y).  The caller
+ * finishes with entries that exist: grad_weight1 = beta * m^T gz (bgnn_gram_f32) and grad_x = the walk of bgnn_gcn_aggregate_f32
+ * over the by-source view applied to t (the operator is symmetric in its dinv products). */
+size_t bgnn_gcn2_conv_workspace_bytes(int64_t n_seg, int32_t H);
+int bgnn_gcn2_conv_f32(const float* x, int64_t ldx, const float* x0, int64_t ldx0, const float* M, const int32_t* rowptr,
+                       const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t H, float alpha,
+                       float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                       int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                       const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                       void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo, void* stream);
+int bgnn_gcn2_conv_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, const float* M, int64_t n_rows,
+                           int32_t H, float alpha, float p_drop, float* gz, int64_t ldgz, float* t, int64_t ldt,
+                           float* gx0, int64_t ldgx0, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
