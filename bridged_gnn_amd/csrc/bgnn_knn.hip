@@ -1040,7 +1040,15 @@ struct Geom { int cap, kp, tpi; };                  // shortlist geometry by k; 
 static Geom geom_fast(int k) { return k <= 20 ? Geom{62, 48, 2} : Geom{128, 112, 1}; }     // 62: leaves LDS for 2 x 64-row stages
 static Geom geom_precise(int k) { return k <= 20 ? Geom{64, 56, 1} : Geom{128, 120, 1}; }   // wide windows: only rows the fast pass could not prove come here
 static Geom geom_mlp(int k) { return k <= 24 ? Geom{64, 40, 1} : Geom{128, 112, 1}; }
-static int max_kp(int k) { return geom_fast(k).kp; }
+// product set of the fast pass: BGNN_KNN_FAST_PRODUCTS = 1 (default), 2 or 3, read once per process; anything else is 1
+static int fast_products() {
+  static const int v = [] { const char* s = getenv("BGNN_KNN_FAST_PRODUCTS"); const int n = s ? atoi(s) : 1; return n >= 1 && n <= 3 ? n : 1; }();
+  return v;
+}
+// the geometry of the instantiation pass1_dk dispatches for a product set: the host's plan (candidates per staged unit),
+// the shortlist stride and the workspace must all be this one's, also where three products run as the FAST pass
+static Geom geom_pass1(int nprod, int k) { return nprod == 3 ? geom_precise(k) : geom_fast(k); }
+static int max_kp(int k) { return geom_pass1(fast_products(), k).kp; }
 
 struct Pass1Plan { int64_t nblocks, tpb; int nslots; };
 static Pass1Plan plan_pass1(int64_t Nq, int64_t Nc, int64_t resident_blocks, int qpb, int ct) {
@@ -1141,9 +1149,10 @@ static int pass1_dk(int nprod, int k, const P1Params& p, const Pass1Plan* plan, 
     if (qpb_out) { *qpb_out = pass1_waves<DK, NP, CAPV, TPI>() * QPW; return 0; }                      \
     return launch_pass1<DK, NP, CAPV, KPV, TPI>(p, plan, st);                                          \
   } while (0)
-  if (nprod == 3) { if (geom_precise(k).cap == 64) BGNN_P1(3, 64, 56, 1); else BGNN_P1(3, 128, 120, 1); }
-  if (nprod == 2) { if (geom_fast(k).cap == 62) BGNN_P1(2, 62, 48, 2); else BGNN_P1(2, 128, 112, 1); }
-  if (geom_fast(k).cap == 62) BGNN_P1(1, 62, 48, 2); else BGNN_P1(1, 128, 112, 1);
+  const bool narrow = geom_pass1(nprod, k).cap < 128;        // the template arguments below restate geom_pass1's two rows
+  if (nprod == 3) { if (narrow) BGNN_P1(3, 64, 56, 1); else BGNN_P1(3, 128, 120, 1); }
+  if (nprod == 2) { if (narrow) BGNN_P1(2, 62, 48, 2); else BGNN_P1(2, 128, 112, 1); }
+  if (narrow) BGNN_P1(1, 62, 48, 2); else BGNN_P1(1, 128, 112, 1);
 #undef BGNN_P1
 }
 static int pass1_any(int d, int nprod, int k, const P1Params& p, const Pass1Plan* plan, int* qpb_out, hipStream_t st) {
@@ -1219,7 +1228,7 @@ extern "C" int bgnn_cosine_topk_f32(const float* qn_query, const float* qn_cand,
   BGNN_LAUNCH_CHECK();
   hipLaunchKernelGGL(split_rows_kernel, dim3(split_grid(Nq)), dim3(256), 0, st, qn_query, Nq, d, w.qh, w.qm, w.mx + 2);
   BGNN_LAUNCH_CHECK();
-  static const int fast_nprod = [] { const char* s = getenv("BGNN_KNN_FAST_PRODUCTS"); const int v = s ? atoi(s) : 1; return v >= 1 && v <= 3 ? v : 1; }();
+  const int fast_nprod = fast_products();
   const EpsSrc eps{w.mx, d};
   CosineCanon canon{qn_query, qn_cand, d};
   int rc;
@@ -1230,11 +1239,12 @@ extern "C" int bgnn_cosine_topk_f32(const float* qn_query, const float* qn_cand,
   // pass over the first ~1/16 of the candidates pays that price once, and the MAIN pass over the rest starts every
   // segment from the head's per-query threshold (a valid lower bound of the final one) instead of from -inf.
   {
-    const int kp = geom_fast(k).kp;
+    const Geom gf = geom_pass1(fast_nprod, k);
+    const int kp = gf.kp;
     int qpb = 0;
     P1Params p{w.qh, w.qm, w.ch, w.cm, Nq, Nc, nullptr, nullptr, 0, 0, w.sl_score, w.sl_idx, w.sl_tau, eps, k, 0, 0, nullptr, 0, 0};
     pass1_any(d, fast_nprod, k, p, nullptr, &qpb, st);
-    const int ct = MT * geom_fast(k).tpi;                                       // candidates per staged unit
+    const int ct = MT * gf.tpi;                                                 // candidates per staged unit
     const int64_t ntiles = (Nc + ct - 1) / ct;
     const int64_t head_tiles = ntiles >= 128 ? (ntiles + 15) / 16 : 0;          // small problems: one pass
     const int64_t NcA = head_tiles * ct, NcB = Nc - NcA;

@@ -805,7 +805,9 @@ int bgnn_gatv2_aggregate_bwd_f32(const float* tbl, int64_t ldt, int64_t n_src, c
  * stage and the proof read the same eps_q; terms that cancel to within eps_q send the row to stage (4), never to a wrong index.
  * n_fallback_opt (optional, int32[2] on the device): [0] = rows re-done exhaustively, [1] = rows sent to the precise pass.
  * val_out = sigmoid(score) as fp32 if apply_sigmoid (models.py:129,:953) else the fp32 score.
- * k <= 56.  q* must already be L2-normalised by bgnn_l2_normalize_rows_f32 (cosine).          */
+ * k <= 56.  q* must already be L2-normalised by bgnn_l2_normalize_rows_f32 (cosine).
+ * bgnn_topk_workspace_bytes depends on the process's BGNN_KNN_FAST_PRODUCTS (read once; =3 gives the fast pass the precise
+ * pass's longer shortlists): size the workspace with the figure of the process that makes the call.          */
 int bgnn_l2_normalize_rows_f32(const float* q, int64_t n, int32_t d, float eps, float* out, void* stream);
 size_t bgnn_topk_workspace_bytes(int64_t Nq, int64_t Nc, int32_t k);
 int bgnn_cosine_topk_f32(const float* qn_query, const float* qn_cand, int64_t Nq, int64_t Nc,
