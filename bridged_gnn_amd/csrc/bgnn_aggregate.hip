@@ -15,6 +15,7 @@
 // rows (which share in-neighbours in a bridged / kNN graph) hit the same XCD's L2.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "bgnn_common.h"
 
 namespace {
@@ -1108,6 +1109,241 @@ __global__ __launch_bounds__(256) void agg_heads_lanes_kernel(AggParams p) {
   }
 }
 
+// ---- narrow multi-head walk, the plain launch (mode 0, no hub segments, ldh == ldo == 4) with 32-bit addressing ----------------
+// agg_heads_lanes_kernel's step is two dependent round trips (the ids, then the rows they name), eight exec-masked branches, eight
+// quarter-rate 64-bit multiplies and a compare + select per LeakyReLU element: ~240 instructions of which ~70 are the arithmetic.
+// This variant is to it what agg_wide_fast_kernel is to agg_wide_kernel: the same tables, lane mapping and per-lane arithmetic
+// ORDER (results are bit-identical, tests/test_gpu_heads_fast.py pins that), fetched differently.  What the launch is bound by
+// is neither of the first two items below -- with them alone (VALU instructions 83.9 M -> 60.6 M, waves waiting 49 % -> 26 % of
+// their cycles) the launch took the same 176-178 us on C4 -- but the number of vector memory instructions: the texture addresser
+// is busy 70-76 % of the launch, and the third item is what moves the time (profiles/heads_fast/README.md):
+//  * both tables lie in one window of < 4 GB (heads_fast_plan checks): a neighbour's piece is `lane base + id * 16 * HEADS`, one
+//    v_mad_u32_u24, through ONE buffer descriptor; a dead slot's offset is the window's size, which the descriptor's range check
+//    answers with zeros -- no traffic, no branch;
+//  * the ids of step it + 1 are requested behind the gathers of step it (a slot past the row's end is dead by its position, not
+//    by id -1) and taken behind the arithmetic: one round trip per step.  Gathers and id loads are INLINE ASSEMBLY with explicit
+//    waits: written as C++ loads the compiler sinks the id loads to the loop top (see load_id in agg_wide_fast_kernel), and its
+//    own vmcnt(n) would wait for the ids before the first row is used.  The compiler counts none of them; nothing else is in
+//    flight inside the step loop;
+//  * the eight ids of a row's step come as ONE 16-byte load per lane plus a swap between the two sub-groups, not as four dword
+//    loads per lane (see `walk` below);
+//  * the step loop is WAVE-UNIFORM (one v_cmp + scalar branch per step).  A step past a row's end is dead in all slots: zeros from
+//    the range check, l = -inf, mn == m, sc = 1, weight 0 -- (m, s, acc) pass through unchanged -- and its lanes would idle in
+//    lockstep anyway;
+//  * LeakyReLU is max(z, z * slope) (0 <= slope <= 1, finite z: the same bits); the attention vectors of both domains are read
+//    once per block with the D tests; tile positions advance without a division; no int64_t behind the kernel's first lines.
+typedef float f4v_t __attribute__((ext_vector_type(4)));
+// Waves per SIMD the register allocator aims at, i.e. resident blocks per CU.  5 (88 VGPRs) is the most that does not spill: at 6
+// (80 VGPRs) 28 bytes per lane go to scratch around the step loops and at 7 (72) 68 bytes -- every scratch access is one more
+// request to the unit this launch is bound by: 161.8 / 170.5 / 192.6 us at 5 / 6 / 7 on C4 (profiles/heads_fast/README.md).
+// agg_heads_lanes_kernel runs 6 blocks per CU (75 VGPRs).
+#ifndef BGNN_HEADS_FAST_WAVES
+#define BGNN_HEADS_FAST_WAVES 5
+#endif
+
+template <int HEADS, int EP, int U>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BGNN_HEADS_FAST_WAVES))) void agg_heads_fast_kernel(AggParams p) {
+  static_assert(EP == 2 && U == 4, "two sub-groups of four slots per step: the id exchange below");
+  constexpr int GL = EP * HEADS, GPW = 64 / GL, RPB = 4 * GPW;
+  constexpr uint32_t RS = (uint32_t)HEADS * 16u;     // bytes between consecutive nodes of a table (ldh == 4)
+  constexpr int32_t STEP = EP * U;                   // edges of a row per step
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / GL, lg = lane % GL;
+  const int sub = lg / HEADS, h = lg % HEADS;
+  const bool lane_on = g < GPW;                      // 64 % GL lanes idle
+  const int32_t row0 = (int32_t)p.row_begin, row1 = (int32_t)p.row_end;
+  const int32_t ntiles = (row1 - row0 + RPB - 1) / RPB;
+  const uint64_t tb = (uint64_t)p.tbl_base;
+  const u32x4_t rt = {(uint32_t)tb, (uint32_t)(tb >> 32) & 0xffffu, p.tbl_bytes, 0x00020000u};     // the asm gathers' descriptor
+  const __amdgpu_buffer_rsrc_t rtb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tbl_base), (short)0, (int)p.tbl_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out, (short)0, (int)((uint32_t)row1 * RS), 0x00020000);
+  const uint32_t dead = p.dead_off;
+  const uint32_t cend = (uint32_t)p.rowptr[row1] * 4u;                         // bytes of `col` this launch's rows own
+  const int pidx = (lane_on ? lane + (sub ? -HEADS : HEADS) : lane) * 4;         // ds_bpermute address of the other sub-group's lane of my head
+  const f2 sl = {p.slope, p.slope};
+  // the attention vectors, [domain][head], zero-padded to four columns: read here with the D tests, taken per row from LDS
+  __shared__ float4 a_lds[2][HEADS];
+  if (threadIdx.x < 2 * HEADS) {
+    const float* av = (threadIdx.x < HEADS ? p.a_s2t : p.a_t2s) + (threadIdx.x % HEADS) * p.D;
+    float4 a;
+    a.x = av[0];
+    a.y = p.D > 1 ? av[1] : 0.f;
+    a.z = p.D > 2 ? av[2] : 0.f;
+    a.w = p.D > 3 ? av[3] : 0.f;
+    a_lds[threadIdx.x / HEADS][threadIdx.x % HEADS] = a;
+  }
+  __syncthreads();
+  // bgnn::xcd_pos_range / xcd_tile_of in 32-bit integers: position j of this XCD's sequence lies in segment sg at offset r
+  const int32_t per = (ntiles + 7) / 8, seg_len = (per + bgnn::XCD_NSEG - 1) / bgnn::XCD_NSEG;
+  const int32_t xcd = blockIdx.x % 8, nslots = ((int32_t)gridDim.x + 7 - xcd) / 8;
+  int32_t sg = 0, r = blockIdx.x / 8;
+  for (;; r += nslots) {
+    while (r >= seg_len) { r -= seg_len; ++sg; }
+    if (sg >= bgnn::XCD_NSEG) break;
+    const int32_t tile = (sg * 8 + xcd) * seg_len + r;
+    if (tile >= ntiles) continue;                    // padding of the last segments
+    const int32_t i = row0 + tile * RPB + wave * GPW + g;
+    const bool rvalid = lane_on && i < row1;
+    const int32_t ic = rvalid ? i : row0;
+    const bool dom_s = p.mask[ic] != 0;
+    const int32_t rp0 = p.rowptr[ic], rp1 = p.rowptr[ic + 1];
+    const int32_t beg = rvalid ? rp0 : 0, end = rvalid ? rp1 : 0;
+    const uint32_t lbase = (dom_s ? p.off_t2s : p.off_s2t) + (uint32_t)h * 16u;        // this lane's head of node 0 of its table
+    const float4 a4 = a_lds[dom_s ? 1 : 0][h];
+    f4v_t hi = __builtin_bit_cast(f4v_t, __builtin_amdgcn_raw_buffer_load_b128(rtb, lbase + __umul24((uint32_t)ic, RS), 0, 0));
+    f2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
+    float m = -INFINITY, s = 0.f;
+    const int32_t niter = (int32_t)((uint32_t)(end - beg + STEP - 1) / (uint32_t)STEP);
+    int32_t rem = end - beg - sub;                   // slot u of the step is alive while rem > u * EP
+    // The ids of a step, E0 + [0, 8) of the row: ONE 16-byte load per lane (sub-group `sub` reads E0 + 4 * sub + [0, 4), the HEADS
+    // lanes of a sub-group the same bytes) instead of four dwords at E0 + sub + 2 * u -- a quarter of the id load instructions,
+    // which are a third of what this launch asks of the texture addresser (profiles/heads_fast/README.md).  The two sub-groups then
+    // swap the halves they need (ds_bpermute: slot u of sub-group `sub` walks edge E0 + sub + 2 * u as in agg_heads_lanes_kernel).
+    // Reading past the row's end is reading the next rows' ids, and the request one step ahead reads at most 8 * (steps + 1) + 8 ids
+    // past a row's first: a wave whose rows lie that close to the end of `col` (bound: the wave's last edge plus all its edges
+    // plus 16 -- the last few waves of a launch) takes the ids as four dwords clamped to the row's last edge instead (SLOW, one
+    // decision per wave and tile, the same loop compiled twice).  Either way the compiler does not count the loads; they are
+    // taken behind an explicit wait.
+    const int32_t bfirst = __builtin_amdgcn_readfirstlane(beg);                // (lane 0's row: valid whenever one of the wave is)
+    const bool slow = __builtin_amdgcn_ballot_w64(rvalid && (uint32_t)(end + (end - bfirst) + 16) * 4u > cend) != 0;
+    const uint32_t elast = (uint32_t)max(end - 1, 0) * 4u;
+    uint32_t off[U] = {dead, dead, dead, dead};
+    const bool any = __builtin_amdgcn_ballot_w64(niter > 0) != 0;      // wave-uniform; (no edge at all: `col` may be empty)
+    auto walk = [&](auto slow_tag) {
+      constexpr bool SLOW = decltype(slow_tag)::value;
+      // byte offset in `col` of the lane's request: its four ids (a lane without a row: the wave's first ones), or slot 0's id
+      uint32_t xoff = SLOW ? (uint32_t)(beg + sub) * 4u : (uint32_t)((rvalid ? beg : bfirst) + 4 * sub) * 4u;
+      auto request = [&](u32x4_t& q) {
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SLOW) {
+          uint32_t eo[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) eo[u] = min(xoff + (uint32_t)(u * EP * 4), elast);
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.x) : "v"(eo[0]), "s"(p.col) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.y) : "v"(eo[1]), "s"(p.col) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.z) : "v"(eo[2]), "s"(p.col) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.w) : "v"(eo[3]), "s"(p.col) : "memory");
+        } else {
+          asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(q) : "v"(xoff), "s"(p.col) : "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      // (the step's state rides through the wait so that all of its arithmetic is in front of it)
+      auto take = [&](u32x4_t& q, uint32_t (&id)[U]) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(q), "+v"(m), "+v"(s), "+v"(acc01), "+v"(acc23) : : "memory");
+        if constexpr (SLOW) {
+          id[0] = q.x; id[1] = q.y; id[2] = q.z; id[3] = q.w;
+        } else {                                       // sub-group 0 holds edges 0..3 and sends 1, 3; sub-group 1 holds 4..7 and sends 4, 6
+          const uint32_t r0 = (uint32_t)__builtin_amdgcn_ds_bpermute(pidx, (int)(sub ? q.x : q.y));
+          const uint32_t r1 = (uint32_t)__builtin_amdgcn_ds_bpermute(pidx, (int)(sub ? q.z : q.w));
+          id[0] = sub ? r0 : q.x; id[1] = sub ? r1 : q.z; id[2] = sub ? q.y : r0; id[3] = sub ? q.w : r1;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto offsets = [&](const uint32_t (&id)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) off[u] = rem > u * EP ? lbase + __umul24(id[u], RS) : dead;
+      };
+      {
+        uint32_t id[U];
+        u32x4_t q;
+        request(q);
+        take(q, id);
+        offsets(id);
+      }
+      // (the row's own piece is taken HERE: inside the loop the compiler's wait for it would wait for the ids in flight as well)
+      asm volatile("" : "+v"(hi) : : "memory");
+      const f2 h01 = {hi.x, hi.y}, h23 = {hi.z, hi.w};
+      for (int32_t it = 0; __builtin_amdgcn_ballot_w64(it < niter) != 0; ++it) {
+        f4v_t v[U];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v[u]) : "v"(off[u]), "s"(rt) : "memory");
+        xoff += (uint32_t)(STEP * 4);
+        u32x4_t nq;
+        request(nq);                                   // behind the gathers
+        // the gathers; the ids stay in flight
+        if constexpr (SLOW) asm volatile("s_waitcnt vmcnt(4)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
+        else asm volatile("s_waitcnt vmcnt(1)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        float l[U], cm = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          f2 z0 = f2{v[u].x, v[u].y} + h01, z1 = f2{v[u].z, v[u].w} + h23;
+          z0 = __builtin_elementwise_max(z0, z0 * sl);
+          z1 = __builtin_elementwise_max(z1, z1 * sl);
+          float t = a4.x * z0.x;
+          t = fmaf(a4.y, z0.y, t);
+          t = fmaf(a4.z, z1.x, t);
+          t = fmaf(a4.w, z1.y, t);
+          l[u] = rem > u * EP ? t : -INFINITY;
+          cm = fmaxf(cm, l[u]);
+        }
+        const float mn = fmaxf(m, cm);
+        const float sc = (m == mn) ? 1.f : __expf(m - mn);
+        const f2 sc2 = {sc, sc};
+        acc01 *= sc2; acc23 *= sc2;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const float pe = (l[u] == -INFINITY) ? 0.f : __expf(l[u] - mn);
+          s = u == 0 ? fmaf(s, sc, pe) : s + pe;       // (s * sc + pe is ONE rounding in agg_heads_lanes_kernel: the compiler contracts it)
+          acc01.x = fmaf(pe, v[u].x, acc01.x); acc01.y = fmaf(pe, v[u].y, acc01.y);
+          acc23.x = fmaf(pe, v[u].z, acc23.x); acc23.y = fmaf(pe, v[u].w, acc23.y);
+        }
+        m = mn;
+        rem -= STEP;
+        uint32_t nid[U];
+        take(nq, nid);
+        offsets(nid);
+      }
+    };
+    if (any) {
+      if (slow) walk(std::true_type{});
+      else walk(std::false_type{});
+    }
+    float4 acc = make_float4(acc01.x, acc01.y, acc23.x, acc23.y);
+    // merge the EP edge slots of a (row, head): agg_heads_lanes_kernel's.  Its `x * c1 + x2 * c2` is compiled to fma(x, c1, x2 * c2);
+    // written that way here this kernel's other surroundings make the compiler pick two products and a sum, so the roundings are
+    // spelled out.
+#pragma unroll
+    for (int o = 1; o < EP; o <<= 1) {
+      const int src = (sub ^ o) * HEADS + h + g * GL;
+      const int from = lane_on ? src : lane;
+      const float m2 = __shfl(m, from), s2 = __shfl(s, from);
+      float4 b;
+      b.x = __shfl(acc.x, from); b.y = __shfl(acc.y, from); b.z = __shfl(acc.z, from); b.w = __shfl(acc.w, from);
+      const float mn = fmaxf(m, m2);
+      const float c1 = (m == mn) ? 1.f : __expf(m - mn), c2 = (m2 == mn) ? 1.f : __expf(m2 - mn);
+      s = fmaf(s, c1, s2 * c2);
+      acc.x = fmaf(acc.x, c1, b.x * c2); acc.y = fmaf(acc.y, c1, b.y * c2);
+      acc.z = fmaf(acc.z, c1, b.z * c2); acc.w = fmaf(acc.w, c1, b.w * c2);
+      m = mn;
+    }
+    if (rvalid && sub == 0) {
+#pragma clang fp contract(off)   // (agg_heads_lanes_kernel's epilogue is compiled without a fused multiply-add of its own: none here either)
+      const float inv = 1.f / (s + 1e-16f);
+      float4 r4 =make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+      if (p.ep_relu == 2) {    // log_softmax over the head's D classes (KTGNN.py:435), row-local
+        float mx = r4.x;
+        if (p.D > 1) mx = fmaxf(mx, r4.y);
+        if (p.D > 2) mx = fmaxf(mx, r4.z);
+        if (p.D > 3) mx = fmaxf(mx, r4.w);
+        float se = expf(r4.x - mx);
+        if (p.D > 1) se += expf(r4.y - mx);
+        if (p.D > 2) se += expf(r4.z - mx);
+        if (p.D > 3) se += expf(r4.w - mx);
+        const float lse = logf(se);
+        r4.x = r4.x - mx - lse;
+        r4.y = p.D > 1 ? r4.y - mx - lse : 0.f;
+        r4.z = p.D > 2 ? r4.z - mx - lse : 0.f;
+        r4.w = p.D > 3 ? r4.w - mx - lse : 0.f;
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, r4), ro, ((uint32_t)i * (uint32_t)HEADS + (uint32_t)h) * 16u, 0, 0);
+    }
+  }
+}
+
 // Tiles per queue claim.  4 amortises the same-address atomic (~90 ns each); measured on a rank's share of C4
 // (tools/rank_of_8_time.py): 1 -> 0.80 ms, 2 -> 0.69, 4 -> 0.67, 8 -> 0.70 per forward, also for the short launches.
 inline int tq_chunk_for(int64_t ntiles, int64_t grid) {
@@ -1215,6 +1451,33 @@ static bool fast_plan(AggParams& p, int64_t table_rows) {
   // lane base < (offset of the upper table) + (row stride); a dead slot's address must stay in [window, 2^32)
   const int64_t lane_max = (span - table_rows * p.ldh * 4) + p.ldh * 4, dead = (((int64_t)1 << 32) - 16) - lane_max;
   p.dead_off = dead >= span ? (uint32_t)dead : 0u;
+  return true;
+}
+
+// Can this launch run agg_heads_fast_kernel?  fast_plan's window and limits at the row stride heads * 16 bytes; row ranges are
+// admitted.  Fills the window fields of `p`; dead_off becomes the window's size (an absolute offset: the first byte the descriptor
+// refuses).  BGNN_HEADS_FAST=0 keeps agg_heads_lanes_kernel (tests compare the two bit for bit).  Like agg_wide_fast_kernel's
+// load_id the kernel addresses `col` by 32-bit byte offsets, i.e. fewer than 2^30 edges, which the host cannot check: the edge
+// count lives in device memory (the int32 CSR itself ends at 2^31 - N edges).
+static bool heads_fast_plan(AggParams& p, int64_t table_rows) {
+  static const bool on = [] { const char* e = getenv("BGNN_HEADS_FAST"); return !(e && atoi(e) == 0); }();
+  if (!on || table_rows <= 0) return false;
+  if ((p.heads != 2 && p.heads != 3) || p.D > 4 || p.ldh != 4 || p.ldo != 4) return false;
+  if (p.mode != 0 || p.n_vrows != 0 || p.hub_threshold != 0 || p.alpha != nullptr) return false;
+  if (!(p.slope >= 0.f && p.slope <= 1.f)) return false;                       // max(z, slope * z) == leaky_relu(z)
+  const int64_t lim24 = (int64_t)1 << 24, lim32 = ((int64_t)1 << 32) - 1;       // v_mul_u32_u24 operands / 32-bit byte offsets
+  const int64_t rs = (int64_t)p.heads * 16;
+  if (table_rows > lim24 || p.row_end > table_rows) return false;
+  const char* a = reinterpret_cast<const char*>(p.h_t2s);
+  const char* b = reinterpret_cast<const char*>(p.h_s2t);
+  const char* lo = a < b ? a : b;
+  const int64_t span = (int64_t)((a < b ? b : a) - lo) + table_rows * rs;
+  if (span > lim32 || p.row_end * rs > lim32) return false;
+  p.tbl_base = lo;
+  p.tbl_bytes = (uint32_t)span;
+  p.off_t2s = (uint32_t)(a - lo);
+  p.off_s2t = (uint32_t)(b - lo);
+  p.dead_off = (uint32_t)span;
   return true;
 }
 
@@ -1413,10 +1676,33 @@ __global__ __launch_bounds__(256) void hub_merge_heads_kernel(HubMergeParams p) 
   *reinterpret_cast<float4*>(p.out + (node * p.heads + h) * p.ldo) = r;
 }
 
+// agg_heads_fast_kernel on launch_heads's grid rule: the resident blocks, at most 8 per CU
+template <int HEADS, int EP, int U>
+int launch_heads_fast(const AggParams& p, hipStream_t st) {
+  constexpr int RPB = 4 * (64 / (EP * HEADS));
+  static const int cap = [] {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, agg_heads_fast_kernel<HEADS, EP, U>, 256, 0) != hipSuccess || per_cu < 1) return 2048;
+    if (per_cu > 8) per_cu = 8;
+    return per_cu * prop.multiProcessorCount / 8 * 8;
+  }();
+  const int64_t ntiles = (p.row_end - p.row_begin + RPB - 1) / RPB;
+  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;
+  if (grid < 8) grid = 8;
+  hipLaunchKernelGGL((agg_heads_fast_kernel<HEADS, EP, U>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
 static int dispatch_aggregate(const AggParams& p, hipStream_t st, int64_t table_rows = 0) {
   const int32_t D = p.D, heads = p.heads;
-  if (heads == 3 && D <= 4 && p.ldh == 4 && p.ldo == 4) return launch_heads<3, 2, 4>(p, st);   // KT-GNN's classifier stage
-  if (heads == 2 && D <= 4 && p.ldh == 4 && p.ldo == 4) return launch_heads<2, 2, 4>(p, st);
+  if ((heads == 3 || heads == 2) && D <= 4 && p.ldh == 4 && p.ldo == 4) {                     // KT-GNN's classifier stage
+    AggParams q = p;
+    if (heads_fast_plan(q, table_rows)) return heads == 3 ? launch_heads_fast<3, 2, 4>(q, st) : launch_heads_fast<2, 2, 4>(q, st);
+    return heads == 3 ? launch_heads<3, 2, 4>(p, st) : launch_heads<2, 2, 4>(p, st);
+  }
   const int nv = (D + 3) / 4;   // float4 slots per row
   // (LF, EP, U) picked from the tools/tune_agg.py sweep on MI355X (profiles/r01/tune_agg_v2.json):
   // one sub-group per row with deep unrolling beats edge-parallel sub-groups except for the narrowest rows.
