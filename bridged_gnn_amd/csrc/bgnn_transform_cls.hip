@@ -9,8 +9,8 @@
 // holds the tile's fragments in registers (the MFMA B operand, 64 VGPRs) and runs them against FIVE stationary 32-column operands
 // that live in LDS for the whole kernel (the four column tiles of W1' and the skinny tile: 28 rows of narrow weights and gate
 // vectors; 80 KB as fp16 hi / lo pieces, XOR-swizzled like the tiles) -- so the 128 activation columns of a row meet in one wave
-// and the second stage needs no reduction across waves.  One 4-wave block per CU (one wave per SIMD with the whole 512-register budget; 8 waves under 256 registers spilled 205); the next
-// tile's 16 KB of loads are in flight in registers while the current one is worked on.  144 MFMAs per tile and wave
+// and the second stage needs no reduction across waves.  One block per CU, of four waves (one per SIMD with the whole 512-register budget) or eight (two per SIMD under 256 registers each,
+// the default: see the kernel's head).  Four waves: the next tile's 16 KB of loads are in flight in registers while the current one is worked on.  144 MFMAs per tile and wave
 // (5 x 24 + 4 x 6) are the backbone; the vector work of a column tile's tail (activation, column sums, split, second stage) issues
 // in the gaps of the next tile's chain.
 //
@@ -46,9 +46,18 @@ __device__ __forceinline__ void pow2_scales(float mx, float& sc, float& inv) {
   inv = __builtin_bit_cast(float, (E - CLS_TARGET_EXP) << 23);
 }
 
-constexpr int CLS_NW = 4;                                // waves per block (two per SIMD: one converts / waits while the other feeds the matrix pipe)
-
-__global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
+// NW waves per block, one block per CU.  NW = 4: one wave per SIMD with the whole 512-register budget, the schedule described above.
+// NW = 8: two waves per SIMD under 256 registers each (waves w and w + 4 of a block share a SIMD and deal that SIMD's tiles between
+// them), so that one wave's waits and vector work are covered by the other's MFMAs instead of by look-ahead inside the wave: the W
+// fragments are fetched at their own half chain's start, the second stage runs behind its own chain, and the next tile's rows are
+// requested once the last chain has released the fragment registers.  Same operands, same MFMA order per accumulator, same
+// conversions: raw and the skinny tables are bit-identical between the two.
+// DF (NW = 8 only): Din == 128 known at compile time (no zero-fill of the columns past Din, no address selects).  The four-wave
+// kernel keeps its schedule, its run-time flag and a single instantiation: the same trims measured no gain on it.
+template <int NW, bool DF>
+__global__ __launch_bounds__(64 * NW) void cls_stage_kernel(GemmParams p) {
+  constexpr int CLS_NW = NW;
+  constexpr bool PAIR = NW == 8;
   __shared__ __attribute__((aligned(16))) unsigned char wl[(NCT + 1) * 2 * PIECE];      // stationary operands [tile][piece][32][128]
   __shared__ __attribute__((aligned(16))) unsigned char slots[CLS_NW * SLOT];
   __shared__ __attribute__((aligned(16))) h8 w2lds[NCT][2][2][64];     // second-stage operand pieces [column tile][k block][hi, lo][lane]
@@ -60,7 +69,7 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 31, fh = lane >> 5;
   const int NC = p.NC;                        // = 128
-  const bool din_full = p.Din == DK;
+  const bool din_full = PAIR ? DF : p.Din == DK;       // (the four-wave kernel is compiled once and keeps the run-time flag)
 #ifdef CLS_STAMP
   uint32_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t st_last = 0;
@@ -174,6 +183,17 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
   float gcs[4];
 #pragma unroll
   for (int h = 0; h < 4; ++h) gcs[h] = h < 2 * p.sk_heads ? p.sk_gc[h] : 0.f;
+  // per-lane constants of the epilogue, selected once: the gate constant of packed group q, whether the group starts a new
+  // (head, table) and which table it belongs to
+  float gcq[3];
+  bool newq[3], t1q[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    gcq[q] = hsel[q] == 0 ? gcs[0] : hsel[q] == 1 ? gcs[1] : hsel[q] == 2 ? gcs[2] : gcs[3];
+    newq[q] = q == 0 || hsel[q] != hsel[q - 1];
+    t1q[q] = hsel[q] & 1;
+  }
+  const bool relu = p.relu != 0;
 
   // ------------------------------------------------------------------ the wave's tiles
   unsigned char* const sb = slots + wave * SLOT;
@@ -183,7 +203,9 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
   auto roff = [&](int kb) { return roff0 ^ (kb << 5); };
   const int64_t ntiles = (p.N + 31) / 32;
   const int64_t stride = (int64_t)gridDim.x * CLS_NW;
-  int64_t tile = (int64_t)blockIdx.x * CLS_NW + wave;
+  // SIMD s = 4 * block + (wave & 3) takes tiles s, s + S, s + 2S, ... (S = 4 * blocks); its two waves (NW = 8) alternate among them, so
+  // the pair together carries the SIMD's fair share and not two rounded-up shares
+  int64_t tile = (int64_t)blockIdx.x * 4 + (wave & 3) + (int64_t)(wave >> 2) * gridDim.x * 4;
   // The tile is loaded straight in the MFMA operand layout: lane (fr, fh) takes elements 16kb + 8fh .. +7 (kb < 8) of row fr -- 32
   // bytes per k block, the two lane halves of a row together one 64-byte segment, so a row's 128-byte lines are fetched once
   // (the second half hits the L1).  No LDS round trip, no cross-lane reduction beyond one exchange between the two halves.
@@ -241,7 +263,6 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
           xl[kb][4 * c + e] = (_Float16)fmaf(f[e], scx, -(float)h);
         }
       }
-    const float dom = sdom ? 1.f : 0.f;
     if (fh == 0) {
       cfs[fr] = (valid && sdom) ? 1.f : 0.f;
       cfs[32 + fr] = (valid && !sdom) ? 1.f : 0.f;
@@ -249,7 +270,7 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
       cnt_t += (valid && !sdom) ? 1.f : 0.f;
     }
     const int64_t tnext = tile + stride < ntiles ? tile + stride : tile;      // past the end: re-read (never used)
-    gload(tnext);
+    if constexpr (!PAIR) gload(tnext);        // (NW = 8: behind the last chain, when the fragment registers are free)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");           // the wave's own LDS writes before its reads
     // The stationary operand's fragments are requested HALF A CHAIN ahead (two buffers of 4 k blocks = 2 x 32 registers; the
     // sequence of ten half chains per tile is skinny, tile 0 .. tile 3): left to the compiler every k block was read -> wait ->
@@ -268,9 +289,12 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
     // `between(kb)`: vector work dropped behind the three MFMAs of k block kb (the second stage of the PREVIOUS column tile: with one
     // wave per SIMD nothing else fills the chain's issue gaps)
     auto half_chain = [&](int hc, f32x16& acc, auto&& between) {          // prefetches half chain hc + 1, runs half chain hc (buffer hc & 1)
-      if (hc + 1 < 2 * (NCT + 1)) fetch_w(hc + 1, (hc + 1) & 1);
+      if constexpr (PAIR) {                   // NW = 8: its own fragments, one buffer; the partner wave covers the LDS round trip
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_w(hc, 0);
+      } else if (hc + 1 < 2 * (NCT + 1)) fetch_w(hc + 1, (hc + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
-      const int half = hc & 1, buf = hc & 1;
+      const int half = hc & 1, buf = PAIR ? 0 : hc & 1;
 #pragma unroll
       for (int j = 0; j < HK; ++j) {
         const int kb = HK * half + j;
@@ -282,7 +306,7 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
     };
     auto nothing = [](int) {};
     CLS_MARK(1);                              // convert (+ wait for the tile's loads)
-    fetch_w(0, 0);
+    if constexpr (!PAIR) fetch_w(0, 0);
     // ---- (3) the skinny tile (needs only the fragment registers; the slot becomes scratch afterwards): narrow tables of the two convs on h itself (KTGNN.py:277-284 by linearity, see bgnn_transform.hip)
     {                                         // (without a skinny operand its LDS tile is zero and nothing is stored)
       f32x16 acc;
@@ -297,12 +321,10 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           if (optr[q] != nullptr) {
-            if (q == 0 || hsel[q] != hsel[q - 1]) {
-              const bool t1 = hsel[q] & 1;
+            if (newq[q]) {
               const float pre = hsel[q] == 0 ? acc[12] : hsel[q] == 1 ? acc[13] : hsel[q] == 2 ? acc[14] : acc[15];
-              const float gcv = hsel[q] == 0 ? gcs[0] : hsel[q] == 1 ? gcs[1] : hsel[q] == 2 ? gcs[2] : gcs[3];
-              cf = ((dom != 0.f) != t1) ? tanh_fast(fmaf(pre, ss, gcv)) : 0.f;
-              cf = t1 ? cf : -cf;
+              cf = (sdom != t1q[q]) ? tanh_fast(fmaf(pre, ss, gcq[q])) : 0.f;
+              cf = t1q[q] ? cf : -cf;
             }
             const float4 bq = *reinterpret_cast<const float4*>(&skc[0][8 * q + 4 * fh]), wq = *reinterpret_cast<const float4*>(&skc[1][8 * q + 4 * fh]);
             float4 o;
@@ -351,10 +373,14 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
           cs_s[ct] = fmaf(cfs[16 * fh + r], v, cs_s[ct]);  // (weights of the lane's 16 rows: LDS broadcasts, no registers held)
           cs_t[ct] = fmaf(cfs[32 + 16 * fh + r], v, cs_t[ct]);
         }
+        // (the sums are used only behind the tile loop: left alone, the compiler sinks all 128 accumulations of a tile into the
+        // loop's last block and keeps the 64 transposed values and their weights alive until there)
+        if constexpr (PAIR) asm volatile("" : "+v"(cs_s[ct]), "+v"(cs_t[ct]));
       } else {
         const float s2 = q.inv2 * cinv2;
 #pragma unroll
         for (int i = 0; i < 8; ++i) o2[i] = fmaf(q.acc2[i], s2, o2[i]);
+        if constexpr (PAIR) asm volatile("" : "+v"(o2[0]), "+v"(o2[1]), "+v"(o2[2]), "+v"(o2[3]), "+v"(o2[4]), "+v"(o2[5]), "+v"(o2[6]), "+v"(o2[7]));
       }
     };
     Stage2 q2;
@@ -377,7 +403,7 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = fmaf(acc[4 * qq + e], sc1, bb[e]);
-          if (p.relu) v = fmaxf(v, 0.f);
+          if (relu) v = fmaxf(v, 0.f);
           q2.a1[4 * qq + e] = v;
           q2.mx = fmaxf(q2.mx, fabsf(v));
         }
@@ -385,7 +411,21 @@ __global__ __launch_bounds__(64 * CLS_NW) void cls_stage_kernel(GemmParams p) {
             make_float4(q2.a1[4 * qq], q2.a1[4 * qq + 1], q2.a1[4 * qq + 2], q2.a1[4 * qq + 3]);
       }
       CLS_MARK(5);                            // activation + transpose writes
-      if (ct + 1 < NCT) {
+      if constexpr (PAIR) {
+        // NW = 8: the second stage of this tile on its own (the partner wave's chain is what runs beside it), then the next chain;
+        // behind the last chain the fragment registers are free and take the next tile's rows
+        if (ct + 1 == NCT) gload(tnext);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) stage2_step(q2, ct, j);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ct + 1 < NCT) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+          half_chain(2 * (ct + 2), acc, nothing);
+          half_chain(2 * (ct + 2) + 1, acc, nothing);
+        }
+      } else if (ct + 1 < NCT) {
         // the next column tile's chain, the second stage of THIS tile behind its MFMAs
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -453,17 +493,41 @@ bool bgnn_tf_cls_supported(const GemmParams& p) {
   return true;
 }
 
+namespace {
+
+// BGNN_CLS_WAVES=4|8 forces the one-wave or the two-wave-per-SIMD instantiation; anything else leaves the choice to the launcher.
+// Its rule (measured: profiles/cls_waves/README.md): eight waves once every wave of the eight-wave grid has a tile.  Below that the
+// eight-wave grid is n_tiles / 8 blocks, half as many CUs as the four-wave grid of the same call, each with two tiles per SIMD.
+int cls_waves(int64_t n_tiles, int n_cu) {
+  const char* e = getenv("BGNN_CLS_WAVES");
+  if (e != nullptr && (e[0] == '4' || e[0] == '8') && e[1] == '\0') return e[0] - '0';
+  return n_tiles >= (int64_t)8 * n_cu ? 8 : 4;
+}
+
+template <int NW>
+void cls_launch_nw(const GemmParams& p, hipStream_t st, int n_cu) {
+  const int64_t nt = (p.N + 31) / 32, nb = (nt + NW - 1) / NW;
+  const dim3 grid((unsigned)(nb < n_cu ? nb : n_cu)), block(64 * NW);
+  if constexpr (NW == 8) {
+    if (p.Din == DK) { hipLaunchKernelGGL((cls_stage_kernel<NW, true>), grid, block, 0, st, p); return; }
+  }
+  hipLaunchKernelGGL((cls_stage_kernel<NW, false>), grid, block, 0, st, p);
+}
+
+}  // namespace
+
 int bgnn_tf_cls_launch(const GemmParams& p, hipStream_t st, int n_cu) {
   if (!bgnn_tf_cls_supported(p)) return BGNN_E_SHAPE;
-  const int64_t nt = (p.N + 31) / 32, nb = (nt + CLS_NW - 1) / CLS_NW;
 #ifdef CLS_STAMP
+  constexpr int CLS_NW = 4;
+  const int64_t nt = (p.N + 31) / 32, nb = (nt + CLS_NW - 1) / CLS_NW;
   {
     GemmParams q = p;
     static float* dbuf = nullptr;
     if (!dbuf) (void)hipMalloc((void**)&dbuf, sizeof(float) * 256 * 8 * 8);
     q.wd = dbuf;
     const unsigned g = (unsigned)(nb < n_cu ? nb : n_cu);
-    hipLaunchKernelGGL(cls_stage_kernel, dim3(g), dim3(64 * CLS_NW), 0, st, q);
+    hipLaunchKernelGGL((cls_stage_kernel<CLS_NW, false>), dim3(g), dim3(64 * CLS_NW), 0, st, q);
     (void)hipDeviceSynchronize();
     static float host[256 * 8 * 8];
     (void)hipMemcpy(host, dbuf, sizeof(float) * g * CLS_NW * 8, hipMemcpyDeviceToHost);
@@ -475,7 +539,8 @@ int bgnn_tf_cls_launch(const GemmParams& p, hipStream_t st, int n_cu) {
     return 0;
   }
 #endif
-  hipLaunchKernelGGL(cls_stage_kernel, dim3((unsigned)(nb < n_cu ? nb : n_cu)), dim3(64 * CLS_NW), 0, st, p);
+  if (cls_waves((p.N + 31) / 32, n_cu) == 8) cls_launch_nw<8>(p, st, n_cu);
+  else cls_launch_nw<4>(p, st, n_cu);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
