@@ -39,4 +39,7 @@ def __getattr__(name):
     if name in ("PartitionedAPPNP", "AppnpPartition"):     # the APPNP baseline on a node partition (two partitions: A and A^T)
         from . import dist_appnp
         return getattr(dist_appnp, name)
+    if name == "PartitionedGCN2":                      # the GCNII baseline on the GCN partition
+        from . import dist_gcn2
+        return dist_gcn2.PartitionedGCN2
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

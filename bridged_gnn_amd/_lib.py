@@ -118,6 +118,8 @@ SIGNATURES = {
     "bgnn_gcn2_conv_f32": (_INT, [_P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _F32, _F32, C.c_uint64, _P,
                                    _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _I64, _P, _I64, _P]),
     "bgnn_gcn2_conv_bwd_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _I32, _F32, _F32, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "bgnn_gcn2_conv_rows_f32": (_INT, [_P, _I64, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P, _I32, _F32, _F32, C.c_uint64, _P,
+                                        _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _I64, _P, _I64, _P]),
     "bgnn_gat_scores_f32": (_INT, [_P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgnn_gat_aggregate_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
     "bgnn_gat_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,

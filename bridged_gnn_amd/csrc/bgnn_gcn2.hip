@@ -16,6 +16,21 @@
 // Bytes in evaluation at width H: E'(4H + 8) + N(8H + 4) + 4H^2 -- the aggregation's own traffic plus x0 in place of nothing
 // and M once per block from L2; the composition pays the aggregation and four more [N, H] passes.
 //
+// Two entries, one launch sequence (conv_run): bgnn_gcn2_conv_f32 over a square graph, and bgnn_gcn2_conv_rows_f32 over a
+// rectangular one (a rank's owned rows gather from n_tbl >= n_rows table rows) with the GLOBAL id of every output row for the dropout
+// hash -- element row_ids[io] * H + column in place of io * H + column, in the row launch and in a hub's finish launch (io =
+// hub_rows[h]).  The lookup is a TEMPLATE FLAG (IDS), not a pointer test in the one kernel.  With the test, the pointer and its
+// condition stay live across the gather loop and the product: the compiler's resource report gave the LF = 2 and LF = 4 row and
+// finish instantiations (H in 5..16) four SGPRs more (104 / 103 and 102 / 101 where they had 100 / 99 and 98 / 97) and called
+// that 7 waves per SIMD instead of 8, for callers that pass no ids.  (By the 16-register granules in which blocks are admitted
+// both counts allow the same six blocks per CU, so the loss was probably on paper only; it was not measured.)  With the flag
+// there is nothing to weigh: the id-free instantiations are the kernels they were -- same registers, LDS and bits -- the square
+// entry and every p_drop = 0 call run them, and only a rank's training step runs the IDS ones.  Those hold one more 64-bit value
+// per gathered row from the end of the gather
+// to the epilogue (the load is issued before the product, not behind it): 2 SGPRs more each, 4 / 2 VGPRs more at LF = 32, no
+// instantiation in another admission granule than its id-free twin except LF = 8 (96 -> 98 and 95 -> 97 SGPRs), which its 82 / 75
+// VGPRs hold at 5 / 6 waves per SIMD already.
+//
 // LDS per block (floats): M as [4*LF rows][max(16, 4*LF) columns] (64 KB at H in 65..128, 16 KB at 33..64), plus the row tile
 // [TR rows][4*LF + 4] for m and as much again for the product; at H > 64 the product overwrites the m rows instead (one more
 // barrier), which keeps two blocks on a CU.  A wave reads back exactly the rows it wrote, so its next m rows never overwrite
@@ -124,6 +139,7 @@ struct Gcn2Params {
   int32_t H;
   int32_t hub_threshold;                           // ROWS: rows of at least this many edges are left to the hub launches (0: none)
   const int32_t* hub_rows; int64_t n_out;          // FINISH: output row of hub h, rows of out
+  const int64_t* row_ids;                          // NULL, or the global id of every output row: the row of the dropout hash
   float alpha, beta;                               // initial-residual weight and 1 - alpha
   float* m_out; int64_t ldmo;                      // the mix, or NULL
   float* out; int64_t ldo;                         // SEGMENT: the partial rows
@@ -178,7 +194,8 @@ __device__ __forceinline__ float4 gather_row(const Gcn2Params& p, int64_t i, int
   return ep_sum<LF, LF * EP>(acc);
 }
 
-template <int LF, int EP, int U, int MODE>
+// IDS: the dropout hash takes its row from p.row_ids (a rank's rows of a partition); false: the row written, and no id is loaded
+template <int LF, int EP, int U, int MODE, bool IDS>
 __global__ __launch_bounds__(256) void gcn2_conv_kernel(Gcn2Params p) {
   using T = Tile<LF, EP>;
   constexpr int GL = T::GL, GPW = T::GPW, RPB = T::RPB, NB = T::NB, TR = T::TR;
@@ -203,6 +220,7 @@ __global__ __launch_bounds__(256) void gcn2_conv_kernel(Gcn2Params p) {
     const int64_t gt = bgnn::xcd_tile_of(pos, ntiles);
     if (gt < 0) continue;                                       // block-uniform
     int64_t io_b[NB];                                           // per gather pass: the row written and whether it is written
+    [[maybe_unused]] int64_t hr_b[IDS ? NB : 1];
     bool ov_b[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -234,6 +252,7 @@ __global__ __launch_bounds__(256) void gcn2_conv_kernel(Gcn2Params p) {
             *reinterpret_cast<float4*>(p.m_out + io * p.ldmo + f0) = make_float4(o[0], o[1], o[2], o[3]);
         }
         io_b[b] = io; ov_b[b] = ovalid;
+        if constexpr (IDS) hr_b[b] = ovalid ? p.row_ids[io] : 0;   // the row the dropout hash sees: in flight across the product
       }
     }
     if constexpr (DENSE) {
@@ -246,7 +265,7 @@ __global__ __launch_bounds__(256) void gcn2_conv_kernel(Gcn2Params p) {
         if (sub == 0 && ov_b[b] && fvalid) {
           const float4 z = *reinterpret_cast<const float4*>(T::os(tile) + lr * T::LDA + f0);
           float y[4] = {fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
-          if (p.thr != 0u) drop4(y, (uint64_t)io * (uint64_t)p.H + (uint64_t)f0, (p.H & 3) == 0, seed, p.thr, p.keep_scale);
+          if (p.thr != 0u) drop4(y, (uint64_t)(IDS ? hr_b[b] : io) * (uint64_t)p.H + (uint64_t)f0, (p.H & 3) == 0, seed, p.thr, p.keep_scale);
 #pragma unroll
           for (int c = 0; c < 4; ++c) if (f0 + c >= p.H) y[c] = 0.f;   // pad columns of the row leave as 0
           *reinterpret_cast<float4*>(p.out + io * p.ldo + f0) = make_float4(y[0], y[1], y[2], y[3]);
@@ -256,20 +275,23 @@ __global__ __launch_bounds__(256) void gcn2_conv_kernel(Gcn2Params p) {
   }
 }
 
-template <int LF, int EP, int U, int MODE>
+template <int LF, int EP, int U, int MODE, bool IDS>
 int launch_conv(const Gcn2Params& p, hipStream_t st) {
   constexpr int TR = Tile<LF, EP>::TR;
   static int cap = 0;
   const int64_t ntiles = (p.n_rows + TR - 1) / TR;
-  const int grid = persistent_grid(gcn2_conv_kernel<LF, EP, U, MODE>, ntiles, &cap);
-  hipLaunchKernelGGL((gcn2_conv_kernel<LF, EP, U, MODE>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  const int grid = persistent_grid(gcn2_conv_kernel<LF, EP, U, MODE, IDS>, ntiles, &cap);
+  hipLaunchKernelGGL((gcn2_conv_kernel<LF, EP, U, MODE, IDS>), dim3((unsigned)grid), dim3(256), 0, st, p);
   BGNN_LAUNCH_CHECK();
   return 0;
 }
 
+// the row-id instantiation only where an id is read: a dropout is drawn (thr != 0) by a launch that has an epilogue
 template <int MODE>
 int dispatch_conv(const Gcn2Params& p, hipStream_t st) {
-  return lf_ladder((p.H + 3) / 4, [&](auto LF, auto EP, auto U) { return launch_conv<LF, EP, U, MODE>(p, st); });
+  if (MODE != MODE_SEGMENT && p.row_ids != nullptr && p.thr != 0u)
+    return lf_ladder((p.H + 3) / 4, [&](auto LF, auto EP, auto U) { return launch_conv<LF, EP, U, MODE, MODE != MODE_SEGMENT>(p, st); });
+  return lf_ladder((p.H + 3) / 4, [&](auto LF, auto EP, auto U) { return launch_conv<LF, EP, U, MODE, false>(p, st); });
 }
 
 // ---- backward dense pass -----------------------------------------------------------------------------------------------------
@@ -356,16 +378,16 @@ extern "C" size_t bgnn_gcn2_conv_workspace_bytes(int64_t n_seg, int32_t H) {
   return (size_t)n_seg * (size_t)pad4_ld(H) * sizeof(float) + 16;
 }
 
-extern "C" int bgnn_gcn2_conv_f32(const float* x, int64_t ldx, const float* x0, int64_t ldx0, const float* M, const int32_t* rowptr,
-                                  const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t H, float alpha,
-                                  float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
-                                  int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
-                                  const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
-                                  void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo,
-                                  void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// What both forward entries run: the argument checks, then the ROWS launch and, with hub tables, the SEGMENT and FINISH launches.
+// n_tbl: rows of x (the gather's table); row_ids: NULL, or the global id of every output row for the dropout hash.
+static int conv_run(const float* x, int64_t ldx, int64_t n_tbl, const float* x0, int64_t ldx0, const float* M, const int32_t* rowptr,
+                    const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, const int64_t* row_ids, int32_t H,
+                    float alpha, float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                    int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                    const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                    void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo, hipStream_t st) {
   if (!x || !x0 || !M || !rowptr || !col || !dinv || !out) return BGNN_E_NULL;
-  if (n_rows < 0 || H < 1 || H > SLICE || n_dinv < n_rows) return BGNN_E_SHAPE;
+  if (n_rows < 0 || H < 1 || H > SLICE || n_tbl < n_rows || n_dinv < n_tbl) return BGNN_E_SHAPE;
   if (!(alpha >= 0.f && alpha <= 1.f) || !(p_drop >= 0.f && p_drop < 1.f)) return BGNN_E_SHAPE;
   if (!ld_ok(ldx, H) || !ld_ok(ldx0, H) || !ld_ok(ldo, H) || (m_out_opt && !ld_ok(ldm, H))) return BGNN_E_ALIGN;
   if (!bgnn_aligned16(x) || !bgnn_aligned16(x0) || !bgnn_aligned16(out) || (m_out_opt && !bgnn_aligned16(m_out_opt)))
@@ -383,12 +405,13 @@ extern "C" int bgnn_gcn2_conv_f32(const float* x, int64_t ldx, const float* x0, 
   }
   if (n_rows == 0) return 0;
   Gcn2Params p{};
-  p.tbl = x; p.ldt = ldx; p.n_tbl = n_rows;
+  p.tbl = x; p.ldt = ldx; p.n_tbl = n_tbl;
   p.x0 = x0; p.ldx0 = ldx0;
   p.M = M; p.ldM = ldw;
   p.rowptr = rowptr; p.col = col; p.dinv = dinv; p.n_dinv = n_dinv; p.n_rows = n_rows; p.H = H;
   p.hub_threshold = hubs ? hub_threshold : 0;
   p.n_out = n_rows;
+  p.row_ids = row_ids;
   p.alpha = alpha; p.beta = 1.f - alpha;
   p.m_out = m_out_opt; p.ldmo = ldm;
   p.out = out; p.ldo = ldo;
@@ -405,6 +428,45 @@ extern "C" int bgnn_gcn2_conv_f32(const float* x, int64_t ldx, const float* x0, 
   f.tbl = part; f.ldt = ldw; f.n_tbl = n_seg;
   f.rowptr = hub_seg_ptr_opt; f.col = nullptr; f.n_rows = n_hubs; f.hub_threshold = 0; f.hub_rows = hub_rows_opt;
   return dispatch_conv<MODE_FINISH>(f, st);
+}
+
+// [base, base + (rows - 1) * ld + pad4(H)) of two row-strided views share a float
+static bool extents_overlap(const float* a, int64_t rows_a, int64_t lda, const float* b, int64_t rows_b, int64_t ldb, int32_t H) {
+  if (rows_a <= 0 || rows_b <= 0) return false;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  const uintptr_t a1 = a0 + (uintptr_t)((rows_a - 1) * lda + pad4_ld(H)) * sizeof(float);
+  const uintptr_t b1 = b0 + (uintptr_t)((rows_b - 1) * ldb + pad4_ld(H)) * sizeof(float);
+  return a0 < b1 && b0 < a1;
+}
+
+extern "C" int bgnn_gcn2_conv_f32(const float* x, int64_t ldx, const float* x0, int64_t ldx0, const float* M, const int32_t* rowptr,
+                                  const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows, int32_t H, float alpha,
+                                  float p_drop, uint64_t seed, const uint64_t* seed_dev_opt,
+                                  int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                                  const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                                  void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo,
+                                  void* stream) {
+  return conv_run(x, ldx, n_rows, x0, ldx0, M, rowptr, col, dinv, n_dinv, n_rows, nullptr, H, alpha, p_drop, seed, seed_dev_opt,
+                  hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, m_out_opt, ldm, out,
+                  ldo, (hipStream_t)stream);
+}
+
+extern "C" int bgnn_gcn2_conv_rows_f32(const float* x, int64_t ldx, int64_t n_tbl, const float* x0, int64_t ldx0, const float* M,
+                                       const int32_t* rowptr, const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows,
+                                       const int64_t* row_ids_opt, int32_t H, float alpha, float p_drop, uint64_t seed,
+                                       const uint64_t* seed_dev_opt, int32_t hub_threshold, const int32_t* hub_rows_opt,
+                                       int64_t n_hubs, const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                                       void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo,
+                                       void* stream) {
+  // x stays whole while rows are written: neither output may share a float with any of its n_tbl rows, as whole extents (two
+  // column slices of one buffer are refused as well)
+  if (x && out && H >= 1 && H <= SLICE && n_tbl >= n_rows && n_rows > 0 && ld_ok(ldx, H) && ld_ok(ldo, H)) {
+    if (extents_overlap(x, n_tbl, ldx, out, n_rows, ldo, H)) return BGNN_E_SHAPE;
+    if (m_out_opt && ld_ok(ldm, H) && extents_overlap(x, n_tbl, ldx, m_out_opt, n_rows, ldm, H)) return BGNN_E_SHAPE;
+  }
+  return conv_run(x, ldx, n_tbl, x0, ldx0, M, rowptr, col, dinv, n_dinv, n_rows, row_ids_opt, H, alpha, p_drop, seed, seed_dev_opt,
+                  hub_threshold, hub_rows_opt, n_hubs, hub_seg_ptr_opt, seg_bounds_opt, n_seg, ws_opt, ws_bytes, m_out_opt, ldm, out,
+                  ldo, (hipStream_t)stream);
 }
 
 extern "C" int bgnn_gcn2_conv_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, const float* M, int64_t n_rows,

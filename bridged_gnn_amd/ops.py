@@ -1145,32 +1145,55 @@ def _gcn2_need_m(M, H):
         raise ValueError(f"M must be a contiguous float32 [pad4(H), pad4(H)] = [{pad4(H)}, {pad4(H)}] (zero padding)")
 
 
-def gcn2_conv(x, x0, M, rowptr, col, dinv, n_rows, H, alpha, p_drop=0.0, seed=0, seed_dev=None, hubs=None, m_out=None, out=None):
+def _rows_extent(t, H):
+    """[first byte, one past the last byte) that a row-strided [rows, >= pad4(H)] view spans over pad4(H) columns"""
+    lo = t.data_ptr()
+    return lo, lo + ((int(t.shape[0]) - 1) * t.stride(0) + pad4(H)) * 4 if t.shape[0] else lo
+
+
+def gcn2_conv(x, x0, M, rowptr, col, dinv, n_rows, H, alpha, p_drop=0.0, seed=0, seed_dev=None, hubs=None, m_out=None, out=None,
+              row_ids=None):
     """One GCNII layer with its ReLU and dropout (models/backbones.py:163-197: GCN2Conv(H, alpha, theta, layer) + relu + the next
-    F.dropout; bgnn.h: bgnn_gcn2_conv_f32) -> out [n_rows, pad4(H)] (use out[:, :H]):
+    F.dropout; bgnn.h: bgnn_gcn2_conv_f32 / bgnn_gcn2_conv_rows_f32) -> out [n_rows, pad4(H)] (use out[:, :H]):
     m_i = (1 - alpha) * dinv[i] * sum_{t in row i} dinv[col[t]] * x[col[t]] + alpha * x0[i],  out_i = drop(relu(m_i @ M)),
     M = (1 - beta) * I + beta * weight1 as float32 [pad4(H), pad4(H)] with zero padding (applied untransposed), over the CSR of
     `gcn_aggregate` (`GcnGraph`: csr.rowptr, col, dinv, hubs).  x / x0 / out / m_out: 2-D row-strided views with unit column
-    stride, n_rows rows (x may be a view of a wider table); 1 <= H <= 128, 0 <= alpha <= 1.  Dropout at p_drop keeps element
-    i * H + column by the (seed + seed_dev, element index) hash of `gcn_aggregate`; p_drop = 0 draws no mask.
+    stride (x may be a view of a wider table); 1 <= H <= 128, 0 <= alpha <= 1.
+    The graph may be RECTANGULAR (a rank's rows of a partition): rowptr [n_rows + 1] and x0 / out / m_out have exactly n_rows rows,
+    x has x.shape[0] >= n_rows rows (the owned rows, then the halo slots), ids in col < x.shape[0], and dinv covers the table:
+    dinv.shape[0] >= x.shape[0] (the gather reads dinv[col]).
+    Dropout at p_drop keeps element i * H + column by the (seed + seed_dev, element index) hash of `gcn_aggregate`; p_drop = 0
+    draws no mask.  row_ids: int64 [n_rows], contiguous, the GLOBAL row id of every output row: the element is then
+    row_ids[i] * H + column, in the row launch and in a hub row's finish launch -- the masks of the whole-graph call in this
+    rank's rows; None = row i itself.
     m_out: None (evaluation: the mix never leaves the chip) or a [n_rows, >= pad4(H)] buffer that receives m (training: the
-    backward's operand); out has the same bits either way.  hubs: as in `gcn_aggregate`.  No atomics, no host synchronisation."""
+    backward's operand); out has the same bits either way.  hubs: as in `gcn_aggregate`, the tables of the n_rows rows.
+    A square call without row_ids takes bgnn_gcn2_conv_f32 as before; every other call takes bgnn_gcn2_conv_rows_f32, the same
+    launch sequence (identity ids on a square graph give the same bits).  Still refused: H > 128, x with fewer than n_rows rows,
+    x0 / out / m_out of another row count, dinv shorter than x, and out or m_out overlapping x -- the same tensor always; on the
+    rectangular / row-id route any overlap of the byte extents of the views, so the front rows of x's own buffer cannot be the
+    output.  No atomics, no host synchronisation."""
     n_rows, H, alpha = int(n_rows), int(H), float(alpha)
     if not gcn2_supported(H):
         raise ValueError(f"gcn2_conv takes 1 <= H <= {GCN2_MAX_WIDTH}, got {H}")
     _need_rows_f32(x, "x", H)
     _need_rows_f32(x0, "x0", H)
     _gcn2_need_m(M, H)
-    if x.shape[0] != n_rows or x0.shape[0] != n_rows:
-        raise ValueError(f"x and x0 must have n_rows = {n_rows} rows (the graph is square)")
-    if dinv.dtype != torch.float32 or dinv.dim() != 1 or dinv.shape[0] < n_rows:
-        raise ValueError("dinv must be float32 [>= n_rows]")
+    n_tbl = int(x.shape[0])
+    if n_tbl < n_rows or x0.shape[0] != n_rows:
+        raise ValueError(f"x must have at least n_rows = {n_rows} rows and x0 exactly n_rows rows, got {n_tbl} and {x0.shape[0]}")
+    if dinv.dtype != torch.float32 or dinv.dim() != 1 or dinv.shape[0] < n_tbl:
+        raise ValueError("dinv must be float32 [>= rows of x]")
     if rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.shape[0] < n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
         raise ValueError("rowptr must be int32 [n_rows + 1] and col int32 [E]")
     if not 0.0 <= alpha <= 1.0:
         raise ValueError("alpha must lie in [0, 1]")
     if not 0.0 <= float(p_drop) < 1.0:
         raise ValueError("p_drop must lie in [0, 1)")
+    if row_ids is not None:
+        L._check_device(row_ids)
+        if row_ids.dtype != torch.int64 or row_ids.dim() != 1 or row_ids.shape[0] != n_rows or not row_ids.is_contiguous():
+            raise ValueError(f"row_ids must be a contiguous int64 [n_rows] = [{n_rows}]")
     if out is None:
         out = torch.empty(n_rows, pad4(H), dtype=torch.float32, device=x.device)
     else:
@@ -1179,6 +1202,14 @@ def gcn2_conv(x, x0, M, rowptr, col, dinv, n_rows, H, alpha, p_drop=0.0, seed=0,
         _need_rows_f32(m_out, "m_out", H)
     if out.shape[0] != n_rows or (m_out is not None and m_out.shape[0] != n_rows):
         raise ValueError(f"out and m_out must have n_rows = {n_rows} rows")
+    rows_entry = row_ids is not None or n_tbl != n_rows
+    if rows_entry:
+        xlo, xhi = _rows_extent(x, H)
+        for name, t in (("out", out), ("m_out", m_out)):
+            if t is not None and n_rows:
+                lo, hi = _rows_extent(t, H)
+                if lo < xhi and xlo < hi:
+                    raise ValueError(f"{name} overlaps x: the rows of x are gathered while {name} is written")
     lib = L.lib()
     if hubs is None:
         hub_args, ws = (0, None, 0, None, None, 0, None, 0), None
@@ -1187,11 +1218,18 @@ def gcn2_conv(x, x0, M, rowptr, col, dinv, n_rows, H, alpha, p_drop=0.0, seed=0,
         n_seg = int(bounds.shape[0]) // 2
         ws = torch.empty(max(int(lib.bgnn_gcn2_conv_workspace_bytes(n_seg, H)), 16), dtype=torch.uint8, device=x.device)
         hub_args = (int(thr), L.ptr(rows), int(rows.shape[0]), L.ptr(seg_ptr), L.ptr(bounds), n_seg, L.ptr(ws), ws.numel())
-    rc = lib.bgnn_gcn2_conv_f32(
-        L.ptr_rows(x), x.stride(0), L.ptr_rows(x0), x0.stride(0), L.ptr(M), L.ptr(rowptr), L.ptr(col), L.ptr(dinv),
-        int(dinv.shape[0]), n_rows, H, alpha, float(p_drop), *_seed_args(seed, seed_dev), *hub_args, L.ptr_rows(m_out),
-        m_out.stride(0) if m_out is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
-    L.check(rc, "bgnn_gcn2_conv_f32")
+    tail = (*_seed_args(seed, seed_dev), *hub_args, L.ptr_rows(m_out), m_out.stride(0) if m_out is not None else 0, L.ptr_rows(out),
+            out.stride(0), L.stream())
+    if rows_entry:
+        rc = lib.bgnn_gcn2_conv_rows_f32(
+            L.ptr_rows(x), x.stride(0), n_tbl, L.ptr_rows(x0), x0.stride(0), L.ptr(M), L.ptr(rowptr), L.ptr(col), L.ptr(dinv),
+            int(dinv.shape[0]), n_rows, L.ptr(row_ids), H, alpha, float(p_drop), *tail)
+        L.check(rc, "bgnn_gcn2_conv_rows_f32")
+    else:
+        rc = lib.bgnn_gcn2_conv_f32(
+            L.ptr_rows(x), x.stride(0), L.ptr_rows(x0), x0.stride(0), L.ptr(M), L.ptr(rowptr), L.ptr(col), L.ptr(dinv),
+            int(dinv.shape[0]), n_rows, H, alpha, float(p_drop), *tail)
+        L.check(rc, "bgnn_gcn2_conv_f32")
     return out
 
 

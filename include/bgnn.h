@@ -49,7 +49,8 @@ extern "C" {
  * the _rows_ entries are gone.  The APPNP baseline's bgnn_appnp_propagate_f32 with its workspace size, bgnn_appnp_log_softmax_bwd_f32 and
  * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 were added after 116 as purely additive symbols, and so were the
  * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32, and the GCNII
- * baseline's bgnn_gcn2_conv_f32 with its workspace size and bgnn_gcn2_conv_bwd_f32. */
+ * baseline's bgnn_gcn2_conv_f32 with its workspace size and bgnn_gcn2_conv_bwd_f32, and the partitioned GCNII's
+ * bgnn_gcn2_conv_rows_f32. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -659,6 +660,23 @@ int bgnn_gcn2_conv_f32(const float* x, int64_t ldx, const float* x0, int64_t ldx
 int bgnn_gcn2_conv_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, const float* M, int64_t n_rows,
                            int32_t H, float alpha, float p_drop, float* gz, int64_t ldgz, float* t, int64_t ldt,
                            float* gx0, int64_t ldgx0, void* stream);
+/* The GCNII conv over a RECTANGULAR graph (GCN2, models/backbones.py:163-197, on a destination-node partition: a rank's owned
+ * rows gather from [owned rows ; halo slots]): bgnn_gcn2_conv_f32 with
+ *   n_tbl        rows of x, n_tbl >= n_rows; rowptr [n_rows+1], ids in col < n_tbl (ids >= n_tbl are never dereferenced);
+ *   row_ids_opt  NULL, or int64 [n_rows]: the GLOBAL id of every output row.  The dropout element of (row i, column) is then
+ *                row_ids[i] * H + column -- in the row launch and, for a hub row, in the finish launch through hub_rows -- the rule
+ *                of bgnn_gcn_aggregate_f32's row_id_opt: every rank drops what the whole-graph call drops in its rows.
+ * x0, m_out and out have n_rows rows; dinv covers the table, n_dinv >= n_tbl (else BGNN_E_SHAPE): the gather reads dinv[col].
+ * out and m_out may not overlap x: checked on the byte extents [base, base + ((rows - 1) * ld + pad4(H)) * 4) of the row-strided
+ * views, x over its n_tbl rows, so the front rows of the buffer x lives in are refused, and so are two column slices of one
+ * buffer; BGNN_E_SHAPE.  Everything else as bgnn_gcn2_conv_f32, which is this entry with n_tbl = n_rows and no ids through the
+ * same launch sequence: identity ids on a square graph give its bits. */
+int bgnn_gcn2_conv_rows_f32(const float* x, int64_t ldx, int64_t n_tbl, const float* x0, int64_t ldx0, const float* M,
+                            const int32_t* rowptr, const int32_t* col, const float* dinv, int64_t n_dinv, int64_t n_rows,
+                            const int64_t* row_ids_opt, int32_t H, float alpha, float p_drop, uint64_t seed,
+                            const uint64_t* seed_dev_opt, int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
+                            const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
+                            void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
