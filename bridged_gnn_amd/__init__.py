@@ -27,6 +27,9 @@ def __getattr__(name):
     if name in ("GCN2", "GCN2Conv", "train_gcn2_noDTC"):   # the GCNII baseline's, likewise
         from . import gcn2
         return getattr(gcn2, name)
+    if name in ("DeeperGCN", "GENConv", "DeepGCNLayer", "train_deepergcn_noDTC"):   # the DeeperGCN baseline's, likewise
+        from . import deepergcn
+        return getattr(deepergcn, name)
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)

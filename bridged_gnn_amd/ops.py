@@ -1259,6 +1259,97 @@ def gcn2_conv_bwd(y, grad_y, M, H, alpha, p_drop):
     return gz, t, gx0
 
 
+def _gen_need_t(t):
+    L._check_device(t)
+    if t.dtype != torch.float32 or t.numel() != 1 or not t.is_contiguous():
+        raise ValueError("t must be a float32 tensor of one element (the temperature stays on the device)")
+
+
+def _gen_need_csr(rowptr, col, n_rows, what="rowptr"):
+    if rowptr.dtype != torch.int32 or rowptr.dim() != 1 or rowptr.shape[0] < n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
+        raise ValueError(f"{what} must be int32 [rows + 1] and its ids int32 [E]")
+
+
+def gen_softmax_aggregate(x, rowptr, col, t, n_rows, H, save=None, out=None):
+    """DeeperGCN's softmax aggregation with the root add (models/backbones.py:130-161: GENConv(aggr='softmax', learn_t=True) in
+    front of its MLP; bgnn.h: bgnn_gen_softmax_aggregate_f32) -> z [n_rows, pad4(H)] (use z[:, :H]):
+    v_j = relu(x_j) + 1e-7, alpha_ij = softmax over the in-edges of row i of t * v_j PER CHANNEL, z_i = sum_j alpha_ij v_j + x_i
+    (a row without in-edges: x_i bit for bit).  (rowptr, col) is the by-destination CSR exactly as given (`SageGraph`: duplicates
+    are separate messages, self loops ordinary edges).  x: a 2-D row-strided view with unit column stride and at least n_rows
+    rows (it may be a view of a wider table; ids in col outside it add nothing); t: a float32 tensor of ONE element on the device
+    (the learnable temperature, any sign or 0; never read by the host); any H >= 1.
+    save: None (evaluation) or a pair (lse, o) of [n_rows, >= pad4(H)] buffers with one row stride that receive
+    lse_i = log sum_j exp(t * v_j) and o_i = z_i - x_i per row and channel (training: `gen_softmax_aggregate_bwd`'s operands); z has
+    the same bits either way.  Pad columns of z, lse and o are written as 0.  No atomics, no host synchronisation."""
+    n_rows, H = int(n_rows), int(H)
+    if H < 1:
+        raise ValueError(f"gen_softmax_aggregate takes H >= 1, got {H}")
+    _need_rows_f32(x, "x", H)
+    _gen_need_t(t)
+    if x.shape[0] < n_rows:
+        raise ValueError(f"x must have at least n_rows = {n_rows} rows, got {x.shape[0]}")
+    _gen_need_csr(rowptr, col, n_rows)
+    lse = o = None
+    if save is not None:
+        lse, o = save
+        for name, s in (("lse", lse), ("o", o)):
+            _need_rows_f32(s, name, H)
+            if s.shape[0] != n_rows:
+                raise ValueError(f"{name} must have n_rows = {n_rows} rows")
+        if lse.stride(0) != o.stride(0) or lse.data_ptr() == o.data_ptr():
+            raise ValueError("lse and o must be two distinct buffers with one row stride")
+    if out is None:
+        out = torch.empty(n_rows, pad4(H), dtype=torch.float32, device=x.device)
+    else:
+        _need_rows_f32(out, "out", H)
+        if out.shape[0] != n_rows or out.data_ptr() == x.data_ptr():
+            raise ValueError(f"out must have n_rows = {n_rows} rows and be distinct from x")
+    rc = L.lib().bgnn_gen_softmax_aggregate_f32(
+        L.ptr_rows(x), x.stride(0), int(x.shape[0]), L.ptr(rowptr), L.ptr(col), int(col.shape[0]), n_rows, H, L.ptr(t),
+        L.ptr_rows(lse), L.ptr_rows(o), lse.stride(0) if lse is not None else 0, L.ptr_rows(out), out.stride(0), L.stream())
+    L.check(rc, "bgnn_gen_softmax_aggregate_f32")
+    return out
+
+
+def gen_softmax_aggregate_bwd(x, grad_z, save, t_rowptr, t_dst, t, H, grad_x=None):
+    """Backward of `gen_softmax_aggregate(x, rowptr, col, t, n_rows, H, save)` (models/backbones.py:130-161; bgnn.h:
+    bgnn_gen_softmax_aggregate_bwd_f32) -> (grad_x [rows of x, pad4(H)] with zero pad columns, grad_t float32 [1]).
+    grad_z: the gradient at z, [n_rows, >= pad4(H)]; save = (lse, o): the forward's tables; (t_rowptr, t_dst): the by-source view of
+    the same edges (`DstCSR.transposed()`), t_rowptr over the rows of x.  One walk: the group of source row j forms
+    a = exp(t * v_j - lse_i) per out-edge and accumulates dv_j = sum a g_i (1 + t (v_j - o_i)) and the centred
+    grad_t = sum a g_i (v_j - o_i)^2; grad_x[j] = [x_j > 0] dv_j + g_j is written once.  grad_t is summed from per-block fp64
+    partials in a fixed order: no atomics, the same bits on every run, nothing carried over between calls, no host
+    synchronisation."""
+    H = int(H)
+    if H < 1:
+        raise ValueError(f"gen_softmax_aggregate_bwd takes H >= 1, got {H}")
+    lse, o = save
+    _need_rows_f32(x, "x", H)
+    _need_rows_f32(grad_z, "grad_z", H)
+    _need_rows_f32(lse, "lse", H)
+    _need_rows_f32(o, "o", H)
+    _gen_need_t(t)
+    n_src, n_rows = int(x.shape[0]), int(grad_z.shape[0])
+    if lse.shape[0] != n_rows or o.shape[0] != n_rows or lse.stride(0) != o.stride(0):
+        raise ValueError("lse and o must have grad_z's rows and one row stride")
+    _gen_need_csr(t_rowptr, t_dst, n_src, "t_rowptr")
+    if grad_x is None:
+        grad_x = torch.empty(n_src, pad4(H), dtype=torch.float32, device=x.device)
+    else:
+        _need_rows_f32(grad_x, "grad_x", H)
+        if grad_x.shape[0] != n_src:
+            raise ValueError(f"grad_x must have the {n_src} rows of x")
+    lib = L.lib()
+    grad_t = torch.empty(1, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(lib.bgnn_gen_softmax_aggregate_workspace_bytes(n_src, H)), 16), dtype=torch.uint8, device=x.device)
+    rc = lib.bgnn_gen_softmax_aggregate_bwd_f32(
+        L.ptr_rows(x), x.stride(0), n_src, L.ptr_rows(grad_z), grad_z.stride(0), L.ptr_rows(lse), L.ptr_rows(o), lse.stride(0), n_rows,
+        L.ptr(t_rowptr), L.ptr(t_dst), int(t_dst.shape[0]), H, L.ptr(t), L.ptr_rows(grad_x), grad_x.stride(0), L.ptr(grad_t),
+        L.ptr(ws), ws.numel(), L.stream())
+    L.check(rc, "bgnn_gen_softmax_aggregate_bwd_f32")
+    return grad_x, grad_t
+
+
 APPNP_STORES = {"state": 0, "out": 1, "log_softmax": 2}
 
 

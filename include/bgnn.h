@@ -50,7 +50,8 @@ extern "C" {
  * bgnn_feature_dropout_f32 / bgnn_feature_dropout_bwd_f32 were added after 116 as purely additive symbols, and so were the
  * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32, and the GCNII
  * baseline's bgnn_gcn2_conv_f32 with its workspace size and bgnn_gcn2_conv_bwd_f32, and the partitioned GCNII's
- * bgnn_gcn2_conv_rows_f32. */
+ * bgnn_gcn2_conv_rows_f32, and the DeeperGCN baseline's bgnn_gen_softmax_aggregate_f32, bgnn_gen_softmax_aggregate_bwd_f32 and
+ * its workspace size. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -677,6 +678,44 @@ int bgnn_gcn2_conv_rows_f32(const float* x, int64_t ldx, int64_t n_tbl, const fl
                             const uint64_t* seed_dev_opt, int32_t hub_threshold, const int32_t* hub_rows_opt, int64_t n_hubs,
                             const int32_t* hub_seg_ptr_opt, const int32_t* seg_bounds_opt, int64_t n_seg,
                             void* ws_opt, size_t ws_bytes, float* m_out_opt, int64_t ldm, float* out, int64_t ldo, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * DeeperGCN softmax aggregation (the DeeperGCN baseline, models/backbones.py:130-161: the message, the aggregation and the root
+ * add of PyG GENConv(H, H, aggr='softmax', t=1.0, learn_t=True, num_layers=2, norm='layer') -- everything in front of its MLP),
+ * one walk over the by-destination CSR exactly as given (duplicates are separate messages, self loops ordinary edges, none added):
+ *     v_j = relu(x_j) + 1e-7
+ *     alpha_ij[c] = softmax over the in-edges j of row i of (t * v_j[c])        per destination AND per channel
+ *     o_i = sum_j alpha_ij * v_j   (0 for a row without in-edges),      z_i = o_i + x_i   (the raw x_i)
+ * x: [n_tbl, ldx] node rows, n_tbl >= n_rows (row i of z adds row i of x), ids in col >= n_tbl are never dereferenced and add
+ * nothing; rowptr [n_rows+1] is cut to [0, n_edges] (a malformed rowptr gives a wrong sum, never a stray read).  t: ONE float in
+ * DEVICE memory (the learnable temperature; the host never waits for it), any sign or 0 -- the running maximum is over t * v.
+ * z: [n_rows, ldz], distinct from x; pad columns H .. pad4(H)-1 are written as 0 whatever x holds there.  Any H >= 1; leading
+ * dimensions in floats, % 4 == 0 and >= pad4(H) (x may be a view of a wider table), bases 16-B aligned.  Columns run in
+ * independent slices of 128.
+ * lse_opt / o_opt: both NULL (evaluation) or both [n_rows, lds] (training): lse_i[c] = log sum_j exp(t * v_j[c]) and o_i[c], pad
+ * columns 0; a row without in-edges stores z_i = x_i bit for bit, lse = 0 and o = 0.  z has the same bits either way.
+ * Each lane keeps (max, sum, weighted sum) per channel, takes the maximum of a batch of gathered rows first and rescales once per
+ * batch; narrow rows merge their sub-groups by a fixed butterfly.  No float atomics, bit-identical from run to run, nothing is
+ * allocated.  A hub row is walked by one lane group.
+ *
+ * bgnn_gen_softmax_aggregate_bwd_f32 (models/backbones.py:130-161, the backward of the same aggregation), one walk over the
+ * by-source view (t_rowptr [n_src+1], t_dst: the destinations of every source's out-edges, ids >= n_rows add nothing):
+ *     a_ij = exp(t * v_j - lse_i)                                    (= alpha_ij, <= 1 up to rounding: no overflow)
+ *     dv_j = sum over the out-edges j -> i of a_ij * g_i * (1 + t * (v_j - o_i))
+ *     grad_x[j] = [x_j > 0] * dv_j + g_j   (g_j for j < n_rows)
+ *     grad_t    = sum over edges and channels of a_ij * g_i * (v_j - o_i)^2       (the centred form)
+ * x: [n_src, ldx]; grad_z (g), lse, o: [n_rows, .] -- the gradient at z and the forward's tables; grad_x: [n_src, ldgx], written
+ * once, pad columns 0, distinct from every input; grad_t: one float in device memory, overwritten.  grad_t leaves the walk as one
+ * fp64 partial per block and is summed in a fixed order by a second, one-block launch per column slice: no float atomics, and
+ * nothing is carried from one call to the next.  ws: bgnn_gen_softmax_aggregate_workspace_bytes(n_src, H) bytes. */
+int bgnn_gen_softmax_aggregate_f32(const float* x, int64_t ldx, int64_t n_tbl, const int32_t* rowptr, const int32_t* col,
+                                   int64_t n_edges, int64_t n_rows, int32_t H, const float* t, float* lse_opt, float* o_opt,
+                                   int64_t lds, float* z, int64_t ldz, void* stream);
+size_t bgnn_gen_softmax_aggregate_workspace_bytes(int64_t n_src, int32_t H);
+int bgnn_gen_softmax_aggregate_bwd_f32(const float* x, int64_t ldx, int64_t n_src, const float* grad_z, int64_t ldg,
+                                       const float* lse, const float* o, int64_t lds, int64_t n_rows, const int32_t* t_rowptr,
+                                       const int32_t* t_dst, int64_t n_edges, int32_t H, const float* t, float* grad_x,
+                                       int64_t ldgx, float* grad_t, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
