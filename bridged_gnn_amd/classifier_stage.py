@@ -37,6 +37,46 @@ class ClassifierStage:
         ld = self.ld
         return [(t2s[:, j * ld:(j + 1) * ld], s2t[:, j * ld:(j + 1) * ld]) for j in range(3)]
 
+    # ---- 32-byte rows (C <= 2): [h0c0 h0c1 h1c0 h1c1 | h2c0 h2c1 0 0] per node and table -----------------------------------------
+    def rows32_eligible(self, dtype=torch.float32, training=False):
+        """the host half of the layout decision: a plain stage of at most two classes, fp32, the eval forward"""
+        return self.plain and self.C <= 2 and dtype == torch.float32 and not training
+
+    @staticmethod
+    def rows32_views(t2s, s2t):
+        """(h_t2s, h_s2t) column views of head j = 0, 1, 2 in two [rows, 8] tables; head 2's view takes the padding along"""
+        return [(t2s[:, 0:2], s2t[:, 0:2]), (t2s[:, 2:4], s2t[:, 2:4]), (t2s[:, 4:8], s2t[:, 4:8])]
+
+    @staticmethod
+    def rows32_pack(tab):
+        """[rows, 3 * 4] padded table (at most two real columns per head) -> [rows, 8]"""
+        t = tab.view(tab.shape[0], 3, 4)
+        return torch.cat((t[:, 0, :2], t[:, 1, :2], t[:, 2, :]), dim=1).contiguous()
+
+    @staticmethod
+    def rows32_unpack(tab8):
+        """[rows, 8] -> the padded [rows, 3 * 4] table with the same values, zeros in the padding"""
+        out = tab8.new_zeros(tab8.shape[0], 3, 4)
+        out[:, 0, :2], out[:, 1, :2], out[:, 2, :] = tab8[:, 0:2], tab8[:, 2:4], tab8[:, 4:8]
+        return out.view(tab8.shape[0], 12)
+
+    def eval_tables_rows32(self, x, mask_u8, sums_h, csr, arena):
+        """the two tables of the eval forward as 32-byte rows, filled -> (t2s, s2t), or None where the stage, the one-pass
+        producer or the walk's plan (one window, no hub rows, BGNN_HEADS_ROWS32) does not take them: the caller then builds
+        the padded tables.  Decided before anything is written -- no other kernel reads this layout."""
+        if not self.rows32_eligible(x.dtype) or x.stride(1) != 1:
+            return None
+        ops_a = self._one_pass_operands(x, sums_h)
+        if ops_a is None:
+            return None
+        both = torch.empty(2, x.shape[0], 8, dtype=torch.float32, device=x.device)       # one allocation: one window
+        t2s, s2t = both[0], both[1]
+        if not ops.heads_rows32_plan(t2s, s2t, csr, self.C, self.slope, row_end=x.shape[0]):
+            return None
+        a = self.one_pass(x, mask_u8, sums_h, None, arena, rows32=(t2s, s2t), operands=ops_a)
+        self.target_stage_b(a, mask_u8, self.rows32_views(t2s, s2t)[2], rows32=True)
+        return t2s, s2t
+
     def attention(self, autograd=False):
         """(a_t2s, a_s2t) of the three heads as [3, C]: stacked under autograd for training, else detached and re-packed only when
         a weight changes"""
@@ -120,9 +160,8 @@ class ClassifierStage:
         return self._tf_pack[1]
 
     # ---- eval tables -----------------------------------------------------------------------------------------------------
-    def one_pass(self, x, mask_u8, sums_h, views, arena):
-        """heads 0 / 1 and stage A of head 2 from ONE pass over x (bgnn_classifier_stage_f32); needs the GLOBAL domain sums of x
-        up front.  -> stage A's result (see `target_stage_a`), or None outside the kernel's envelope."""
+    def _one_pass_operands(self, x, sums_h):
+        """(pair, pack_t) of `one_pass`, or None outside the kernel's envelope"""
         if sums_h is None or x.dtype != torch.float32 or x.stride(1) != 1:
             return None
         self.fold_transformer()
@@ -133,9 +172,21 @@ class ClassifierStage:
         pair = self.convs[0].packed(x.shape[1], self.convs[1])
         if not ops.classifier_stage_supported(x, pair, self._tf_w0, pack_t):
             return None
-        n_s = 2 * ops.pad4(dout) + 2
+        return pair, pack_t
+
+    def one_pass(self, x, mask_u8, sums_h, views, arena, rows32=None, operands=None):
+        """heads 0 / 1 and stage A of head 2 from ONE pass over x (bgnn_classifier_stage_f32); needs the GLOBAL domain sums of x
+        up front.  -> stage A's result (see `target_stage_a`), or None outside the kernel's envelope.  `rows32` = (t2s, s2t):
+        heads 0 / 1 into tables of 32-byte rows instead of `views`."""
+        if operands is None:
+            operands = self._one_pass_operands(x, sums_h)
+        if operands is None:
+            return None
+        pair, pack_t = operands
+        n_s = 2 * ops.pad4(self._tf_w0.shape[0]) + 2
         sums_t = arena.take(n_s) if arena is not None else torch.zeros(n_s, dtype=torch.float64, device=x.device)
-        raw = ops.classifier_stage(x, mask_u8, sums_h, pair, [views[0], views[1]], self._tf_w0, self._tf_b0, sums_t, pack_t, relu=True)
+        outs = [views[0], views[1]] if rows32 is None else None
+        raw = ops.classifier_stage(x, mask_u8, sums_h, pair, outs, self._tf_w0, self._tf_b0, sums_t, pack_t, relu=True, rows32=rows32)
         return raw, None, sums_t
 
     def pair_tables(self, x, mask_u8, sums_h, views):
@@ -159,13 +210,14 @@ class ClassifierStage:
             sums1 = ops.domain_sums(h1, mask_u8)
         return None, h1, sums1
 
-    def target_stage_b(self, stage_a, mask_u8, out, sums_t=None):
+    def target_stage_b(self, stage_a, mask_u8, out, sums_t=None, rows32=False):
         """head 2's (h_t2s, h_s2t) tables into `out` from stage A's result; `sums_t`: the GLOBAL domain sums of h1 where stage A's
-        are one rank's share"""
+        are one rank's share; `rows32` (raw form only): `out` is the second half of 32-byte rows"""
         raw, h1, sums_t = (*stage_a[:2], sums_t if sums_t is not None else stage_a[2])
         if raw is not None:
-            ops.narrow_transform_finish(raw, mask_u8, sums_t, self.composed_target_pack(ops.pad4(self._tf_w0.shape[0])), out)
+            ops.narrow_transform_finish(raw, mask_u8, sums_t, self.composed_target_pack(ops.pad4(self._tf_w0.shape[0])), out, rows32=rows32)
         else:
+            assert not rows32
             ops.adaptedconv_transform(h1, mask_u8, None, self.composed_target_pack(h1.shape[1]), out=[out], sums=sums_t)
 
     def target_tables(self, x, mask_u8, out, arena=None, sums_out=None):

@@ -1344,6 +1344,203 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BGNN_HEADS_
   }
 }
 
+// ---- the three-head walk on 32-byte node rows (D <= 2) ---------------------------------------------------------------------------
+// At D <= 2 half of agg_heads_fast_kernel's 48-byte row is padding.  Here a table row is [h0c0 h0c1 h1c0 h1c1 | h2c0 h2c1 0 0]
+// (bgnn_adaptedconv_aggregate_heads_rows32_f32): TWO lanes gather an edge instead of three, a wave holds 16 rows with all 64 lanes
+// live (10 rows, 60 lanes), so a gather instruction covers 32 edges instead of 20, and no row straddles a 128-byte line.  Lane A
+// of a sub-group (part 0) takes bytes 0-15 and carries the online-softmax state of heads 0 and 1, lane B (part 1) takes bytes
+// 16-31 and carries head 2 in its first pair; its second pair is the padding, walked with a zero attention vector and never stored.
+// Everything else is agg_heads_fast_kernel's: the one-window descriptor and the dead-slot offset, one 16-byte id load per lane and
+// the swap between the sub-groups (the partner is lane ^ 2), the clamped dwords of a launch's last waves, the wave-uniform step
+// loop, and per head the SAME operations in the same order on the two real columns -- the padded columns' terms there are
+// fma(0, 0, t) = t and 0 * x = 0 -- so `out` is bit-identical (tests/test_gpu_heads_rows32.py).  `out` keeps 16 bytes per head.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BGNN_HEADS_FAST_WAVES))) void agg_heads_rows32_kernel(AggParams p) {
+  constexpr int EP = 2, U = 4, GPW = 16, RPB = 4 * GPW;
+  constexpr uint32_t RS = 32u;                       // bytes between consecutive nodes of a table
+  constexpr int32_t STEP = EP * U;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 2, sub = (lane >> 1) & 1, part = lane & 1;
+  const int32_t row0 = (int32_t)p.row_begin, row1 = (int32_t)p.row_end;
+  const int32_t ntiles = (row1 - row0 + RPB - 1) / RPB;
+  const uint64_t tb = (uint64_t)p.tbl_base;
+  const u32x4_t rt = {(uint32_t)tb, (uint32_t)(tb >> 32) & 0xffffu, p.tbl_bytes, 0x00020000u};     // the asm gathers' descriptor
+  const __amdgpu_buffer_rsrc_t rtb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tbl_base), (short)0, (int)p.tbl_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out, (short)0, (int)((uint32_t)row1 * 48u), 0x00020000);
+  const uint32_t dead = p.dead_off;
+  const uint32_t cend = (uint32_t)p.rowptr[row1] * 4u;                         // bytes of `col` this launch's rows own
+  const int pidx = (lane ^ 2) * 4;                   // ds_bpermute address of the other sub-group's lane of my part
+  const f2 sl = {p.slope, p.slope};
+  // the attention vectors, [domain][part] = (first head's two columns | second head's), zero where there is no column or head
+  __shared__ float4 a_lds[2][2];
+  if (threadIdx.x < 4) {
+    const float* a = threadIdx.x < 2 ? p.a_s2t : p.a_t2s;
+    const int h0 = (threadIdx.x & 1) * 2;
+    float4 v;
+    v.x = a[h0 * p.D];
+    v.y = p.D > 1 ? a[h0 * p.D + 1] : 0.f;
+    v.z = h0 == 0 ? a[p.D] : 0.f;
+    v.w = (h0 == 0 && p.D > 1) ? a[p.D + 1] : 0.f;
+    a_lds[threadIdx.x >> 1][threadIdx.x & 1] = v;
+  }
+  __syncthreads();
+  const int32_t per = (ntiles + 7) / 8, seg_len = (per + bgnn::XCD_NSEG - 1) / bgnn::XCD_NSEG;
+  const int32_t xcd = blockIdx.x % 8, nslots = ((int32_t)gridDim.x + 7 - xcd) / 8;
+  int32_t sg = 0, r = blockIdx.x / 8;
+  for (;; r += nslots) {
+    while (r >= seg_len) { r -= seg_len; ++sg; }
+    if (sg >= bgnn::XCD_NSEG) break;
+    const int32_t tile = (sg * 8 + xcd) * seg_len + r;
+    if (tile >= ntiles) continue;                    // padding of the last segments
+    const int32_t i = row0 + tile * RPB + wave * GPW + g;
+    const bool rvalid = i < row1;
+    const int32_t ic = rvalid ? i : row0;
+    const bool dom_s = p.mask[ic] != 0;
+    const int32_t rp0 = p.rowptr[ic], rp1 = p.rowptr[ic + 1];
+    const int32_t beg = rvalid ? rp0 : 0, end = rvalid ? rp1 : 0;
+    const uint32_t lbase = (dom_s ? p.off_t2s : p.off_s2t) + (uint32_t)part * 16u;     // this lane's half of node 0 of its table
+    const float4 a4 = a_lds[dom_s ? 1 : 0][part];
+    f4v_t hi = __builtin_bit_cast(f4v_t, __builtin_amdgcn_raw_buffer_load_b128(rtb, lbase + __umul24((uint32_t)ic, RS), 0, 0));
+    f2 accA = {0.f, 0.f}, accB = {0.f, 0.f};         // (A, B: the first and the second head of this lane's half)
+    float mA = -INFINITY, sA = 0.f, mB = -INFINITY, sB = 0.f;
+    const int32_t niter = (int32_t)((uint32_t)(end - beg + STEP - 1) / (uint32_t)STEP);
+    int32_t rem = end - beg - sub;                   // slot u of the step is alive while rem > u * EP
+    // (the ids: see agg_heads_fast_kernel -- the two lanes of a sub-group read the same 16 bytes)
+    const int32_t bfirst = __builtin_amdgcn_readfirstlane(beg);
+    const bool slow = __builtin_amdgcn_ballot_w64(rvalid && (uint32_t)(end + (end - bfirst) + 16) * 4u > cend) != 0;
+    const uint32_t elast = (uint32_t)max(end - 1, 0) * 4u;
+    uint32_t off[U] = {dead, dead, dead, dead};
+    const bool any = __builtin_amdgcn_ballot_w64(niter > 0) != 0;      // wave-uniform; (no edge at all: `col` may be empty)
+    auto walk = [&](auto slow_tag) {
+      constexpr bool SLOW = decltype(slow_tag)::value;
+      uint32_t xoff = SLOW ? (uint32_t)(beg + sub) * 4u : (uint32_t)((rvalid ? beg : bfirst) + 4 * sub) * 4u;
+      auto request = [&](u32x4_t& q) {
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SLOW) {
+          uint32_t eo[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) eo[u] = min(xoff + (uint32_t)(u * EP * 4), elast);
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.x) : "v"(eo[0]), "s"(p.col) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.y) : "v"(eo[1]), "s"(p.col) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.z) : "v"(eo[2]), "s"(p.col) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(q.w) : "v"(eo[3]), "s"(p.col) : "memory");
+        } else {
+          asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(q) : "v"(xoff), "s"(p.col) : "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      // (the step's state rides through the wait so that all of its arithmetic is in front of it)
+      auto take = [&](u32x4_t& q, uint32_t (&id)[U]) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(q), "+v"(mA), "+v"(sA), "+v"(accA), "+v"(mB), "+v"(sB), "+v"(accB) : : "memory");
+        if constexpr (SLOW) {
+          id[0] = q.x; id[1] = q.y; id[2] = q.z; id[3] = q.w;
+        } else {                                       // sub-group 0 holds edges 0..3 and sends 1, 3; sub-group 1 holds 4..7 and sends 4, 6
+          const uint32_t r0 = (uint32_t)__builtin_amdgcn_ds_bpermute(pidx, (int)(sub ? q.x : q.y));
+          const uint32_t r1 = (uint32_t)__builtin_amdgcn_ds_bpermute(pidx, (int)(sub ? q.z : q.w));
+          id[0] = sub ? r0 : q.x; id[1] = sub ? r1 : q.z; id[2] = sub ? q.y : r0; id[3] = sub ? q.w : r1;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto offsets = [&](const uint32_t (&id)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) off[u] = rem > u * EP ? lbase + __umul24(id[u], RS) : dead;
+      };
+      {
+        uint32_t id[U];
+        u32x4_t q;
+        request(q);
+        take(q, id);
+        offsets(id);
+      }
+      // (the row's own piece is taken HERE: inside the loop the compiler's wait for it would wait for the ids in flight as well)
+      asm volatile("" : "+v"(hi) : : "memory");
+      const f2 hA = {hi.x, hi.y}, hB = {hi.z, hi.w};
+      for (int32_t it = 0; __builtin_amdgcn_ballot_w64(it < niter) != 0; ++it) {
+        f4v_t v[U];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v[u]) : "v"(off[u]), "s"(rt) : "memory");
+        xoff += (uint32_t)(STEP * 4);
+        u32x4_t nq;
+        request(nq);                                   // behind the gathers
+        // the gathers; the ids stay in flight
+        if constexpr (SLOW) asm volatile("s_waitcnt vmcnt(4)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
+        else asm volatile("s_waitcnt vmcnt(1)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        float lA[U], lB[U], cmA = -INFINITY, cmB = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          f2 zA = f2{v[u].x, v[u].y} + hA, zB = f2{v[u].z, v[u].w} + hB;
+          zA = __builtin_elementwise_max(zA, zA * sl);
+          zB = __builtin_elementwise_max(zB, zB * sl);
+          float tA = a4.x * zA.x;                      // the two real terms of a head: product, then ONE fused multiply-add
+          tA = fmaf(a4.y, zA.y, tA);
+          float tB = a4.z * zB.x;
+          tB = fmaf(a4.w, zB.y, tB);
+          lA[u] = rem > u * EP ? tA : -INFINITY;
+          lB[u] = rem > u * EP ? tB : -INFINITY;
+          cmA = fmaxf(cmA, lA[u]);
+          cmB = fmaxf(cmB, lB[u]);
+        }
+        const float mnA = fmaxf(mA, cmA), mnB = fmaxf(mB, cmB);
+        const float scA = (mA == mnA) ? 1.f : __expf(mA - mnA), scB = (mB == mnB) ? 1.f : __expf(mB - mnB);
+        accA *= f2{scA, scA}; accB *= f2{scB, scB};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const float peA = (lA[u] == -INFINITY) ? 0.f : __expf(lA[u] - mnA);
+          const float peB = (lB[u] == -INFINITY) ? 0.f : __expf(lB[u] - mnB);
+          sA = u == 0 ? fmaf(sA, scA, peA) : sA + peA;
+          sB = u == 0 ? fmaf(sB, scB, peB) : sB + peB;
+          accA.x = fmaf(peA, v[u].x, accA.x); accA.y = fmaf(peA, v[u].y, accA.y);
+          accB.x = fmaf(peB, v[u].z, accB.x); accB.y = fmaf(peB, v[u].w, accB.y);
+        }
+        mA = mnA; mB = mnB;
+        rem -= STEP;
+        uint32_t nid[U];
+        take(nq, nid);
+        offsets(nid);
+      }
+    };
+    if (any) {
+      if (slow) walk(std::true_type{});
+      else walk(std::false_type{});
+    }
+    // merge the two edge slots of a (row, head): agg_heads_fast_kernel's, roundings spelled out
+    {
+      const int from = lane ^ 2;
+      const float mA2 = __shfl(mA, from), sA2 = __shfl(sA, from), mB2 = __shfl(mB, from), sB2 = __shfl(sB, from);
+      f2 bA, bB;
+      bA.x = __shfl(accA.x, from); bA.y = __shfl(accA.y, from); bB.x = __shfl(accB.x, from); bB.y = __shfl(accB.y, from);
+      const float mnA = fmaxf(mA, mA2), mnB = fmaxf(mB, mB2);
+      const float cA1 = (mA == mnA) ? 1.f : __expf(mA - mnA), cA2 = (mA2 == mnA) ? 1.f : __expf(mA2 - mnA);
+      const float cB1 = (mB == mnB) ? 1.f : __expf(mB - mnB), cB2 = (mB2 == mnB) ? 1.f : __expf(mB2 - mnB);
+      sA = fmaf(sA, cA1, sA2 * cA2); sB = fmaf(sB, cB1, sB2 * cB2);
+      accA.x = fmaf(accA.x, cA1, bA.x * cA2); accA.y = fmaf(accA.y, cA1, bA.y * cA2);
+      accB.x = fmaf(accB.x, cB1, bB.x * cB2); accB.y = fmaf(accB.y, cB1, bB.y * cB2);
+    }
+    if (rvalid && sub == 0) {
+#pragma clang fp contract(off)   // (as agg_heads_fast_kernel's epilogue: no fused multiply-add of its own)
+      auto finish = [&](float s, f2 acc) {
+        const float inv = 1.f / (s + 1e-16f);
+        float4 r4 = make_float4(acc.x * inv, acc.y * inv, 0.f, 0.f);
+        if (p.ep_relu == 2) {    // log_softmax over the head's D classes (KTGNN.py:435), row-local
+          float mx = r4.x;
+          if (p.D > 1) mx = fmaxf(mx, r4.y);
+          float se = expf(r4.x - mx);
+          if (p.D > 1) se += expf(r4.y - mx);
+          const float lse = logf(se);
+          r4.x = r4.x - mx - lse;
+          r4.y = p.D > 1 ? r4.y - mx - lse : 0.f;
+        }
+        return __builtin_bit_cast(u32x4_t, r4);
+      };
+      const uint32_t o = ((uint32_t)i * 3u + (uint32_t)part * 2u) * 16u;
+      __builtin_amdgcn_raw_buffer_store_b128(finish(sA, accA), ro, o, 0, 0);
+      if (part == 0) __builtin_amdgcn_raw_buffer_store_b128(finish(sB, accB), ro, o + 16u, 0, 0);
+    }
+  }
+}
+
 // Tiles per queue claim.  4 amortises the same-address atomic (~90 ns each); measured on a rank's share of C4
 // (tools/rank_of_8_time.py): 1 -> 0.80 ms, 2 -> 0.69, 4 -> 0.67, 8 -> 0.70 per forward, also for the short launches.
 inline int tq_chunk_for(int64_t ntiles, int64_t grid) {
@@ -1459,14 +1656,18 @@ static bool fast_plan(AggParams& p, int64_t table_rows) {
 // refuses).  BGNN_HEADS_FAST=0 keeps agg_heads_lanes_kernel (tests compare the two bit for bit).  Like agg_wide_fast_kernel's
 // load_id the kernel addresses `col` by 32-bit byte offsets, i.e. fewer than 2^30 edges, which the host cannot check: the edge
 // count lives in device memory (the int32 CSR itself ends at 2^31 - N edges).
-static bool heads_fast_plan(AggParams& p, int64_t table_rows) {
+constexpr bool kHeadsRows32Default = true;       // BGNN_HEADS_ROWS32 unset (measured: profiles/heads_rows32/README.md)
+static bool heads_fast_plan(AggParams& p, int64_t table_rows, bool rows32 = false) {
   static const bool on = [] { const char* e = getenv("BGNN_HEADS_FAST"); return !(e && atoi(e) == 0); }();
   if (!on || table_rows <= 0) return false;
   if ((p.heads != 2 && p.heads != 3) || p.D > 4 || p.ldh != 4 || p.ldo != 4) return false;
   if (p.mode != 0 || p.n_vrows != 0 || p.hub_threshold != 0 || p.alpha != nullptr) return false;
   if (!(p.slope >= 0.f && p.slope <= 1.f)) return false;                       // max(z, slope * z) == leaky_relu(z)
   const int64_t lim24 = (int64_t)1 << 24, lim32 = ((int64_t)1 << 32) - 1;       // v_mul_u32_u24 operands / 32-bit byte offsets
-  const int64_t rs = (int64_t)p.heads * 16;
+  // rows32: agg_heads_rows32_kernel's tables, three heads of D <= 2 in 32 bytes per node (BGNN_HEADS_ROWS32=0: never)
+  static const bool on32 = [] { const char* e = getenv("BGNN_HEADS_ROWS32"); return e ? atoi(e) != 0 : kHeadsRows32Default; }();
+  if (rows32 && (!on32 || p.heads != 3 || p.D > 2)) return false;
+  const int64_t rs = rows32 ? 32 : (int64_t)p.heads * 16;
   if (table_rows > lim24 || p.row_end > table_rows) return false;
   const char* a = reinterpret_cast<const char*>(p.h_t2s);
   const char* b = reinterpret_cast<const char*>(p.h_s2t);
@@ -1696,6 +1897,25 @@ int launch_heads_fast(const AggParams& p, hipStream_t st) {
   return 0;
 }
 
+// agg_heads_rows32_kernel, same grid rule (64 rows per block)
+static int launch_heads_rows32(const AggParams& p, hipStream_t st) {
+  constexpr int RPB = 64;
+  static const int cap = [] {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, agg_heads_rows32_kernel, 256, 0) != hipSuccess || per_cu < 1) return 2048;
+    if (per_cu > 8) per_cu = 8;
+    return per_cu * prop.multiProcessorCount / 8 * 8;
+  }();
+  const int64_t ntiles = (p.row_end - p.row_begin + RPB - 1) / RPB;
+  int64_t grid = ntiles < cap ? (ntiles + 7) / 8 * 8 : cap;
+  if (grid < 8) grid = 8;
+  hipLaunchKernelGGL(agg_heads_rows32_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
+  BGNN_LAUNCH_CHECK();
+  return 0;
+}
+
 static int dispatch_aggregate(const AggParams& p, hipStream_t st, int64_t table_rows = 0) {
   const int32_t D = p.D, heads = p.heads;
   if ((heads == 3 || heads == 2) && D <= 4 && p.ldh == 4 && p.ldo == 4) {                     // KT-GNN's classifier stage
@@ -1804,6 +2024,36 @@ extern "C" int bgnn_adaptedconv_aggregate_bounded_f32(const float* h_t2s, const 
   if (table_rows < row_end || gather_hint < 0 || gather_hint > 2) return BGNN_E_SHAPE;
   return aggregate_impl(h_t2s, h_s2t, ldh, a_t2s, a_s2t, rowptr, col, mask, row_begin, row_end, D, negative_slope, out, ldo, alpha_opt,
                         ep_scale_opt, ep_shift_opt, ep_relu, state_ms_opt, part, park_begin, heads, colsum_opt, tile_queue_opt, 8, table_rows, gather_hint, stream);
+}
+
+// the three-head walk on 32-byte rows: the plan as a question (the caller chooses the tables' layout by it), and the launch
+static int rows32_params(AggParams& p, const float* t_t2s, const float* t_s2t, const float* a_t2s, const float* a_s2t,
+                         const int32_t* rowptr, const int32_t* col, const uint8_t* mask, int64_t row_begin, int64_t row_end,
+                         int32_t D, float negative_slope, float* out, int ep_relu, int64_t table_rows) {
+  if (!t_t2s || !t_s2t) return BGNN_E_NULL;
+  if (row_begin < 0 || row_end < row_begin || table_rows < row_end || D <= 0 || D > 2 || (ep_relu != 0 && ep_relu != 2)) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(t_t2s) || !bgnn_aligned16(t_s2t) || (out && !bgnn_aligned16(out))) return BGNN_E_ALIGN;
+  p = AggParams{t_t2s, t_s2t, 4, a_t2s, a_s2t, rowptr, col, mask, row_begin, row_end, D, negative_slope,
+                out, 4, nullptr, nullptr, nullptr, ep_relu, nullptr, nullptr, 3, nullptr, 0, row_begin, 4};
+  return heads_fast_plan(p, table_rows, true) ? 0 : BGNN_E_SHAPE;
+}
+
+extern "C" int bgnn_adaptedconv_aggregate_heads_rows32_plan(const float* t_t2s, const float* t_s2t, int64_t table_rows,
+                                                            int64_t row_end, int32_t D, float negative_slope) {
+  AggParams p;
+  return rows32_params(p, t_t2s, t_s2t, nullptr, nullptr, nullptr, nullptr, nullptr, 0, row_end, D, negative_slope, nullptr, 0, table_rows) == 0;
+}
+
+extern "C" int bgnn_adaptedconv_aggregate_heads_rows32_f32(const float* t_t2s, const float* t_s2t, const float* a_t2s, const float* a_s2t,
+                                                           const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                                           int64_t row_begin, int64_t row_end, int32_t D, float negative_slope,
+                                                           float* out, int ep_relu, int64_t table_rows, void* stream) {
+  if (!a_t2s || !a_s2t || !rowptr || !col || !mask || !out) return BGNN_E_NULL;
+  AggParams p;
+  const int rc = rows32_params(p, t_t2s, t_s2t, a_t2s, a_s2t, rowptr, col, mask, row_begin, row_end, D, negative_slope, out, ep_relu, table_rows);
+  if (rc) return rc;                                   // (no other kernel reads these tables: a refused plan is the caller's error)
+  if (row_end == row_begin) return 0;
+  return launch_heads_rows32(p, (hipStream_t)stream);
 }
 
 extern "C" int64_t bgnn_aggregate_tile_queue_words(void) { return claim_cfg().tile ? claim_queue_words() : 8; }

@@ -1062,7 +1062,7 @@ __global__ __launch_bounds__(256) void narrow_finish_kernel(const float* __restr
                                                             const uint8_t* __restrict__ mask,
                                                             const float* __restrict__ bias, const float* __restrict__ wd,
                                                             const float* __restrict__ gc, float* __restrict__ out_s2t,
-                                                            float* __restrict__ out_t2s, int64_t row_stride) {
+                                                            float* __restrict__ out_t2s, int64_t row_stride, int rows32) {
   const float4 b0 = *reinterpret_cast<const float4*>(bias), b1 = *reinterpret_cast<const float4*>(bias + 4);
   const float4 w0 = *reinterpret_cast<const float4*>(wd), w1 = *reinterpret_cast<const float4*>(wd + 4);
   const float g0 = gc[0], g1 = gc[1];
@@ -1078,6 +1078,7 @@ __global__ __launch_bounds__(256) void narrow_finish_kernel(const float* __restr
     o0.z = fmaf(c0, w0.z, a.z + b0.z); o0.w = fmaf(c0, w0.w, a.w + b0.w);
     o1.x = fmaf(c1, w1.x, b.x + b1.x); o1.y = fmaf(c1, w1.y, b.y + b1.y);
     o1.z = fmaf(c1, w1.z, b.z + b1.z); o1.w = fmaf(c1, w1.w, b.w + b1.w);
+    if (rows32) o0.z = o0.w = o1.z = o1.w = 0.f;     // the second half of a 32-byte row [h2c0 h2c1 0 0]: the padding is +0, whatever D
     *reinterpret_cast<float4*>(out_s2t + r * row_stride) = o0;
     *reinterpret_cast<float4*>(out_t2s + r * row_stride) = o1;
   }
@@ -1101,13 +1102,13 @@ extern "C" int bgnn_linear_narrow_transform_f32(const float* x, int64_t N, int32
   return launch_wreg<2>(p, (hipStream_t)stream);      // (gridDim.y == 1: NC is one column group)
 }
 
-extern "C" int bgnn_classifier_stage_f32(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
-                                         const double* sums_x, int32_t sk_heads, int32_t sk_D, const float* sk_Wp,
-                                         const float* sk_bias, const float* sk_gates, const float* sk_gate_const_opt,
-                                         float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1, int64_t sk_ldh,
-                                         int64_t sk_row_stride, const float* W, const float* bias, int32_t Dout, int relu,
-                                         double* colsum, const float* Wp2, const float* gates2, float* raw, float* small_ws,
-                                         void* stream) {
+static int classifier_stage_impl(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
+                                 const double* sums_x, int32_t sk_heads, int32_t sk_D, const float* sk_Wp,
+                                 const float* sk_bias, const float* sk_gates, const float* sk_gate_const_opt,
+                                 float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1, int64_t sk_ldh,
+                                 int64_t sk_row_stride, const float* W, const float* bias, int32_t Dout, int relu,
+                                 double* colsum, const float* Wp2, const float* gates2, float* raw, float* small_ws,
+                                 void* stream, int rows32) {
   if (!x || !mask || !sums_x || !sk_Wp || !sk_bias || !sk_gates || !h_s2t_0 || !h_t2s_0 || !W || !bias || !colsum || !Wp2 || !gates2 ||
       !raw || !small_ws) return BGNN_E_NULL;
   if (sk_heads < 1 || sk_heads > MAXH || (sk_heads == 2 && (!h_s2t_1 || !h_t2s_1))) return BGNN_E_NULL;
@@ -1126,7 +1127,7 @@ extern "C" int bgnn_classifier_stage_f32(const float* x, int64_t N, int32_t Din,
   p.w2 = Wp2; p.g2 = gates2; p.raw = raw;
   p.sk_Wp = sk_Wp; p.sk_bias = sk_bias; p.sk_wd = wd; p.sk_g = sk_gates; p.sk_gc = gc;
   p.sk_out[0][0] = h_s2t_0; p.sk_out[0][1] = h_t2s_0; p.sk_out[1][0] = h_s2t_1; p.sk_out[1][1] = h_t2s_1;
-  p.sk_ldh = sk_ldh; p.sk_row_stride = sk_row_stride; p.sk_NC = sk_NC; p.sk_heads = sk_heads;
+  p.sk_ldh = sk_ldh; p.sk_row_stride = sk_row_stride; p.sk_NC = sk_NC; p.sk_heads = sk_heads; p.sk_rows32 = rows32;
   if (!bgnn_tf_cls_supported(p)) return BGNN_E_SHAPE;
   hipLaunchKernelGGL(wd_kernel, dim3((unsigned)((sk_NC + 2 * sk_heads + 3) / 4)), dim3(256), 0, st, sk_Wp, sk_NC, Din, (const float*)nullptr,
                      sums_x, sk_gates, sk_gate_const_opt, sk_heads, wd, gc);
@@ -1134,10 +1135,34 @@ extern "C" int bgnn_classifier_stage_f32(const float* x, int64_t N, int32_t Din,
   return bgnn_tf_cls_launch(p, st, n_cu());
 }
 
-extern "C" int bgnn_narrow_transform_finish_f32(const float* raw, int64_t N, const uint8_t* mask, const double* sums,
-                                                int32_t Din, const float* Wp2, const float* bias2, const float* gates2,
-                                                const float* gate_const_opt, float* h_s2t, float* h_t2s,
-                                                int64_t row_stride, float* small_ws, void* stream) {
+extern "C" int bgnn_classifier_stage_f32(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
+                                         const double* sums_x, int32_t sk_heads, int32_t sk_D, const float* sk_Wp,
+                                         const float* sk_bias, const float* sk_gates, const float* sk_gate_const_opt,
+                                         float* h_s2t_0, float* h_t2s_0, float* h_s2t_1, float* h_t2s_1, int64_t sk_ldh,
+                                         int64_t sk_row_stride, const float* W, const float* bias, int32_t Dout, int relu,
+                                         double* colsum, const float* Wp2, const float* gates2, float* raw, float* small_ws,
+                                         void* stream) {
+  return classifier_stage_impl(x, N, Din, ldx, mask, sums_x, sk_heads, sk_D, sk_Wp, sk_bias, sk_gates, sk_gate_const_opt, h_s2t_0, h_t2s_0,
+                               h_s2t_1, h_t2s_1, sk_ldh, sk_row_stride, W, bias, Dout, relu, colsum, Wp2, gates2, raw, small_ws, stream, 0);
+}
+
+extern "C" int bgnn_classifier_stage_rows32_f32(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
+                                                const double* sums_x, int32_t sk_D, const float* sk_Wp, const float* sk_bias,
+                                                const float* sk_gates, const float* sk_gate_const_opt, float* t_s2t, float* t_t2s,
+                                                int64_t sk_row_stride, const float* W, const float* bias, int32_t Dout, int relu,
+                                                double* colsum, const float* Wp2, const float* gates2, float* raw, float* small_ws,
+                                                void* stream) {
+  if (sk_D > 2) return BGNN_E_SHAPE;
+  if (!bgnn_aligned16(t_s2t) || !bgnn_aligned16(t_t2s)) return BGNN_E_ALIGN;
+  // (both heads' packed operands keep ldh = 4; head 1's table pointers only say "present": the kernel stores through head 0's)
+  return classifier_stage_impl(x, N, Din, ldx, mask, sums_x, 2, sk_D, sk_Wp, sk_bias, sk_gates, sk_gate_const_opt, t_s2t, t_t2s, t_s2t, t_t2s,
+                               4, sk_row_stride, W, bias, Dout, relu, colsum, Wp2, gates2, raw, small_ws, stream, 1);
+}
+
+static int narrow_finish_impl(const float* raw, int64_t N, const uint8_t* mask, const double* sums,
+                              int32_t Din, const float* Wp2, const float* bias2, const float* gates2,
+                              const float* gate_const_opt, float* h_s2t, float* h_t2s,
+                              int64_t row_stride, float* small_ws, void* stream, int rows32) {
   if (!raw || !mask || !sums || !Wp2 || !bias2 || !gates2 || !h_s2t || !h_t2s || !small_ws) return BGNN_E_NULL;
   if (N < 0 || Din <= 0 || (Din & 3) || row_stride < 4 || (row_stride & 3)) return BGNN_E_SHAPE;
   if (!bgnn_aligned16(raw) || !bgnn_aligned16(h_s2t) || !bgnn_aligned16(h_t2s) || !bgnn_aligned16(bias2) ||
@@ -1150,8 +1175,22 @@ extern "C" int bgnn_narrow_transform_finish_f32(const float* raw, int64_t N, con
   BGNN_LAUNCH_CHECK();
   const int64_t nb = (N + 255) / 256;
   hipLaunchKernelGGL(narrow_finish_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, raw, N, mask, bias2, wd, gc,
-                     h_s2t, h_t2s, row_stride);
+                     h_s2t, h_t2s, row_stride, rows32);
   BGNN_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int bgnn_narrow_transform_finish_f32(const float* raw, int64_t N, const uint8_t* mask, const double* sums,
+                                                int32_t Din, const float* Wp2, const float* bias2, const float* gates2,
+                                                const float* gate_const_opt, float* h_s2t, float* h_t2s,
+                                                int64_t row_stride, float* small_ws, void* stream) {
+  return narrow_finish_impl(raw, N, mask, sums, Din, Wp2, bias2, gates2, gate_const_opt, h_s2t, h_t2s, row_stride, small_ws, stream, 0);
+}
+
+extern "C" int bgnn_narrow_transform_finish_rows32_f32(const float* raw, int64_t N, const uint8_t* mask, const double* sums,
+                                                       int32_t Din, const float* Wp2, const float* bias2, const float* gates2,
+                                                       const float* gate_const_opt, float* h_s2t, float* h_t2s,
+                                                       int64_t row_stride, float* small_ws, void* stream) {
+  return narrow_finish_impl(raw, N, mask, sums, Din, Wp2, bias2, gates2, gate_const_opt, h_s2t, h_t2s, row_stride, small_ws, stream, 1);
 }
 

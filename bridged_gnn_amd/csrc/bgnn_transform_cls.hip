@@ -317,7 +317,7 @@ __global__ __launch_bounds__(64 * NW) void cls_stage_kernel(GemmParams p) {
       CLS_MARK(2);                            // skinny chain
       const float ss = s_row * cinvS;
       if (valid) {
-        float cf = 0.f;
+        float cf = 0.f, k0 = 0.f, k1 = 0.f;     // (k: head 0's two columns of a 32-byte row, stored with head 1's)
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           if (optr[q] != nullptr) {
@@ -330,7 +330,9 @@ __global__ __launch_bounds__(64 * NW) void cls_stage_kernel(GemmParams p) {
             float4 o;
             o.x = fmaf(cf, wq.x, fmaf(acc[4 * q], ss, bq.x));     o.y = fmaf(cf, wq.y, fmaf(acc[4 * q + 1], ss, bq.y));
             o.z = fmaf(cf, wq.z, fmaf(acc[4 * q + 2], ss, bq.z)); o.w = fmaf(cf, wq.w, fmaf(acc[4 * q + 3], ss, bq.w));
-            *reinterpret_cast<float4*>(optr[q] + row * p.sk_row_stride) = o;
+            if (!p.sk_rows32) *reinterpret_cast<float4*>(optr[q] + row * p.sk_row_stride) = o;
+            else if (q == 0) { k0 = o.x; k1 = o.y; }
+            else *reinterpret_cast<float4*>(optr[0] + row * p.sk_row_stride) = make_float4(k0, k1, o.x, o.y);
           }
         }
       }

@@ -47,6 +47,9 @@ struct GemmParams {
   // that read x directly -- clf_base / clf_target on h); nullptr: absent
   const float* sk_Wp; const float* sk_bias; const float* sk_wd; const float* sk_g; const float* sk_gc;
   float* sk_out[MAXH][2]; int64_t sk_ldh; int64_t sk_row_stride; int32_t sk_NC; int32_t sk_heads;
+  // 1: two heads of D <= 2, a row's four real columns as ONE 16-byte piece [h0c0 h0c1 h1c0 h1c1] at sk_out[0][table] + row * sk_row_stride
+  // (the first half of the walk's 32-byte rows, bgnn_classifier_stage_rows32_f32); sk_out[1] is not written
+  int32_t sk_rows32;
 };
 
 // tanh through v_exp_f32 + v_rcp_f32 (abs. error < 5e-7; the coefficient scales an O(1) rank-1 term)

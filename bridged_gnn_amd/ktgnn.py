@@ -836,11 +836,17 @@ class KTGNN_no_complement(_PlistHooks, nn.Module):
             return (F.log_softmax(logits_base, dim=1), F.log_softmax(logits_target, dim=1),
                     F.log_softmax(logits_hat, dim=1), None)                                              # :435
         # the six narrow tables interleaved per node ([N, 3*pad4(C)]), clf_base/clf_target(x) from ONE pass over x, and ONE
-        # aggregation launch that walks the CSR for all three heads (in-neighbour ids and 48-B rows read once)
+        # aggregation launch that walks the CSR for all three heads (in-neighbour ids and 48-B rows read once).  At C <= 2 half
+        # of such a row is padding: the tables are then [N, 8], 32-byte rows, where the walk's plan takes them
+        a_t2s, a_s2t = stage.attention()
+        tabs = stage.eval_tables_rows32(x, mask_u8, sums_h, csr, self._arena)
+        if tabs is not None:
+            out3 = ops.adaptedconv_aggregate_heads_rows32(*tabs, a_t2s, a_s2t, csr, mask_u8, stage.C, stage.slope,
+                                                          log_softmax=stage.fused_log_softmax)
+            return (*stage.finish(out3), None)                                                           # :432,:434,:433
         t2s = torch.empty(x.shape[0], 3 * stage.ld, dtype=torch.float32, device=x.device)
         s2t = torch.empty_like(t2s)
         stage.eval_tables(x, mask_u8, sums_h, stage.views(t2s, s2t), self._arena)
-        a_t2s, a_s2t = stage.attention()
         out3 = ops.adaptedconv_aggregate(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, stage.C, stage.slope, heads=3,
                                          log_softmax=stage.fused_log_softmax)
         return (*stage.finish(out3), None)                                                               # :432,:434,:433

@@ -288,17 +288,28 @@ def classifier_stage_supported(x, packed_pair, weight, packed_t):
             and os.environ.get("BGNN_FUSED_CLS", "1") != "0")
 
 
-def classifier_stage(x, mask_u8, sums_x, packed_pair, outs, weight, bias, colsum, packed_t, relu=True):
+def classifier_stage(x, mask_u8, sums_x, packed_pair, outs, weight, bias, colsum, packed_t, relu=True, rows32=None):
     """ONE pass over the hidden activation x for the whole classifier stage's dense work (KTGNN.py:432-434): the narrow
     (h_t2s, h_s2t) tables of the convs in `packed_pair` (clf_base, clf_target on x; `outs` = list of (h_t2s, h_s2t) views) and
     stage A of the fused clf_transformer -> clf_target path (`linear_narrow_transform`: -> raw [N, 12], `colsum` += the
-    per-domain column sums of the activation)."""
+    per-domain column sums of the activation).
+    `rows32` = (t2s, s2t), two [>= N, 8] tables of 32-byte rows, instead of `outs`: both heads' two columns go to the rows' first
+    16 bytes (bgnn.h: bgnn_classifier_stage_rows32_f32)."""
     N, din = x.shape
     Wp, bp, gates, D, ldh, gconst = packed_pair
     H = gates.shape[0]
     Wp2, _, gates2, _, _, _ = packed_t
     raw = torch.empty(N, 12, dtype=torch.float32, device=x.device)
     small = torch.empty(H * (2 * ldh + 2) + 8, dtype=torch.float32, device=x.device)
+    if rows32 is not None:
+        t2s, s2t = rows32
+        assert H == 2 and ldh == 4 and D <= 2 and t2s.shape[0] >= N and s2t.shape[0] >= N and t2s.stride(0) == s2t.stride(0)
+        rc = L.lib().bgnn_classifier_stage_rows32_f32(L.ptr_rows(x), N, din, x.stride(0), L.ptr(mask_u8), L.ptr(sums_x), D, L.ptr(Wp),
+                                                      L.ptr(bp), L.ptr(gates), L.ptr(gconst), L.ptr_rows(s2t), L.ptr_rows(t2s),
+                                                      t2s.stride(0), L.ptr(weight), L.ptr(bias), weight.shape[0], 1 if relu else 0,
+                                                      L.ptr(colsum), L.ptr(Wp2), L.ptr(gates2), L.ptr(raw), L.ptr(small), L.stream())
+        L.check(rc, "bgnn_classifier_stage_rows32_f32")
+        return raw
     row_stride = outs[0][0].stride(0)
     for a, b in outs:
         assert a.shape[0] >= N and b.shape[0] >= N and a.stride(0) == row_stride and b.stride(0) == row_stride
@@ -312,18 +323,20 @@ def classifier_stage(x, mask_u8, sums_x, packed_pair, outs, weight, bias, colsum
     return raw
 
 
-def narrow_transform_finish(raw, mask_u8, sums, packed, out):
+def narrow_transform_finish(raw, mask_u8, sums, packed, out, rows32=False):
     """Stage B: raw [N,12] + the (all-reduced) domain sums of the activation -> the conv's (h_t2s, h_s2t) rows in `out`
-    (two [>=N, 4] views with a common row stride)."""
+    (two [>=N, 4] views with a common row stride).  `rows32`: `out` is the second half of 32-byte rows, columns D.. are +0."""
     Wp, bp, gates, D, ldh, gconst = packed
     h_t2s, h_s2t = out
     N = raw.shape[0]
     assert h_t2s.stride(0) == h_s2t.stride(0) and sums.dtype == torch.float64 and sums.numel() == 2 * Wp.shape[1] + 2
+    assert not rows32 or D <= 2
     small = torch.empty(16, dtype=torch.float32, device=raw.device)
-    rc = L.lib().bgnn_narrow_transform_finish_f32(L.ptr(raw), N, L.ptr(mask_u8), L.ptr(sums), Wp.shape[1], L.ptr(Wp), L.ptr(bp),
-                                                  L.ptr(gates), L.ptr(gconst), L.ptr_rows(h_s2t), L.ptr_rows(h_t2s),
-                                                  h_t2s.stride(0), L.ptr(small), L.stream())
-    L.check(rc, "bgnn_narrow_transform_finish_f32")
+    name = "bgnn_narrow_transform_finish_rows32_f32" if rows32 else "bgnn_narrow_transform_finish_f32"
+    rc = getattr(L.lib(), name)(L.ptr(raw), N, L.ptr(mask_u8), L.ptr(sums), Wp.shape[1], L.ptr(Wp), L.ptr(bp),
+                                L.ptr(gates), L.ptr(gconst), L.ptr_rows(h_s2t), L.ptr_rows(h_t2s),
+                                h_t2s.stride(0), L.ptr(small), L.stream())
+    L.check(rc, name)
     return out
 
 
@@ -726,6 +739,34 @@ def adaptedconv_aggregate(h_t2s, h_s2t, a_t2s, a_s2t, csr, mask_u8, D, negative_
         csr.gather_hint() if (heads == 1 and D > 32 and part == 0) else 0, L.stream())
     L.check(rc, "bgnn_adaptedconv_aggregate_queued_f32")
     return (out, alpha) if want_alpha else out
+
+
+def heads_rows32_plan(t2s, s2t, csr, D, negative_slope, row_end=None):
+    """would `adaptedconv_aggregate_heads_rows32` walk these two [rows, 8] tables (bgnn.h: ..._heads_rows32_plan)?  Asked BEFORE
+    the tables are filled: no other kernel reads 32-byte rows.  A graph with hub rows is walked in segments, on padded rows."""
+    if not (t2s.is_cuda and t2s.dtype == s2t.dtype == torch.float32 and t2s.dim() == s2t.dim() == 2 and t2s.shape[1] == s2t.shape[1] == 8
+            and t2s.stride() == s2t.stride() == (8, 1)):
+        return False
+    if os.environ.get("BGNN_HUB_ROWS", "1") != "0" and csr.hub_tables() is not None:
+        return False
+    rows = min(int(t2s.shape[0]), int(s2t.shape[0]))
+    row_end = csr.num_nodes if row_end is None else int(row_end)
+    return bool(L.lib().bgnn_adaptedconv_aggregate_heads_rows32_plan(L.ptr(t2s), L.ptr(s2t), rows, row_end, int(D), float(negative_slope)))
+
+
+def adaptedconv_aggregate_heads_rows32(t2s, s2t, a_t2s, a_s2t, csr, mask_u8, D, negative_slope=0.1, log_softmax=False,
+                                       row_begin=0, row_end=None, out=None):
+    """`adaptedconv_aggregate(..., heads=3)` for D <= 2 over tables of 32-byte rows [h0c0 h0c1 h1c0 h1c1 | h2c0 h2c1 0 0]
+    -> out [n_dst, 3 * 4], the same bits as the walk over padded rows.  Raises outside `heads_rows32_plan`."""
+    row_end = csr.num_nodes if row_end is None else int(row_end)
+    if out is None:
+        out = torch.empty(csr.num_nodes, 12, dtype=torch.float32, device=t2s.device)
+    assert t2s.stride() == s2t.stride() == (8, 1) and out.stride() == (12, 1) and out.shape[0] >= row_end
+    rc = L.lib().bgnn_adaptedconv_aggregate_heads_rows32_f32(
+        L.ptr(t2s), L.ptr(s2t), L.ptr(a_t2s), L.ptr(a_s2t), L.ptr(csr.rowptr), L.ptr(csr.col), L.ptr(mask_u8), int(row_begin), row_end,
+        int(D), float(negative_slope), L.ptr(out), 2 if log_softmax else 0, min(int(t2s.shape[0]), int(s2t.shape[0])), L.stream())
+    L.check(rc, "bgnn_adaptedconv_aggregate_heads_rows32_f32")
+    return out
 
 
 def _bwd_hub_args(csr, use=True):

@@ -153,6 +153,34 @@ int bgnn_narrow_transform_finish_f32(const float* raw, int64_t N, const uint8_t*
                                      int32_t Din, const float* Wp2, const float* bias2, const float* gates2,
                                      const float* gate_const_opt, float* h_s2t, float* h_t2s, int64_t row_stride,
                                      float* small_ws, void* stream);
+/* The eval classifier stage on 32-BYTE node rows (additive symbols, the revision stays 116).  At D <= 2 classes half of a
+ * [3 heads][4 floats] table row is padding; these entries keep per node and table 8 floats [h0c0 h0c1 h1c0 h1c1 | h2c0 h2c1 0 0]
+ * (D = 1: the c1 columns are 0 too), the same values as the padded rows bit for bit.
+ *   bgnn_classifier_stage_rows32_f32: bgnn_classifier_stage_f32 for its two heads (sk_heads = 2, sk_ldh = 4, sk_D <= 2), each
+ *     row's first 16 bytes as ONE store at t_* + row * sk_row_stride; small_ws: 28 floats.
+ *   bgnn_narrow_transform_finish_rows32_f32: bgnn_narrow_transform_finish_f32 with the padding written as +0 -- called with
+ *     h_* = table + 4 and row_stride = 8 it defines the second 16 bytes of every row.
+ *   bgnn_adaptedconv_aggregate_heads_rows32_f32: the three-head walk (heads = 3, mode 0, no hub rows, no alpha; ep_relu 0 or 2)
+ *     over such tables; `out` keeps [rows][3][4].  Bit-identical to bgnn_adaptedconv_aggregate_queued_f32 on the padded tables.
+ *     Only inside the plan that bgnn_adaptedconv_aggregate_heads_rows32_plan answers with 1 -- D <= 2, 0 <= slope <= 1, at most
+ *     2^24 table rows, both tables inside one window below 4 GB, BGNN_HEADS_FAST and BGNN_HEADS_ROWS32 not 0 -- else BGNN_E_SHAPE:
+ *     no other kernel reads this layout, so a caller asks the plan BEFORE it chooses the tables' layout. */
+int bgnn_classifier_stage_rows32_f32(const float* x, int64_t N, int32_t Din, int64_t ldx, const uint8_t* mask,
+                                     const double* sums_x, int32_t sk_D, const float* sk_Wp, const float* sk_bias,
+                                     const float* sk_gates, const float* sk_gate_const_opt, float* t_s2t, float* t_t2s,
+                                     int64_t sk_row_stride, const float* W, const float* bias, int32_t Dout, int relu,
+                                     double* colsum, const float* Wp2, const float* gates2, float* raw, float* small_ws,
+                                     void* stream);
+int bgnn_narrow_transform_finish_rows32_f32(const float* raw, int64_t N, const uint8_t* mask, const double* sums,
+                                            int32_t Din, const float* Wp2, const float* bias2, const float* gates2,
+                                            const float* gate_const_opt, float* h_s2t, float* h_t2s, int64_t row_stride,
+                                            float* small_ws, void* stream);
+int bgnn_adaptedconv_aggregate_heads_rows32_plan(const float* t_t2s, const float* t_s2t, int64_t table_rows, int64_t row_end,
+                                                 int32_t D, float negative_slope);
+int bgnn_adaptedconv_aggregate_heads_rows32_f32(const float* t_t2s, const float* t_s2t, const float* a_t2s, const float* a_s2t,
+                                                const int32_t* rowptr, const int32_t* col, const uint8_t* mask,
+                                                int64_t row_begin, int64_t row_end, int32_t D, float negative_slope,
+                                                float* out, int ep_relu, int64_t table_rows, void* stream);
 /* bgnn_gram_f32: out[a][b] = sum_i A[i][a] * B[i][b] for tall-skinny A [N,p], B [N,q] (p <= 288, q <= 128, both % 4 == 0).
  *   The training path's weight / gate gradients of the dense transform (KTGNN.py:275-284 under autograd) are
  *   [G_s2t | G_t2s | dgate]^T . x with the node count as the reduction dimension; one streaming pass, deterministic
