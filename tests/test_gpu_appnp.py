@@ -270,6 +270,10 @@ def test_backward_past_the_persistent_cap_with_many_segment_hubs(D):
     from bridged_gnn_amd.appnp import APPNP
     dev = _dev()
     n, g, parts = _case("C")
+    if D >= 31:
+        # bgnn_conv_common.h launch_bwd_rows (the log_softmax rule, conv_bwd_rows_kernel): at most 2048 blocks of 256 // LF rows,
+        # lf_ladder: LF = 8 at D = 31, 32 at D = 128; at D = 2 (LF = 1) the cap is 524 288 rows and graph C stays under it
+        assert n > 2048 * (256 // (8 if D == 31 else 32))
     h, dy, refs = _c_ref(D)
     prop = APPNP(10, 0.1)
     worst = 0.0

@@ -2,7 +2,8 @@
 forward entry against an fp64 torch restatement of PyG 2.0.x's GENConv(aggr='softmax', learn_t=True) formulas (scatter_reduce amax,
 index_add_) on the generator of test_gpu_gcn.py with the shapes of test_gpu_appnp.py, the edges EXACTLY as generated (no self loop
 added or dropped; A: 3000 nodes, no hub; B: 2000 nodes, node 3 with >= 700 in-edges and node 5 with >= 700 out-edges; both with
-duplicates, self loops, rows without in-edges, asymmetric; C: past the persistent grid's cap, forward only), its identities, the
+duplicates, self loops, rows without in-edges, asymmetric; C: past the persistent grid's cap, forward only; A2: 20 000 nodes, no
+hub, past the backward's grid at H = 128), its identities, the
 backward entry against fp64 autograd, the layers under autograd, the model on the office graph and `train_deepergcn_noDTC`.
 Inputs are 2 * randn, so t * v reaches a few hundred at t = 40 and would overflow without the running maximum.
 Bars: those of test_gpu_gcn.py (activations 1e-5, gradients 2e-5 of each tensor's max); grad_t: |dt - dt64| <= 2e-5 * sum |g * w64|
@@ -18,7 +19,7 @@ its row) and 0.003 of the grad_t bar, which leaves 2.4x and more for another sum
 Measured on an MI355X, worst error as a share of its bar (each test prints its own): forward 0.026 (z) / 0.021 (lse) / 0.034 (o) on
 graph A and 0.022 / 0.018 / 0.042 on graph B; identities 0.016 and 0.017; graph C 0.020 at H = 5 and 0.033 at H = 128 (its row of
 30 000 in-edges was 1.4 of the bar in o before the running sums became compensated adds); backward 0.495 (grad_x) / 0.004 (grad_t)
-on graph A, 0.365 / 0.005 on graph B, 0.325 / 0.001 at 3001 rows; layers 0.293 on graph A and 0.099 on graph B; the model 0.050 at
+on graph A, 0.365 / 0.005 on graph B, 0.325 / 0.001 at 3001 rows, 0.025 / 0.000 on graph A2; layers 0.293 on graph A and 0.099 on graph B; the model 0.050 at
 1 layer and 0.067 at 3."""
 import types
 
@@ -38,7 +39,7 @@ FP32_FWD, FP32_GX, FP32_GT = 2.2e-6, 9.7e-6, 2.1e-4
 HS = (1, 2, 3, 4, 5, 31, 32, 33, 64, 100, 128, 129, 200)
 TS = (1.0, 0.05, -0.7, 0.0, 40.0)
 _CACHE = {}
-_EXTRA = {"A1": dict(n=3001, e=30000, seed=24, hub=0)}
+_EXTRA = {"A1": dict(n=3001, e=30000, seed=24, hub=0), "A2": dict(n=20000, e=120000, seed=25, hub=0)}
 
 
 def _case(name):
@@ -255,6 +256,19 @@ def test_backward_at_3001_rows():
     for H, t in ((5, 1.0), (64, 40.0), (200, -0.7)):
         _backward_case("A1", H, t, rng, worst)
     print(f"3001 rows: worst backward error {worst[0]:.3f} (grad_x), {worst[1]:.3f} (grad_t) of the bar")
+
+
+def test_backward_past_the_persistent_cap():
+    """graph A2 (20 000 nodes, no hub): at H = 128 more tiles than the backward's grid has blocks, so blocks walk several tiles and
+    several blocks' partial sums of grad_t are made of more than one tile"""
+    n = _EXTRA["A2"]["n"]
+    # bgnn_gen.hip launch_bwd: RPB = 4 * (64 / (LF * EP)) = 8 rows per tile at H = 128 (lf_ladder: LF = 32, EP = 1); the grid is
+    # bgnn_conv_common.h persistent_grid (at most 8 blocks per CU), and never more than GEN_MAX_BLOCKS = 4096
+    cap = min(8 * torch.cuda.get_device_properties(0).multi_processor_count, 4096)
+    assert -(-n // 8) > cap, f"graph A2 must have more tiles of 8 rows than the {cap} blocks of the backward's grid"
+    worst = [0.0, 0.0]
+    _backward_case("A2", 128, 1.0, np.random.default_rng(66), worst)
+    print(f"graph A2 H=128: worst backward error {worst[0]:.3f} (grad_x), {worst[1]:.3f} (grad_t) of the bar")
 
 
 # ---- the layers under autograd -----------------------------------------------------------------------------------

@@ -186,6 +186,9 @@ def test_randomised_parity_with_the_torch_path(feat, within):
     idx_mat, sim_mat = topk_tables(d_from.x.shape[0], n, k, n_cls, 3 + feat)
     ei = ops.coalesce(ops.topk_edges(idx_mat))                     # sorted by `from`; duplicate candidates of a row collapse
     E = ei.shape[1]
+    # bgnn_edge_filter.hip grid_for: at most MAX_BLOCKS = 4096 blocks; edge_validity_kernel walks 256 // 16 edges per block and trip,
+    # edge_rule1_counts_kernel 256 (its grid is sized for 8 trips), select_pass_kernel is sized the same way
+    assert E > 4096 * (256 // 16)
     e_al = bridge.align_e_sim_to_edges(ei, sim_mat, idx_mat)
     e_quirk = torch.sigmoid(torch.randn(E, generator=torch.Generator().manual_seed(9)) * 2).to(DEV)
     perm = torch.randperm(E, generator=torch.Generator().manual_seed(11)).to(DEV)
@@ -240,6 +243,9 @@ def test_scale_beyond_2_pow_24_edges_and_memory():
     ei = ops.coalesce(ops.topk_edges(idx_mat))
     E = ei.shape[1]
     assert E >= 1 << 24
+    # bgnn_edge_filter.hip grid_for past MAX_BLOCKS = 4096 in every launch: 2048 values per block (select_pass, rule1_counts),
+    # 16 rows per block (row_inv_norms, both domains), 16 edges per block (edge_validity)
+    assert E > 4096 * 256 * 8 and min(ns, nt) > 4096 * (256 // 16)
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     base = torch.cuda.memory_allocated()

@@ -151,6 +151,20 @@ def test_forward_kernel_every_shape_epilogue_and_bias(H, C):
     _forward_shape(G, H, C, seed=10 + H * 131 + C)
 
 
+def test_scores_past_the_grid_cap():
+    """bgnn_gat_scores_f32 launches at most 4096 blocks of 256 (node, head) pairs and walks the rest in a grid-stride loop (DESIGN
+    section 20); the other kernel tests stay at n * H <= 120 000"""
+    from bridged_gnn_amd import ops
+    dev, n, H, C = _dev(), 350_000, 3, 4
+    assert n * H > 4096 * 256
+    T, a_s, a_d, _, _ = _inputs(n, H, C, seed=4242)
+    s_src, s_dst = ops.gat_scores(T.to(dev), a_s.to(dev), a_d.to(dev), H, C)
+    T64 = T[:, :H * C].double().view(n, H, C)
+    assert s_src.shape == s_dst.shape == (n, H)
+    _act_ok(s_src.cpu(), (T64 * a_s.double()).sum(-1), "scores past the cap: s_src")
+    _act_ok(s_dst.cpu(), (T64 * a_d.double()).sum(-1), "scores past the cap: s_dst")
+
+
 def test_wide_requests_raise_shape_errors():
     from bridged_gnn_amd import ops
     from bridged_gnn_amd.gat import GATConv
@@ -235,6 +249,10 @@ def test_backward_kernel_matches_fp64_autograd_and_is_deterministic(H, C):
 def test_hub_row_and_hub_source_forward_and_backward(H, C):
     G = _shared_graph(HUBG)
     assert G.indeg.max() >= 30000 and G.outdeg.max() >= 30000 and (G.indeg == 0).any()
+    if C == 64:
+        # bgnn_conv_common.h launch_rows (attn_bwd_rows_kernel): at most 2048 blocks of 256 // LF (node, head) rows, lf_ladder: LF = 16
+        # at C = 64 -- the backward's row pass takes a second trip here; at C = 2 (LF = 1) the cap is 524 288
+        assert G.n * H > 2048 * (256 // 16)
     _forward_shape(G, H, C, seed=900 + C)
     _backward_case(G, H, C, seed=950 + C, epilogues=("elu",))
 

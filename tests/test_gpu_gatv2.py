@@ -208,6 +208,10 @@ def test_backward_kernel_matches_fp64_autograd_and_is_deterministic(H, C):
 def test_hub_row_and_hub_source_forward_and_backward(H, C):
     G = _shared_graph(HUBG)
     assert G.indeg.max() >= 30000 and G.outdeg.max() >= 30000 and (G.indeg == 0).any()
+    if C == 64:
+        # bgnn_gatv2.hip launch_dst: the persistent grid, never more than DATT_BLOCKS = 2048 blocks, over tiles of 4 * (64 // LF) = 16
+        # rows at C = 64 (lf_ladder: LF = 16, EP = 1); bgnn_conv_common.h launch_rows: 2048 blocks of 256 // LF = 16 (node, head) rows
+        assert -(-G.n // 16) > 2048 and G.n * H > 2048 * 16
     _forward_shape(G, H, C, seed=900 + C)
     _backward_case(G, H, C, seed=950 + C, epilogues=("elu",))
 

@@ -264,6 +264,7 @@ def test_rowdot_beyond_one_pass_exact_on_integers_and_bounded_on_floats(d):
     from bridged_gnn_amd import ops
     g = _gen(7000 + d)
     nmax = 2 * 65536 + 5
+    assert nmax > 2 * 4096 * 16                                              # bgnn_rowdot_f32: grid > 4096 ? 4096 blocks of 16 rows
     bufI = torch.full((nmax, d + 4), float("nan"), device=DEV)
     bufF = torch.full((nmax, d + 4), float("nan"), device=DEV)
     bufI[:, :d] = _ints(g, nmax, d, 16)
@@ -347,6 +348,7 @@ def test_transform_bwd_prep_with_four_rows_in_flight(din, D, n):
     from bridged_gnn_amd import ops
     c = _prep_inputs(din, D, n)
     ex_route = D <= 128
+    assert n > 3 * (2048 if ex_route and c["p"] > 16 else 8192) * 8              # bgnn_gram.hip prep_blocks: blocks of 8 rows, capped
 
     def call(lo, hi):
         return ops.transform_bwd_prep(c["x"][lo:hi], c["G1"][lo:hi], c["G2"][lo:hi], D, c["m8"][lo:hi], c["gx"], c["gconst"], c["wd"],
