@@ -30,6 +30,9 @@ def __getattr__(name):
     if name in ("DeeperGCN", "GENConv", "DeepGCNLayer", "train_deepergcn_noDTC"):   # the DeeperGCN baseline's, likewise
         from . import deepergcn
         return getattr(deepergcn, name)
+    if name in ("GINNet", "GINConv", "train_gin_noDTC"):   # the GIN baseline's, likewise
+        from . import gin
+        return getattr(gin, name)
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)

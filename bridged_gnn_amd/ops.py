@@ -1391,6 +1391,123 @@ def gen_softmax_aggregate_bwd(x, grad_z, save, t_rowptr, t_dst, t, H, grad_x=Non
     return grad_x, grad_t
 
 
+def _gin_need_eps(eps):
+    if eps is None:
+        return
+    if not isinstance(eps, torch.Tensor):
+        raise ValueError("eps must be a float32 tensor of one element on the device, or None (it stays on the device: a Python "
+                         f"number is not taken, got {type(eps).__name__})")
+    L._check_device(eps)
+    if eps.dtype != torch.float32 or eps.numel() != 1 or not eps.is_contiguous():
+        raise ValueError("eps must be a float32 tensor of one element (it stays on the device)")
+
+
+def _gin_need_cfg(what, D, epilogue, p_drop):
+    if D < 1:
+        raise ValueError(f"{what} takes D >= 1, got {D}")
+    if epilogue not in SAGE_EPILOGUES:
+        raise ValueError(f"{what}: epilogue must be None, 'relu' or 'log_softmax', got {epilogue!r}")
+    if not 0.0 <= float(p_drop) < 1.0 or (p_drop > 0 and epilogue != "relu"):
+        raise ValueError(f"{what}: 0 <= p_drop < 1, and dropout only after the 'relu' epilogue")
+    if epilogue == "log_softmax" and D > 128:
+        raise ValueError(f"{what}: the fused log_softmax serves D <= 128, got {D}")
+
+
+def gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, out=None,
+                  row_ids=None):
+    """GIN sum aggregation (models/backbones.py:26-57: PyG GINConv(Linear, train_eps=True) after its transform; bgnn.h:
+    bgnn_gin_aggregate_f32) -> out [n_rows, pad4(D)] (use out[:, :D]):
+    out[i] = epi((1 + eps) * tbl[i] + sum_{t in row i} tbl[col[t]] + bias) over the by-destination CSR exactly as given (`SageGraph`:
+    no self loop added or removed, duplicates are separate messages) or its `transposed()` view.  Row i of tbl is row i's root: no
+    root buffer.  tbl: a 2-D row-strided view with unit column stride and at least n_rows rows (it may be a view of a wider
+    table; ids in col outside it add nothing); eps: a float32 tensor of ONE element on the device (GINConv's eps, never read by the
+    host: changing it in place changes the next call), or None for weight 1 (the bits of a device 0); bias: float32 [>= D] or None.
+    epilogue: None, "relu" (then dropout at p_drop, the (seed, element index) hash of `sage_mean_aggregate`) or "log_softmax"
+    (D <= 128).  row_ids: int64 [n_rows], the GLOBAL row id of every output row (a rank's rows of a partition): the dropout element
+    index is then row_ids[i] * D + column; None = row i itself.  Pad columns of out are written as 0.  No atomics, no host
+    synchronisation."""
+    n_rows, D = int(n_rows), int(D)
+    _gin_need_cfg("gin_aggregate", D, epilogue, p_drop)
+    _gin_need_eps(eps)
+    _need_rows_f32(tbl, "tbl", D)
+    if tbl.shape[0] < n_rows:
+        raise ValueError(f"tbl must have at least n_rows = {n_rows} rows, got {tbl.shape[0]}")
+    _gen_need_csr(rowptr, col, n_rows)
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < D:
+            raise ValueError("bias must be float32 [>= D]")
+        if bias.shape[0] < pad4(D) or bias.data_ptr() % 16 != 0:      # the kernel reads whole float4 slots of an aligned row
+            bp = torch.zeros(pad4(D), dtype=torch.float32, device=bias.device)
+            bp[:D] = bias[:D]
+            bias = bp
+    if row_ids is not None and (row_ids.dtype != torch.int64 or row_ids.dim() != 1 or row_ids.shape[0] != n_rows
+                                or not row_ids.is_contiguous()):
+        raise ValueError("row_ids must be a contiguous int64 [n_rows]")
+    if out is None:
+        out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
+    else:
+        _need_rows_f32(out, "out", D)
+        if out.shape[0] != n_rows or out.data_ptr() == tbl.data_ptr():
+            raise ValueError(f"out must have n_rows = {n_rows} rows and be distinct from tbl")
+    rc = L.lib().bgnn_gin_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(eps), L.ptr(bias), L.ptr(rowptr), L.ptr(col), int(col.shape[0]),
+        n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev), L.ptr(row_ids), L.ptr_rows(out),
+        out.stride(0), L.stream())
+    L.check(rc, "bgnn_gin_aggregate_f32")
+    return out
+
+
+def gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue=None, p_drop=0.0, want_bias=True, want_eps=True,
+                      grad_tbl=None):
+    """Backward of `gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias, epilogue, p_drop)` (models/backbones.py:26-57; bgnn.h:
+    bgnn_gin_aggregate_bwd_f32) -> (grad_tbl [n_src, pad4(D)], grad_bias [D] | None, grad_eps float32 [1] | None).
+    tbl: the forward's table (read only for grad_eps; may be None with want_eps=False); y: the forward's output (unused without an
+    epilogue, may be None); grad_y: [n_rows, >= pad4(D)]; (t_rowptr, t_col): the by-source view of the same edges
+    (`DstCSR.transposed()`).  g (the gradient at the epilogue's input) comes from one row pass, grad_bias = its fixed-order column
+    sums (`column_sums`), grad_eps = sum_i <g_i, tbl_i> from per-block fp64 partials summed in a fixed order, and
+    grad_tbl[j] = (1 + eps) * g[j] + sum_{i : j -> i} g[i] from the forward walk over the swapped view with the same eps tensor.
+    want_eps=False launches no eps pass.  No atomics: bit-identical from run to run; no host synchronisation."""
+    n_src, D = int(n_src), int(D)
+    _gin_need_cfg("gin_aggregate_bwd", D, epilogue, p_drop)
+    _gin_need_eps(eps)
+    _need_rows_f32(grad_y, "grad_y", D)
+    n_rows = int(grad_y.shape[0])
+    if epilogue is not None and epilogue != "none":
+        if y is None:
+            raise ValueError("y (the forward's output) is needed under an epilogue")
+    if y is not None:
+        _need_rows_f32(y, "y", D)
+        if y.shape[0] != n_rows:
+            raise ValueError(f"y must have grad_y's {n_rows} rows")
+    if want_eps:
+        if tbl is None:
+            raise ValueError("tbl (the forward's table) is needed for grad_eps")
+        _need_rows_f32(tbl, "tbl", D)
+        if tbl.shape[0] < n_rows:
+            raise ValueError(f"tbl must have at least grad_y's {n_rows} rows, got {tbl.shape[0]}")
+    _gen_need_csr(t_rowptr, t_col, n_src, "t_rowptr")
+    dev = grad_y.device
+    if grad_tbl is None:
+        grad_tbl = torch.empty(n_src, pad4(D), dtype=torch.float32, device=dev)
+    else:
+        _need_rows_f32(grad_tbl, "grad_tbl", D)
+        if grad_tbl.shape[0] != n_src:
+            raise ValueError(f"grad_tbl must have n_src = {n_src} rows")
+    lib = L.lib()
+    g = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=dev)
+    grad_eps = ws = None
+    if want_eps:
+        grad_eps = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(int(lib.bgnn_gin_aggregate_bwd_workspace_bytes(n_rows, D)), 16), dtype=torch.uint8, device=dev)
+    rc = lib.bgnn_gin_aggregate_bwd_f32(
+        L.ptr_rows(tbl) if want_eps else None, tbl.stride(0) if want_eps else 0, L.ptr_rows(y), y.stride(0) if y is not None else 0,
+        L.ptr_rows(grad_y), grad_y.stride(0), n_rows, L.ptr(t_rowptr), L.ptr(t_col), int(t_col.shape[0]), n_src, D, L.ptr(eps),
+        SAGE_EPILOGUES[epilogue], float(p_drop), L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0),
+        L.ptr(grad_eps), L.ptr(ws), ws.numel() if ws is not None else 0, L.stream())
+    L.check(rc, "bgnn_gin_aggregate_bwd_f32")
+    return grad_tbl, (column_sums(g)[:D] if want_bias else None), grad_eps
+
+
 APPNP_STORES = {"state": 0, "out": 1, "log_softmax": 2}
 
 

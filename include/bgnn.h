@@ -51,7 +51,7 @@ extern "C" {
  * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32, and the GCNII
  * baseline's bgnn_gcn2_conv_f32 with its workspace size and bgnn_gcn2_conv_bwd_f32, and the partitioned GCNII's
  * bgnn_gcn2_conv_rows_f32, and the DeeperGCN baseline's bgnn_gen_softmax_aggregate_f32, bgnn_gen_softmax_aggregate_bwd_f32 and
- * its workspace size. */
+ * its workspace size, and the GIN baseline's bgnn_gin_aggregate_f32, bgnn_gin_aggregate_bwd_f32 and its workspace size. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -744,6 +744,41 @@ int bgnn_gen_softmax_aggregate_bwd_f32(const float* x, int64_t ldx, int64_t n_sr
                                        const float* lse, const float* o, int64_t lds, int64_t n_rows, const int32_t* t_rowptr,
                                        const int32_t* t_dst, int64_t n_edges, int32_t H, const float* t, float* grad_x,
                                        int64_t ldgx, float* grad_t, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GIN sum aggregation (the GINNet baseline, models/backbones.py:26-57: PyG GINConv(Linear(in, out), train_eps=True) after its
+ * transform T = x W^T, with the F.relu / F.dropout between convs and the closing F.log_softmax), one walk over the by-destination
+ * CSR exactly as given (duplicates are separate messages, self loops ordinary edges, none added or removed):
+ *     out_i = epi( (1 + eps) * tbl_i + sum over t in row i of tbl[col[t]] + bias )
+ * tbl: [n_tbl, ldt], n_tbl >= n_rows (row i is its own root: no root buffer); ids in col outside [0, n_tbl) are never dereferenced
+ * and add nothing; rowptr [n_rows+1] is cut to [0, n_edges] (a malformed rowptr gives a wrong sum, never a stray read).
+ * eps: ONE float in DEVICE memory (GINConv's eps, trainable or not; the host never waits for it), or NULL for weight 1 -- the same
+ * bits as a device 0.  bias_opt: [>= pad4(D)] floats, 16-B aligned, or NULL.  epilogue: 0 none, 1 ReLU then dropout at p_drop (the
+ * (seed + *seed_dev_opt, element index) hash of bgnn_sage_mean_aggregate_f32; row_id_opt: int64 [n_rows], the GLOBAL row of each
+ * output row for that hash, or NULL = row i), 2 log_softmax (D <= 128).  out: [n_rows, ldo], distinct from tbl; pad columns
+ * D .. pad4(D)-1 are written as 0 whatever tbl holds there.  Leading dimensions in floats, % 4 == 0 and >= pad4(D) (tbl may be a
+ * view of a wider table), bases 16-B aligned; BGNN_E_SHAPE / BGNN_E_ALIGN otherwise.  One lane group per row (the mapping of
+ * bgnn_sage_mean_aggregate_f32), columns in slices of 128, a hub row walked by one group.  No float atomics, nothing allocated.
+ *
+ * bgnn_gin_aggregate_bwd_f32 (models/backbones.py:26-57, the backward of the same aggregation):
+ *     g_i        = the gradient at the epilogue's input from (y_i, grad_y_i): y > 0 ? grad_y * keep_scale : 0 (ReLU then dropout),
+ *                  grad_y - exp(y) * rowsum(grad_y) (log_softmax), grad_y (none); written to g [n_rows, ldg], pad columns 0
+ *     grad_eps   = sum over i < n_rows of <g_i, tbl_i>        (only with grad_eps_opt; tbl_opt is the forward's table)
+ *     grad_tbl_j = (1 + eps) * g_j + sum over the out-edges j -> i of g_i        (g_j for j < n_rows)
+ * (t_rowptr [n_src+1], t_col): the by-source view of the same edges, ids >= n_rows add nothing.  grad_tbl: [n_src, ldgt], written
+ * once, distinct from g, y and grad_y.  grad_eps_opt: one float in device memory, overwritten, or NULL (no eps pass runs; tbl_opt
+ * and ws_opt may then be NULL).  grad_eps is formed in fp64: one partial per block of a row pass, summed in a fixed order by a
+ * one-block launch -- no float atomics, bit-identical from run to run, nothing carried from one call to the next.  grad_bias is
+ * the caller's: the column sums of g.  ws_opt: bgnn_gin_aggregate_bwd_workspace_bytes(n_rows, D) bytes. */
+int bgnn_gin_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* eps, const float* bias_opt,
+                           const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t D, int epilogue,
+                           float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, const int64_t* row_id_opt, float* out,
+                           int64_t ldo, void* stream);
+size_t bgnn_gin_aggregate_bwd_workspace_bytes(int64_t n_rows, int32_t D);
+int bgnn_gin_aggregate_bwd_f32(const float* tbl_opt, int64_t ldt, const float* y, int64_t ldy, const float* grad_y, int64_t ldgy,
+                               int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_edges, int64_t n_src,
+                               int32_t D, const float* eps, int epilogue, float p_drop, float* g, int64_t ldg, float* grad_tbl,
+                               int64_t ldgt, float* grad_eps_opt, void* ws_opt, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
