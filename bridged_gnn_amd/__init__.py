@@ -33,6 +33,9 @@ def __getattr__(name):
     if name in ("GINNet", "GINConv", "train_gin_noDTC"):   # the GIN baseline's, likewise
         from . import gin
         return getattr(gin, name)
+    if name in ("JKNet", "JKGraph", "JumpingKnowledge", "train_jknet_noDTC"):   # the JKNet baseline's, likewise
+        from . import jknet
+        return getattr(jknet, name)
     if name in ("PartitionedGCN", "GcnPartition"):     # the same model on a node partition across GPUs
         from . import dist_gcn
         return getattr(dist_gcn, name)

@@ -134,6 +134,13 @@ SIGNATURES = {
     "bgnn_gin_aggregate_bwd_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_gin_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _I32, _P, _INT, _F32, _P, _I64,
                                            _P, _I64, _P, _P, _SZ, _P]),
+    "bgnn_jk_gcn_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P, _P, _I64,
+                                          _P]),
+    "bgnn_jk_gcn_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _I32, _INT, _F32, _P, _I64, _P,
+                                              _I64, _P]),
+    "bgnn_jk_head_supported": (_INT, [_I32, _I32, _I32, _INT]),
+    "bgnn_jk_head_f32": (_INT, [_P, _I64, _I64, _I32, _I32, _INT, _P, _I64, _P, _I32, _INT, _P, _I64, _P, _P, _I64, _P]),
+    "bgnn_jk_max_route_f32": (_INT, [_P, _I64, _P, _I64, _I32, _I32, _P, _I64, _P]),
     "bgnn_gat_scores_f32": (_INT, [_P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgnn_gat_aggregate_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
     "bgnn_gat_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _F32, _F32, C.c_uint64, _P,
@@ -178,7 +185,7 @@ def source_hash():
 
 # keep in step with HASHED in csrc/Makefile
 _HASHED_SOURCES = ("bgnn_api.hip", "bgnn_csr.hip", "bgnn_transform.hip", "bgnn_transform_stream.hip", "bgnn_transform_cls.hip", "bgnn_aggregate.hip", "bgnn_aggregate_bwd.hip",
-                   "bgnn_aggregate_bwd_fast.hip", "bgnn_aggregate_bwd_wide.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_gcn.hip", "bgnn_appnp.hip", "bgnn_gcn2.hip", "bgnn_gen.hip", "bgnn_gat.hip", "bgnn_gatv2.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_pair_mlp.hip", "bgnn_pair_cos.hip", "bgnn_step2.hip", "bgnn_optim.hip", "bgnn_edge_filter.hip", "bgnn_gin.hip", "bgnn_common.h", "bgnn_conv_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
+                   "bgnn_aggregate_bwd_fast.hip", "bgnn_aggregate_bwd_wide.hip", "bgnn_knn.hip", "bgnn_gram.hip", "bgnn_norm.hip", "bgnn_sage.hip", "bgnn_gcn.hip", "bgnn_appnp.hip", "bgnn_gcn2.hip", "bgnn_gen.hip", "bgnn_gat.hip", "bgnn_gatv2.hip", "bgnn_aggregate_heads_wide.hip", "bgnn_pair_mlp.hip", "bgnn_pair_cos.hip", "bgnn_step2.hip", "bgnn_optim.hip", "bgnn_edge_filter.hip", "bgnn_gin.hip", "bgnn_jk.hip", "bgnn_common.h", "bgnn_conv_common.h", "bgnn_transform_params.h", "bgnn_aggregate_bwd_params.h", os.path.join("..", "..", "include", "bgnn.h"))
 
 
 def _sidecar_hash():

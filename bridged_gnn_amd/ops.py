@@ -1508,6 +1508,228 @@ def gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue=N
     return grad_tbl, (column_sums(g)[:D] if want_bias else None), grad_eps
 
 
+JK_MODES = {"cat": 0, "max": 1}
+
+
+def _jk_need_cfg(what, D, epilogue, p_drop):
+    if D < 1:
+        raise ValueError(f"{what} takes D >= 1, got {D}")
+    if epilogue not in (None, "none", "relu"):
+        raise ValueError(f"{what}: epilogue must be None or 'relu', got {epilogue!r}")
+    if not 0.0 <= float(p_drop) < 1.0 or (p_drop > 0 and epilogue != "relu"):
+        raise ValueError(f"{what}: 0 <= p_drop < 1, and dropout only after the 'relu' epilogue")
+
+
+def _jk_need_scales(s, w, n, what):
+    for t, name in ((s, "s"), (w, "w")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] < n or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous float32 [>= {n}]")
+        L._check_device(t)
+
+
+def jk_gcn_aggregate(tbl, rowptr, col, s, w, n_rows, D, bias=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, out=None):
+    """JKNet's scaled-sum conv (models/backbones.py:60-107: PyG GCNConv handed the already normalised adj_t_cache, after its
+    transform; bgnn.h: bgnn_jk_gcn_aggregate_f32) -> out [n_rows, pad4(D)] (use out[:, :D]):
+    out[i] = epi(w[i] * tbl[i] + s[i] * sum_{t in row i} s[col[t]] * tbl[col[t]] + bias) over a by-destination CSR WITHOUT self
+    loops (`JKGraph`; duplicates are separate messages) or its by-source view.  Row i of tbl is row i's root.  tbl: a 2-D row-strided
+    view with unit column stride and at least n_rows rows; s, w: float32 [>= tbl rows]; bias: float32 [>= D] or None.  epilogue: None
+    or "relu" (then dropout at p_drop, element index row * D + column under the hash of `gcn_aggregate`).  out: None, or a
+    row-strided view that MAY BE A COLUMN SLICE OF A WIDER BUFFER (a layer's slice of the layer buffer): only its pad4(D) columns
+    are written, the pad columns as 0.  No atomics, no host synchronisation."""
+    n_rows, D = int(n_rows), int(D)
+    _jk_need_cfg("jk_gcn_aggregate", D, epilogue, p_drop)
+    _need_rows_f32(tbl, "tbl", D)
+    if tbl.shape[0] < n_rows:
+        raise ValueError(f"tbl must have at least n_rows = {n_rows} rows, got {tbl.shape[0]}")
+    _jk_need_scales(s, w, int(tbl.shape[0]), "jk_gcn_aggregate")
+    _gen_need_csr(rowptr, col, n_rows)
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] < D:
+            raise ValueError("bias must be float32 [>= D]")
+        if bias.shape[0] < pad4(D) or bias.data_ptr() % 16 != 0:      # the kernel reads whole float4 slots of an aligned row
+            bp = torch.zeros(pad4(D), dtype=torch.float32, device=bias.device)
+            bp[:D] = bias[:D]
+            bias = bp
+    if out is None:
+        out = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=tbl.device)
+    else:
+        _need_rows_f32(out, "out", D)
+        if out.shape[0] != n_rows or out.data_ptr() == tbl.data_ptr():
+            raise ValueError(f"out must have n_rows = {n_rows} rows and be distinct from tbl")
+    rc = L.lib().bgnn_jk_gcn_aggregate_f32(
+        L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(s), L.ptr(w), L.ptr(bias), L.ptr(rowptr), L.ptr(col),
+        int(col.shape[0]), n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev), L.ptr_rows(out),
+        out.stride(0), L.stream())
+    L.check(rc, "bgnn_jk_gcn_aggregate_f32")
+    return out
+
+
+def jk_gcn_aggregate_bwd(y, grad_y, t_rowptr, t_col, s, w, n_src, D, epilogue=None, p_drop=0.0, want_bias=True, grad_tbl=None):
+    """Backward of `jk_gcn_aggregate` (models/backbones.py:60-107; bgnn.h: bgnn_jk_gcn_aggregate_bwd_f32) ->
+    (grad_tbl [n_src, pad4(D)], grad_bias [D] | None).  y: the forward's output (a slice of the layer buffer is fine; unused
+    without an epilogue, may be None); grad_y: [n_rows, >= pad4(D)], n_rows == n_src; (t_rowptr, t_col): the by-source view of the
+    same edges.  g comes from one row pass, grad_bias = its fixed-order column sums (`column_sums`), and
+    grad_tbl[j] = w[j] * g[j] + s[j] * sum_{i : j -> i} s[i] * g[i] from the forward walk over the swapped view.  No atomics:
+    bit-identical from run to run; no host synchronisation."""
+    n_src, D = int(n_src), int(D)
+    _jk_need_cfg("jk_gcn_aggregate_bwd", D, epilogue, p_drop)
+    _need_rows_f32(grad_y, "grad_y", D)
+    n_rows = int(grad_y.shape[0])
+    if n_rows != n_src:
+        raise ValueError(f"grad_y must have n_src = {n_src} rows (one node set), got {n_rows}")
+    if epilogue is not None and epilogue != "none" and y is None:
+        raise ValueError("y (the forward's output) is needed under an epilogue")
+    if y is not None:
+        _need_rows_f32(y, "y", D)
+        if y.shape[0] != n_rows:
+            raise ValueError(f"y must have grad_y's {n_rows} rows")
+    _jk_need_scales(s, w, n_src, "jk_gcn_aggregate_bwd")
+    _gen_need_csr(t_rowptr, t_col, n_src, "t_rowptr")
+    dev = grad_y.device
+    if grad_tbl is None:
+        grad_tbl = torch.empty(n_src, pad4(D), dtype=torch.float32, device=dev)
+    else:
+        _need_rows_f32(grad_tbl, "grad_tbl", D)
+        if grad_tbl.shape[0] != n_src:
+            raise ValueError(f"grad_tbl must have n_src = {n_src} rows")
+    g = torch.empty(n_rows, pad4(D), dtype=torch.float32, device=dev)
+    rc = L.lib().bgnn_jk_gcn_aggregate_bwd_f32(
+        L.ptr_rows(y), y.stride(0) if y is not None else 0, L.ptr_rows(grad_y), grad_y.stride(0), n_rows, L.ptr(t_rowptr),
+        L.ptr(t_col), int(t_col.shape[0]), n_src, L.ptr(s), L.ptr(w), D, SAGE_EPILOGUES[epilogue], float(p_drop), L.ptr_rows(g),
+        g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0), L.stream())
+    L.check(rc, "bgnn_jk_gcn_aggregate_bwd_f32")
+    return grad_tbl, (column_sums(g)[:D] if want_bias else None)
+
+
+JK_HEAD_LDS_BYTES = 65536
+JK_MAX_LAYERS = 8
+
+
+def jk_head_supported(L_, H, C, mode):
+    """envelope of `jk_head` (bgnn.h: bgnn_jk_head_supported, restated on the host so that no library is needed to ask): mode 'cat' or
+    'max', 1 <= L <= 8, 1 <= C <= 32, and W -- 16 (C <= 16) or 32 rows of K floats, K = L * pad4(H) (cat) or pad4(H) (max) rounded
+    up to 16 -- fits 64 KB of LDS."""
+    L_, H, C = int(L_), int(H), int(C)
+    if mode not in JK_MODES or not 1 <= L_ <= JK_MAX_LAYERS or H < 1 or not 1 <= C <= 32:
+        return False
+    K = L_ * pad4(H) if mode == "cat" else pad4(H)
+    return (16 if C <= 16 else 32) * ((K + 15) // 16 * 16) * 4 <= JK_HEAD_LDS_BYTES
+
+
+def jk_pack_weight(weight, L_, H, mode):
+    """the head's weight [C, L*H] (cat) or [C, H] (max) in the layer buffer's padded column layout: [C, L*pad4(H)] | [C, pad4(H)],
+    pad columns 0"""
+    C, Hp = weight.shape[0], pad4(H)
+    nl = L_ if mode == "cat" else 1
+    if weight.shape[1] != nl * H:
+        raise ValueError(f"weight must be [C, {nl * H}] in mode {mode!r}, got {tuple(weight.shape)}")
+    if Hp == H:
+        return weight.detach().float().contiguous()
+    wp = torch.zeros(C, nl, Hp, dtype=torch.float32, device=weight.device)
+    wp[:, :, :H] = weight.detach().float().reshape(C, nl, H)
+    return wp.reshape(C, nl * Hp)
+
+
+def _jk_need_x(x, L_, H):
+    Hp = pad4(H)
+    if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] < L_ * Hp or x.stride(1) != 1
+            or x.stride(0) % 4 != 0):
+        raise ValueError(f"x must be a float32 [N, >= L * pad4(H) = {L_ * Hp}] row-strided view (row stride % 4 == 0)")
+    L._check_device(x)
+    if x.data_ptr() % 16 != 0:
+        raise ValueError("x must be 16-byte aligned")
+
+
+def jk_head(x, L_, H, mode, weight_packed, bias, C, log_softmax=True, want_state=False, out=None):
+    """JKNet's head in one pass (models/backbones.py:60-107: JumpingKnowledge(cat | max), Linear, log_softmax; bgnn.h:
+    bgnn_jk_head_f32) -> out [N, pad4(C)] (use out[:, :C]), or (out, winners uint8 [N, pad4(H)], jumped [N, pad4(H)]) with
+    want_state (max mode: what `jk_head_bwd` needs; cat mode returns (out, None, None)).  x: the layer buffer [N, L * pad4(H)], layer l
+    in columns [l * pad4(H), l * pad4(H) + H), pad columns 0; weight_packed: `jk_pack_weight(weight, L, H, mode)`; bias: float32 [C]
+    or None.  Raises ValueError outside `jk_head_supported(L, H, C, mode)`."""
+    L_, H, C = int(L_), int(H), int(C)
+    if mode not in JK_MODES:
+        raise ValueError(f"jk_head: mode must be 'cat' or 'max', got {mode!r}")
+    if H < 1 or C < 1 or L_ < 1:
+        raise ValueError(f"jk_head takes L, H, C >= 1, got {(L_, H, C)}")
+    if not jk_head_supported(L_, H, C, mode):
+        raise ValueError(f"jk_head: (L, H, C, mode) = {(L_, H, C, mode)} is outside the kernel's envelope (jk_head_supported)")
+    _jk_need_x(x, L_, H)
+    Hp, Cp = pad4(H), pad4(C)
+    K = L_ * Hp if mode == "cat" else Hp
+    wp = weight_packed
+    if (not isinstance(wp, torch.Tensor) or wp.dtype != torch.float32 or wp.dim() != 2 or tuple(wp.shape) != (C, K)
+            or not wp.is_contiguous()):
+        raise ValueError(f"weight_packed must be a contiguous float32 [{C}, {K}] (jk_pack_weight)")
+    if wp.data_ptr() % 16 != 0:
+        wp = wp.clone()
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] != C or not bias.is_contiguous()):
+        raise ValueError(f"bias must be a contiguous float32 [{C}]")
+    N = int(x.shape[0])
+    if out is None:
+        out = torch.empty(N, Cp, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != N or out.shape[1] < Cp or out.stride(1) != 1:
+        raise ValueError(f"out must be float32 [N, >= {Cp}] with unit column stride")
+    win = jump = None
+    if want_state and mode == "max":
+        win = torch.empty(N, Hp, dtype=torch.uint8, device=x.device)
+        jump = torch.empty(N, Hp, dtype=torch.float32, device=x.device)
+    rc = L.lib().bgnn_jk_head_f32(L.ptr_rows(x), x.stride(0), N, L_, H, JK_MODES[mode], L.ptr(wp), K, L.ptr(bias), C,
+                                  1 if log_softmax else 0, L.ptr_rows(out), out.stride(0), L.ptr(win), L.ptr(jump), Hp, L.stream())
+    L.check(rc, "bgnn_jk_head_f32")
+    return (out, win, jump) if want_state else out
+
+
+def jk_head_bwd(x, L_, H, mode, weight_packed, C, logp, grad_out, log_softmax=True, win=None, jump=None, want_x=True):
+    """Backward of `jk_head` (models/backbones.py:60-107) -> (grad_x [N, L * pad4(H)] | None, grad_weight_packed [C, K], grad_bias
+    [C]).  dlogits from (logp, grad_out) in a row pass (`appnp_log_softmax_bwd`; grad_out itself without the log_softmax), grad_bias
+    = `column_sums`, grad_weight = dlogits^T J by `gram` where supported (J: x itself in cat mode, the forward's jumped rows in max
+    mode), dJ = dlogits W by `linear` or mm; cat: dJ's column blocks are the layer gradients; max: one streaming pass
+    (bgnn.h: bgnn_jk_max_route_f32) writes every layer's slice from dJ and the forward's uint8 winners.  grad_weight is in the
+    padded layout of `jk_pack_weight`."""
+    L_, H, C = int(L_), int(H), int(C)
+    if mode not in JK_MODES:
+        raise ValueError(f"jk_head_bwd: mode must be 'cat' or 'max', got {mode!r}")
+    _jk_need_x(x, L_, H)
+    Hp, Cp = pad4(H), pad4(C)
+    N = int(x.shape[0])
+    K = L_ * Hp if mode == "cat" else Hp
+    if mode == "max":
+        if (win is None or jump is None or win.dtype != torch.uint8 or tuple(win.shape) != (N, Hp) or not win.is_contiguous()
+                or jump.dtype != torch.float32 or tuple(jump.shape) != (N, Hp) or not jump.is_contiguous()):
+            raise ValueError(f"max mode needs the forward's state: win uint8 [{N}, {Hp}] and jump float32 [{N}, {Hp}]")
+    _need_rows_f32(grad_out, "grad_out", C)
+    if grad_out.shape[0] != N:
+        raise ValueError(f"grad_out must have {N} rows")
+    if log_softmax:
+        _need_rows_f32(logp, "logp", C)
+        dz = appnp_log_softmax_bwd(logp, grad_out, C)
+    else:
+        dz = torch.zeros(N, Cp, dtype=torch.float32, device=x.device)
+        dz[:, :C] = grad_out[:, :C]
+    gb = column_sums(dz)[:C]
+    J = x[:, :K] if mode == "cat" else jump
+    if gram_supported(K, Cp) and J.stride(0) % 4 == 0 and J.data_ptr() % 16 == 0:
+        gw = gram(J, dz).t()[:C].contiguous()                   # the kernel's wide operand comes first: (J^T dz)^T
+    else:
+        gw = dz.t().mm(J)[:C]
+    gx = None
+    if want_x:
+        wpad = torch.zeros(Cp, K, dtype=torch.float32, device=x.device)
+        wpad[:C] = weight_packed
+        if linear_supported(Cp, K):
+            dj = linear(dz, wpad.t().contiguous(), torch.zeros(K, dtype=torch.float32, device=x.device))
+        else:
+            dj = dz.mm(wpad)
+        if mode == "cat":
+            gx = dj
+        else:
+            gx = torch.empty(N, L_ * Hp, dtype=torch.float32, device=x.device)
+            rc = L.lib().bgnn_jk_max_route_f32(L.ptr_rows(dj), dj.stride(0), L.ptr(win), N, L_, H, L.ptr_rows(gx), gx.stride(0),
+                                               L.stream())
+            L.check(rc, "bgnn_jk_max_route_f32")
+    return gx, gw, gb
+
+
 APPNP_STORES = {"state": 0, "out": 1, "log_softmax": 2}
 
 

@@ -51,7 +51,9 @@ extern "C" {
  * partitioned APPNP's bgnn_appnp_step_f32 and bgnn_feature_dropout_rows_f32 / bgnn_feature_dropout_rows_bwd_f32, and the GCNII
  * baseline's bgnn_gcn2_conv_f32 with its workspace size and bgnn_gcn2_conv_bwd_f32, and the partitioned GCNII's
  * bgnn_gcn2_conv_rows_f32, and the DeeperGCN baseline's bgnn_gen_softmax_aggregate_f32, bgnn_gen_softmax_aggregate_bwd_f32 and
- * its workspace size, and the GIN baseline's bgnn_gin_aggregate_f32, bgnn_gin_aggregate_bwd_f32 and its workspace size. */
+ * its workspace size, and the GIN baseline's bgnn_gin_aggregate_f32, bgnn_gin_aggregate_bwd_f32 and its workspace size, and the
+ * JKNet baseline's bgnn_jk_gcn_aggregate_f32, bgnn_jk_gcn_aggregate_bwd_f32, bgnn_jk_head_supported, bgnn_jk_head_f32 and
+ * bgnn_jk_max_route_f32. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -779,6 +781,53 @@ int bgnn_gin_aggregate_bwd_f32(const float* tbl_opt, int64_t ldt, const float* y
                                int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_edges, int64_t n_src,
                                int32_t D, const float* eps, int epilogue, float p_drop, float* g, int64_t ldg, float* grad_tbl,
                                int64_t ldgt, float* grad_eps_opt, void* ws_opt, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * JKNet scaled-sum conv (the JKNet baseline, models/backbones.py:60-107: PyG GCNConv handed the already normalised adj_t_cache,
+ * which GCNConv.forward normalises a second time, after its transform T = x W^T, with the F.relu / F.dropout after every conv), one
+ * walk over the by-destination CSR WITHOUT self loops (loops dropped, none appended, duplicates are separate messages):
+ *     out_i = epi( w_i * tbl_i + s_i * sum over t in row i of s[col[t]] * tbl[col[t]] + bias )
+ * s, w: [n_tbl] floats each (twice-normalised operator: s_i = dinv_i * d2_i^-1/2, w_i = 1 / d2_i; textbook GCN: s = dinv, w = dinv^2).
+ * tbl: [n_tbl, ldt], n_tbl >= n_rows (row i is its own root: no root buffer); ids in col outside [0, n_tbl) are never dereferenced
+ * (neither in s nor in tbl) and add nothing; rowptr [n_rows+1] is cut to [0, n_edges].  bias_opt: [>= pad4(D)] floats, 16-B aligned,
+ * or NULL.  epilogue: 0 none, 1 ReLU then dropout at p_drop, element index row * D + column under the (seed + *seed_dev_opt) hash
+ * of bgnn_gcn_aggregate_f32 (with w = s^2 and the same seed the zero pattern is that entry's); 2 is refused (BGNN_E_SHAPE).  out:
+ * [n_rows, ldo], distinct from tbl, MAY BE A COLUMN SLICE OF A WIDER BUFFER (ldo the buffer's row length): only columns
+ * 0 .. pad4(D)-1 of the slice are written, the pad columns as 0.  Leading dimensions in floats, % 4 == 0 and >= pad4(D), bases 16-B
+ * aligned.  One lane group per row, columns in slices of 128, a hub row walked by one group with compensated batch adds.  No float
+ * atomics, nothing allocated.
+ *
+ * bgnn_jk_gcn_aggregate_bwd_f32 (models/backbones.py:60-107, the backward of the same conv):
+ *     g_i        = y > 0 ? grad_y * keep_scale : 0 (ReLU then dropout) | grad_y (none); written to g [n_rows, ldg], pad columns 0
+ *     grad_tbl_j = w_j * g_j + s_j * sum over the out-edges j -> i of s_i * g_i
+ * (t_rowptr [n_src+1], t_col): the by-source view of the same edges; n_src == n_rows (one node set).  grad_tbl: [n_src, ldgt],
+ * written once, distinct from g, y and grad_y.  grad_bias is the caller's: the column sums of g.  Bit-identical from run to run.
+ *
+ * bgnn_jk_head_f32 (models/backbones.py:60-107: JumpingKnowledge(cat | max), Linear, log_softmax in one pass):
+ * x: the layer buffer [n_rows, ldx], layer l in columns [l*Hp, l*Hp + H), Hp = pad4(H), pad columns 0.  mode 0 (cat): the jumped
+ * row is the L slices (K = L*Hp); mode 1 (max): their elementwise maximum, the lowest l on ties (K = Hp).  W: [C, ldw >= K] in the
+ * SAME padded column layout (pad columns 0), 16-B aligned, ldw % 4 == 0; bias_opt: [C] or NULL.  out [n_rows, ldo >= pad4(C)] =
+ * jumped @ W^T + bias, then log_softmax over the C classes when log_softmax != 0; pad columns are written as 0.  The product is the
+ * f32-input MFMA (exact fp32 products, four split-K partial sums per class).  Max mode only: win_opt uint8 [n_rows, Hp] (4-B
+ * aligned) receives the winning layer per element and jump_opt [n_rows, ldj >= Hp] the jumped row (both or neither may be NULL).
+ * Envelope: bgnn_jk_head_supported(L, H, C, mode) != 0 <=> 1 <= L <= 8, 1 <= C <= 32 and W fits 64 KB of LDS (16 or 32 rows of
+ * K rounded up to 16 floats); BGNN_E_SHAPE outside it.
+ *
+ * bgnn_jk_max_route_f32 (models/backbones.py:60-107, the backward of the max jump): grad_x[i, l*Hp + c] = win[i, c] == l ?
+ * grad_jump[i, c] : 0 for every l < L and c < Hp; grad_x [n_rows, ldx >= L*Hp] is written whole. */
+int bgnn_jk_gcn_aggregate_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* s, const float* w, const float* bias_opt,
+                              const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t D, int epilogue,
+                              float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, float* out, int64_t ldo, void* stream);
+int bgnn_jk_gcn_aggregate_bwd_f32(const float* y, int64_t ldy, const float* grad_y, int64_t ldgy, int64_t n_rows,
+                                  const int32_t* t_rowptr, const int32_t* t_col, int64_t n_edges, int64_t n_src, const float* s,
+                                  const float* w, int32_t D, int epilogue, float p_drop, float* g, int64_t ldg, float* grad_tbl,
+                                  int64_t ldgt, void* stream);
+int bgnn_jk_head_supported(int32_t L, int32_t H, int32_t C, int mode);
+int bgnn_jk_head_f32(const float* x, int64_t ldx, int64_t n_rows, int32_t L, int32_t H, int mode, const float* W, int64_t ldw,
+                     const float* bias_opt, int32_t C, int log_softmax, float* out, int64_t ldo, uint8_t* win_opt, float* jump_opt,
+                     int64_t ldj, void* stream);
+int bgnn_jk_max_route_f32(const float* grad_jump, int64_t ldj, const uint8_t* win, int64_t n_rows, int32_t L, int32_t H,
+                          float* grad_x, int64_t ldx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAT attention aggregation (the `gnn='GAT'` baseline of main_graph_knowledge_transfer.py:327-328):
