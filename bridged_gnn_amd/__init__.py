@@ -51,4 +51,7 @@ def __getattr__(name):
     if name == "PartitionedGCN2":                      # the GCNII baseline on the GCN partition
         from . import dist_gcn2
         return dist_gcn2.PartitionedGCN2
+    if name == "PartitionedGIN":                       # the GIN baseline on the GraphSAGE partition (edges as given)
+        from . import dist_gin
+        return dist_gin.PartitionedGIN
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -134,6 +134,11 @@ SIGNATURES = {
     "bgnn_gin_aggregate_bwd_workspace_bytes": (_SZ, [_I64, _I32]),
     "bgnn_gin_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _I32, _P, _INT, _F32, _P, _I64,
                                            _P, _I64, _P, _P, _SZ, _P]),
+    "bgnn_gin_aggregate_hub_workspace_bytes": (_SZ, [_I64, _I32]),
+    "bgnn_gin_aggregate_hub_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P,
+                                           _I32, _P, _I64, _P, _P, _I64, _P, _SZ, _P, _P, _I64, _P]),
+    "bgnn_gin_aggregate_bwd_hub_f32": (_INT, [_P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _I32, _P, _INT, _F32,
+                                               _I32, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _SZ, _P]),
     "bgnn_jk_gcn_aggregate_f32": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I32, _INT, _F32, C.c_uint64, _P, _P, _I64,
                                           _P]),
     "bgnn_jk_gcn_aggregate_bwd_f32": (_INT, [_P, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _I32, _INT, _F32, _P, _I64, _P,

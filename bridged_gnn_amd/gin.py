@@ -23,11 +23,20 @@ from .sage import SageGraph
 __all__ = ["GINConv", "GINNet", "train_gin_noDTC"]
 
 
-def _layer_forward(x, wp, bp, eps, D, graph, epilogue, p_drop, seed, seed_dev=None):
+def graph_hubs(graph, threshold=None, segment=None):
+    """the `hubs` argument of `GINConv.run` for a SageGraph: (hub tables of the by-destination view | None, of the by-source view |
+    None), each (threshold, hub_rows, hub_seg_ptr, seg_bounds); built once per graph and (threshold, segment)"""
+    thr = ops.GIN_HUB_THRESHOLD if threshold is None else int(threshold)
+    seg = ops.GIN_HUB_SEGMENT if segment is None else int(segment)
+    pick = lambda t: None if t is None else (thr, t[0], t[1], t[2])
+    return pick(graph.csr.hub_tables(thr, seg)), pick(graph.csr.transposed_hub_tables(thr, seg))
+
+
+def _layer_forward(x, wp, bp, eps, D, graph, epilogue, p_drop, seed, seed_dev=None, hubs=None):
     T = _transform(x, wp)
     rowptr, col = graph.by_dst[0], graph.by_dst[1]
-    return T, ops.gin_aggregate(T, rowptr, col, eps, graph.num_nodes, D, bias=bp, epilogue=epilogue, p_drop=p_drop, seed=seed,
-                                seed_dev=seed_dev)
+    return T, ops.gin_aggregate_hubs(T, rowptr, col, eps, graph.num_nodes, D, bias=bp, epilogue=epilogue, p_drop=p_drop, seed=seed,
+                                     seed_dev=seed_dev, hubs=hubs[0] if hubs is not None else None)
 
 
 class _GinLayerFn(torch.autograd.Function):
@@ -35,14 +44,15 @@ class _GinLayerFn(torch.autograd.Function):
     dW = dT^T x, dx = dT W.  A buffer eps (no gradient wanted) keeps no T and runs no eps pass."""
 
     @staticmethod
-    def forward(ctx, x, w, b, eps, graph, epilogue, p_drop, seed, seed_dev=None):
+    def forward(ctx, x, w, b, eps, graph, epilogue, p_drop, seed, seed_dev=None, hubs=None):
         D = w.shape[0]
         wp = _pad_rows(w.detach())
         T, y = _layer_forward(x.detach(), wp, _pad_bias(b.detach(), D) if b is not None else None, eps.detach(), D, graph, epilogue,
-                              p_drop, seed, seed_dev)
+                              p_drop, seed, seed_dev, hubs)
         want_eps = eps.requires_grad
         ctx.save_for_backward(x, wp, eps)
         ctx.T = T if want_eps else None
+        ctx.t_hubs = hubs[1] if hubs is not None else None
         ctx.y, ctx.graph, ctx.cfg = y, graph, (D, epilogue, p_drop, b is not None, want_eps)
         return y[:, :D]
 
@@ -57,8 +67,9 @@ class _GinLayerFn(torch.autograd.Function):
             g[:, :D] = gy
             gy = g
         t_rowptr, t_dst = graph.by_dst[2], graph.by_dst[3]
-        dT, gb, ge = ops.gin_aggregate_bwd(ctx.T, y, gy, t_rowptr, t_dst, eps.detach(), N, D, epilogue=epilogue, p_drop=p_drop,
-                                           want_bias=has_b and ctx.needs_input_grad[2], want_eps=want_eps and ctx.needs_input_grad[3])
+        dT, gb, ge = ops.gin_aggregate_bwd_hubs(ctx.T, y, gy, t_rowptr, t_dst, eps.detach(), N, D, epilogue=epilogue, p_drop=p_drop,
+                                                want_bias=has_b and ctx.needs_input_grad[2],
+                                                want_eps=want_eps and ctx.needs_input_grad[3], hubs=ctx.t_hubs)
         xd = x.detach()
         dW = None
         if ctx.needs_input_grad[1]:
@@ -73,7 +84,7 @@ class _GinLayerFn(torch.autograd.Function):
                 gx = ops.linear(dT, wp.t().contiguous(), torch.zeros(din, dtype=torch.float32, device=x.device))
             else:
                 gx = dT.mm(wp)
-        return gx, dW, gb, (ge.reshape(eps.shape) if ge is not None else None), None, None, None, None, None
+        return gx, dW, gb, (ge.reshape(eps.shape) if ge is not None else None), None, None, None, None, None, None
 
 
 class GINConv(nn.Module):
@@ -105,8 +116,10 @@ class GINConv(nn.Module):
         with torch.no_grad():
             self.eps.fill_(self.initial_eps)
 
-    def run(self, x, graph, epilogue=None, p_drop=0.0):
-        """conv output with an optional fused epilogue ("relu" then dropout at p_drop, or "log_softmax"); graph: SageGraph."""
+    def run(self, x, graph, epilogue=None, p_drop=0.0, hubs=None):
+        """conv output with an optional fused epilogue ("relu" then dropout at p_drop, or "log_softmax"); graph: SageGraph.  hubs:
+        None (every row is walked by one lane group, the default) or `graph_hubs(graph)`: hub rows of the forward and hub sources of
+        the backward are summed in segments across the grid."""
         _no_cpu(x)
         if x.shape[1] != self.in_channels:
             raise ValueError(f"GINConv: x must have {self.in_channels} columns, got {x.shape[1]}")
@@ -118,10 +131,10 @@ class GINConv(nn.Module):
         seed, seed_dev = dropout_seed(kern_p, step_word=False)       # a captured epoch: 0 and this layer's device word
         x = x.float()
         if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad) or eps.requires_grad):
-            out = _GinLayerFn.apply(x, w, b, eps, graph, kern_epi, float(kern_p), seed, seed_dev)
+            out = _GinLayerFn.apply(x, w, b, eps, graph, kern_epi, float(kern_p), seed, seed_dev, hubs)
         else:
             out = _layer_forward(x, _pad_rows(w.detach()), _pad_bias(b.detach(), D) if b is not None else None, eps.detach(), D, graph,
-                                 kern_epi, float(kern_p), seed, seed_dev)[1][:, :D]
+                                 kern_epi, float(kern_p), seed, seed_dev, hubs)[1][:, :D]
         if torch_epi:
             out = F.log_softmax(out, dim=1)
         return out
@@ -143,11 +156,14 @@ class GINNet(nn.Module):
     """models/backbones.py:26-57 on the HIP aggregation.  Same constructor and state_dict keys (convs.{i}.eps, convs.{i}.nn.weight,
     convs.{i}.nn.bias), parameters drawn in the reference's order; layer_num == 1 builds `GINConv(Linear(F, C))` with a buffer eps,
     as the reference does.  `dropout` (default the reference's hard-coded 0.5) lets tests switch it off.  forward ->
-    log-probabilities.  Dropout sites in forward order: one per conv but the last."""
+    log-probabilities.  Dropout sites in forward order: one per conv but the last.  `segment_hubs=True` sums rows (and, in the
+    backward, sources) of at least `ops.GIN_HUB_THRESHOLD` edges in segments of `ops.GIN_HUB_SEGMENT` across the grid; off by default:
+    a hub's sum is then added in another order, within the same bound but not the same bits."""
 
-    def __init__(self, dataset, layer_num=2, hidden=16, dropout=0.5):
+    def __init__(self, dataset, layer_num=2, hidden=16, dropout=0.5, segment_hubs=False):
         super().__init__()
         self.dropout = float(dropout)
+        self.segment_hubs = bool(segment_hubs)
         F_in, C = dataset.num_features, dataset.num_classes
         self.convs = nn.ModuleList()
         if layer_num == 1:
@@ -180,9 +196,10 @@ class GINNet(nn.Module):
         _no_cpu(x)
         g = self.graph(data.edge_index, x.shape[0])
         p = self.dropout if self.training else 0.0
+        hubs = graph_hubs(g) if self.segment_hubs else None
         for ind, conv in enumerate(self.convs):
             last = ind == len(self.convs) - 1
-            x = conv.run(x, g, epilogue="log_softmax" if last else "relu", p_drop=0.0 if last else p)
+            x = conv.run(x, g, epilogue="log_softmax" if last else "relu", p_drop=0.0 if last else p, hubs=hubs)
         return x
 
 

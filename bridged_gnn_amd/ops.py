@@ -1413,6 +1413,30 @@ def _gin_need_cfg(what, D, epilogue, p_drop):
         raise ValueError(f"{what}: the fused log_softmax serves D <= 128, got {D}")
 
 
+# rows with at least GIN_HUB_THRESHOLD edges are cut into segments of GIN_HUB_SEGMENT edges (bgnn_gin_aggregate_hub_f32): GCN's
+# values -- the lane group and its depth of 8 gathers a round are the same
+GIN_HUB_THRESHOLD = 256
+GIN_HUB_SEGMENT = 128
+
+
+def _gin_hub_args(hubs, D, dev, head_bytes=0):
+    """hubs: (threshold, hub_rows, hub_seg_ptr, seg_bounds) -> the hub arguments of the GIN hub entries (without the workspace) and
+    the workspace: `head_bytes` for the caller, then the partial rows"""
+    if len(hubs) != 4:
+        raise ValueError("hubs must be (threshold, hub_rows, hub_seg_ptr, seg_bounds)")
+    thr, rows, seg_ptr, bounds = hubs
+    for t, what in ((rows, "hub_rows"), (seg_ptr, "hub_seg_ptr"), (bounds, "seg_bounds")):
+        L._check_device(t)
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"hubs: {what} must be a contiguous int32 vector")
+    if int(thr) < 1 or seg_ptr.shape[0] != rows.shape[0] + 1 or bounds.shape[0] % 2:
+        raise ValueError("hubs: threshold >= 1, hub_seg_ptr [n_hubs + 1], seg_bounds [2 n_seg]")
+    n_seg = int(bounds.shape[0]) // 2
+    wsb = int(head_bytes) + int(L.lib().bgnn_gin_aggregate_hub_workspace_bytes(n_seg, int(D)))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    return (int(thr), L.ptr(rows), int(rows.shape[0]), L.ptr(seg_ptr), L.ptr(bounds), n_seg), ws
+
+
 def gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, out=None,
                   row_ids=None):
     """GIN sum aggregation (models/backbones.py:26-57: PyG GINConv(Linear, train_eps=True) after its transform; bgnn.h:
@@ -1425,7 +1449,21 @@ def gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias=None, epilogue=None, p_
     epilogue: None, "relu" (then dropout at p_drop, the (seed, element index) hash of `sage_mean_aggregate`) or "log_softmax"
     (D <= 128).  row_ids: int64 [n_rows], the GLOBAL row id of every output row (a rank's rows of a partition): the dropout element
     index is then row_ids[i] * D + column; None = row i itself.  Pad columns of out are written as 0.  No atomics, no host
-    synchronisation."""
+    synchronisation.  Hub rows walk as one lane group each: `gin_aggregate_hubs` segments them."""
+    return _gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias, epilogue, p_drop, seed, seed_dev, out, row_ids, None)
+
+
+def gin_aggregate_hubs(tbl, rowptr, col, eps, n_rows, D, bias=None, epilogue=None, p_drop=0.0, seed=0, seed_dev=None, out=None,
+                       row_ids=None, hubs=None):
+    """`gin_aggregate` (models/backbones.py:26-57; bgnn.h: bgnn_gin_aggregate_hub_f32) with segmented hub rows.  hubs: None -- the
+    call of `gin_aggregate`, the same launches and the same bits -- or (threshold, hub_rows, hub_seg_ptr, seg_bounds) from
+    `DstCSR.hub_tables(threshold, segment)` of the SAME view (`transposed_hub_tables` for the by-source view): those rows are summed
+    segment by segment across the grid, then finished (own row, bias, epilogue, the mask of row_ids[hub row]) by one lane group a hub.
+    Every other row carries the bits of `gin_aggregate`, and so does a hub of one segment."""
+    return _gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias, epilogue, p_drop, seed, seed_dev, out, row_ids, hubs)
+
+
+def _gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias, epilogue, p_drop, seed, seed_dev, out, row_ids, hubs):
     n_rows, D = int(n_rows), int(D)
     _gin_need_cfg("gin_aggregate", D, epilogue, p_drop)
     _gin_need_eps(eps)
@@ -1449,6 +1487,14 @@ def gin_aggregate(tbl, rowptr, col, eps, n_rows, D, bias=None, epilogue=None, p_
         _need_rows_f32(out, "out", D)
         if out.shape[0] != n_rows or out.data_ptr() == tbl.data_ptr():
             raise ValueError(f"out must have n_rows = {n_rows} rows and be distinct from tbl")
+    if hubs is not None:
+        hub_args, ws = _gin_hub_args(hubs, D, tbl.device)
+        rc = L.lib().bgnn_gin_aggregate_hub_f32(
+            L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(eps), L.ptr(bias), L.ptr(rowptr), L.ptr(col), int(col.shape[0]),
+            n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev), *hub_args, L.ptr(ws), ws.numel(),
+            L.ptr(row_ids), L.ptr_rows(out), out.stride(0), L.stream())
+        L.check(rc, "bgnn_gin_aggregate_hub_f32")
+        return out
     rc = L.lib().bgnn_gin_aggregate_f32(
         L.ptr_rows(tbl), tbl.stride(0), int(tbl.shape[0]), L.ptr(eps), L.ptr(bias), L.ptr(rowptr), L.ptr(col), int(col.shape[0]),
         n_rows, D, SAGE_EPILOGUES[epilogue], float(p_drop), *_seed_args(seed, seed_dev), L.ptr(row_ids), L.ptr_rows(out),
@@ -1467,6 +1513,19 @@ def gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue=N
     sums (`column_sums`), grad_eps = sum_i <g_i, tbl_i> from per-block fp64 partials summed in a fixed order, and
     grad_tbl[j] = (1 + eps) * g[j] + sum_{i : j -> i} g[i] from the forward walk over the swapped view with the same eps tensor.
     want_eps=False launches no eps pass.  No atomics: bit-identical from run to run; no host synchronisation."""
+    return _gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue, p_drop, want_bias, want_eps, grad_tbl, None)
+
+
+def gin_aggregate_bwd_hubs(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue=None, p_drop=0.0, want_bias=True, want_eps=True,
+                           grad_tbl=None, hubs=None):
+    """`gin_aggregate_bwd` (models/backbones.py:26-57; bgnn.h: bgnn_gin_aggregate_bwd_hub_f32) with the walk over the by-source view
+    segmented.  hubs: None -- the call of `gin_aggregate_bwd`, the same launches and bits -- or the hub tables of the BY-SOURCE view
+    (`DstCSR.transposed_hub_tables`): (threshold, hub_rows, hub_seg_ptr, seg_bounds).  A hub source j >= grad_y's rows (a rank's
+    halo slot) has no own term.  g, grad_bias and grad_eps are formed as without hubs."""
+    return _gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue, p_drop, want_bias, want_eps, grad_tbl, hubs)
+
+
+def _gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue, p_drop, want_bias, want_eps, grad_tbl, hubs):
     n_src, D = int(n_src), int(D)
     _gin_need_cfg("gin_aggregate_bwd", D, epilogue, p_drop)
     _gin_need_eps(eps)
@@ -1498,6 +1557,16 @@ def gin_aggregate_bwd(tbl, y, grad_y, t_rowptr, t_col, eps, n_src, D, epilogue=N
     grad_eps = ws = None
     if want_eps:
         grad_eps = torch.empty(1, dtype=torch.float32, device=dev)
+    if hubs is not None:
+        hub_args, ws = _gin_hub_args(hubs, D, dev, lib.bgnn_gin_aggregate_bwd_workspace_bytes(n_rows, D) if want_eps else 0)
+        rc = lib.bgnn_gin_aggregate_bwd_hub_f32(
+            L.ptr_rows(tbl) if want_eps else None, tbl.stride(0) if want_eps else 0, L.ptr_rows(y), y.stride(0) if y is not None else 0,
+            L.ptr_rows(grad_y), grad_y.stride(0), n_rows, L.ptr(t_rowptr), L.ptr(t_col), int(t_col.shape[0]), n_src, D, L.ptr(eps),
+            SAGE_EPILOGUES[epilogue], float(p_drop), *hub_args, L.ptr_rows(g), g.stride(0), L.ptr_rows(grad_tbl), grad_tbl.stride(0),
+            L.ptr(grad_eps), L.ptr(ws), ws.numel(), L.stream())
+        L.check(rc, "bgnn_gin_aggregate_bwd_hub_f32")
+        return grad_tbl, (column_sums(g)[:D] if want_bias else None), grad_eps
+    if want_eps:
         ws = torch.empty(max(int(lib.bgnn_gin_aggregate_bwd_workspace_bytes(n_rows, D)), 16), dtype=torch.uint8, device=dev)
     rc = lib.bgnn_gin_aggregate_bwd_f32(
         L.ptr_rows(tbl) if want_eps else None, tbl.stride(0) if want_eps else 0, L.ptr_rows(y), y.stride(0) if y is not None else 0,

@@ -53,7 +53,8 @@ extern "C" {
  * bgnn_gcn2_conv_rows_f32, and the DeeperGCN baseline's bgnn_gen_softmax_aggregate_f32, bgnn_gen_softmax_aggregate_bwd_f32 and
  * its workspace size, and the GIN baseline's bgnn_gin_aggregate_f32, bgnn_gin_aggregate_bwd_f32 and its workspace size, and the
  * JKNet baseline's bgnn_jk_gcn_aggregate_f32, bgnn_jk_gcn_aggregate_bwd_f32, bgnn_jk_head_supported, bgnn_jk_head_f32 and
- * bgnn_jk_max_route_f32. */
+ * bgnn_jk_max_route_f32, and the segmented hub rows of the GIN walk: bgnn_gin_aggregate_hub_f32, bgnn_gin_aggregate_bwd_hub_f32 and
+ * bgnn_gin_aggregate_hub_workspace_bytes. */
 #define BGNN_VERSION 116
 #define BGNN_E_NULL (-1)        /* required pointer is NULL                     */
 #define BGNN_E_SHAPE (-2)       /* unsupported / inconsistent shape             */
@@ -760,7 +761,7 @@ int bgnn_gen_softmax_aggregate_bwd_f32(const float* x, int64_t ldx, int64_t n_sr
  * output row for that hash, or NULL = row i), 2 log_softmax (D <= 128).  out: [n_rows, ldo], distinct from tbl; pad columns
  * D .. pad4(D)-1 are written as 0 whatever tbl holds there.  Leading dimensions in floats, % 4 == 0 and >= pad4(D) (tbl may be a
  * view of a wider table), bases 16-B aligned; BGNN_E_SHAPE / BGNN_E_ALIGN otherwise.  One lane group per row (the mapping of
- * bgnn_sage_mean_aggregate_f32), columns in slices of 128, a hub row walked by one group.  No float atomics, nothing allocated.
+ * bgnn_sage_mean_aggregate_f32), columns in slices of 128, a hub row walked by one group (the _hub_ entries below segment it).  No float atomics, nothing allocated.
  *
  * bgnn_gin_aggregate_bwd_f32 (models/backbones.py:26-57, the backward of the same aggregation):
  *     g_i        = the gradient at the epilogue's input from (y_i, grad_y_i): y > 0 ? grad_y * keep_scale : 0 (ReLU then dropout),
@@ -781,6 +782,45 @@ int bgnn_gin_aggregate_bwd_f32(const float* tbl_opt, int64_t ldt, const float* y
                                int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_edges, int64_t n_src,
                                int32_t D, const float* eps, int epilogue, float p_drop, float* g, int64_t ldg, float* grad_tbl,
                                int64_t ldgt, float* grad_eps_opt, void* ws_opt, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GIN sum aggregation with segmented hub rows (the GINNet baseline, models/backbones.py:26-57; the ROWS / SEGMENT / FINISH scheme of
+ * bgnn_gcn_aggregate_f32 on GIN's sum).  bgnn_gin_aggregate_hub_f32 computes what bgnn_gin_aggregate_f32 computes,
+ *     out_i = epi( (1 + eps) * tbl_i + sum over t in row i of tbl[col[t]] + bias ),
+ * with the same arguments plus the hub tables of the SAME view, in bgnn_gcn_aggregate_f32's order: hub_rows_opt [n_hubs] the rows
+ * of at least hub_threshold (>= 1) edges, hub_seg_ptr_opt [n_hubs+1] the segment range of each hub, seg_bounds_opt [2 n_seg] one
+ * (begin, end) pair of edge offsets per segment, n_seg >= n_hubs, ws_opt >= bgnn_gin_aggregate_hub_workspace_bytes(n_seg, D) bytes
+ * (BGNN_E_SHAPE / BGNN_E_NULL / BGNN_E_WORKSPACE otherwise).  n_hubs == 0 takes no table and launches what the entry without hubs
+ * launches.  With hubs three launches per 128-column slice:
+ *   ROWS     the row kernel neither gathers nor stores for a row of at least hub_threshold edges;
+ *   SEGMENT  one lane group per segment sums tbl[col[t]] over its pair (cut to [0, n_edges]; ids outside [0, n_tbl) are never
+ *            dereferenced) with the row walk's batches and compensated add into one partial row of ws: no own row, bias, epilogue;
+ *   FINISH   one lane group per hub adds its partial rows in segment order through the same compensated add (a segment range is
+ *            cut to [0, n_seg]), then fma(1 + eps, own, sum) with the own row read from tbl at hub_rows[h] where that is < n_tbl,
+ *            then bias and epilogue; under row_id_opt the mask is drawn for row_id[hub_rows[h]]; pad columns leave as 0; a hub
+ *            row outside [0, n_rows) is dropped.
+ * Every non-hub row carries the bits of the entry without hubs, and so does a hub of ONE segment; a hub's bits do not depend on
+ * which block took which segment.  No float atomics, nothing allocated.
+ *
+ * bgnn_gin_aggregate_bwd_hub_f32 (models/backbones.py:26-57, the backward of the same aggregation): g, grad_eps and
+ *     grad_tbl_j = (1 + eps) * g_j + sum over the out-edges j -> i of g_i        (g_j for j < n_rows)
+ * as the backward entry without hubs forms them -- pass A and the grad_eps passes are its launches -- with pass B, the walk over
+ * the by-source view (t_rowptr, t_col), run through the hub walk above: the tables are those of the by-source view, hub SOURCES
+ * j >= n_rows (a rank's halo slots) have no own term.  ws_opt: bgnn_gin_aggregate_bwd_workspace_bytes(n_rows, D) bytes first (only
+ * with grad_eps_opt), then bgnn_gin_aggregate_hub_workspace_bytes(n_seg, D) bytes. */
+size_t bgnn_gin_aggregate_hub_workspace_bytes(int64_t n_seg, int32_t D);
+int bgnn_gin_aggregate_hub_f32(const float* tbl, int64_t ldt, int64_t n_tbl, const float* eps, const float* bias_opt,
+                               const int32_t* rowptr, const int32_t* col, int64_t n_edges, int64_t n_rows, int32_t D, int epilogue,
+                               float p_drop, uint64_t seed, const uint64_t* seed_dev_opt, int32_t hub_threshold,
+                               const int32_t* hub_rows_opt, int64_t n_hubs, const int32_t* hub_seg_ptr_opt,
+                               const int32_t* seg_bounds_opt, int64_t n_seg, void* ws_opt, size_t ws_bytes,
+                               const int64_t* row_id_opt, float* out, int64_t ldo, void* stream);
+int bgnn_gin_aggregate_bwd_hub_f32(const float* tbl_opt, int64_t ldt, const float* y, int64_t ldy, const float* grad_y, int64_t ldgy,
+                                   int64_t n_rows, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_edges, int64_t n_src,
+                                   int32_t D, const float* eps, int epilogue, float p_drop, int32_t hub_threshold,
+                                   const int32_t* hub_rows_opt, int64_t n_hubs, const int32_t* hub_seg_ptr_opt,
+                                   const int32_t* seg_bounds_opt, int64_t n_seg, float* g, int64_t ldg, float* grad_tbl,
+                                   int64_t ldgt, float* grad_eps_opt, void* ws_opt, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * JKNet scaled-sum conv (the JKNet baseline, models/backbones.py:60-107: PyG GCNConv handed the already normalised adj_t_cache,
